@@ -9,13 +9,20 @@ GPU's HBM): STRONG scaling -- the same 10^8 ids, rank r takes ids r, r+N, ... (t
 interleave, unitig.c:333, 398-399) and the step ends with the one exchange of the pipeline: the packed
 overlap records of every rank gathered device-to-device on rank 0 over RCCL (xGMI).
 
-Further legs at N = 1 (same JSON line): check_left (unitig.c:186-204), backward search on configs[1]
-(10 M reads, its own index), SMEM and the k-mer harvest of `correct` on the raw-read index (configs[2]).
+A plain run sets up (synthetic reads in HBM, the index built on the GPU), warms up, times K steps of the headline and prints
+the JSON line: metric, value, unit, higher_is_better, dtype, ms_per_step (the K timed steps on the host clock between device
+synchronisations, over K).
+--full adds everything else, in the same JSON line: the index through fermi's .fmd file (the drop-in loader), check_left
+(unitig.c:186-204), backward search on configs[1] (10 M reads, its own index), SMEM and the k-mer harvest of `correct` on the
+raw-read index (configs[2]), the A/B runs, the CPU baselines with their parity checks, the rooflines with their counter passes,
+and at N > 1 the check of the gathered records and the product path.
+--dump-outputs DIR (N = 1): after the timed steps, a fixed sample of what the last one computed, as DIR/<name>.npy (dump_outputs in
+benchlegs/overlap.py), so that two builds can be compared output for output on the same inputs.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-roofline.achieved / frac are MEASURED HBM bytes: rocprofv3 --pmc FETCH_SIZE (x the calibration of the run's own 64-byte
+With --full, roofline.achieved / frac are MEASURED HBM bytes: rocprofv3 --pmc FETCH_SIZE (x the calibration of the run's own 64-byte
 gather probe) + WRITE_SIZE, separate passes spawned by this run over two steps of the leg, over the HIP-event time of
 the timed steps, over 8 TB/s (frac_basis says so; where no counter pass could run the requested-bytes figure stands
 in and frac_basis says that).  achieved_requested / frac_requested = the bytes the kernels ASK for: 64 B x rank blocks
@@ -24,7 +31,7 @@ streams the kernels read and write.  The SURVEY 8(d) accounting (128 B per rank 
 reported beside them as algorithmic_equivalent_GBps; it exceeds the peak because this layout needs far fewer bytes
 per query.
 
-Knobs: FMD_BENCH_READS (50_000_000), FMD_BENCH_BSEARCH_READS (10_000_000), FMD_BENCH_LEGS
+Knobs: FMD_BENCH_READS (50_000_000), FMD_BENCH_BSEARCH_READS (10_000_000), FMD_BENCH_LEGS with --full
 (overlap,check_left,bsearch,smem,kmer,ecfix), FMD_BENCH_CPU_SAMPLE* (bounded CPU samples).
 """
 import argparse
@@ -53,7 +60,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true", help="also the other legs, A/B runs, CPU baselines, parity checks and rooflines (off: the headline alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write a fixed sample of the last timed step's results as DIR/<name>.npy (N = 1)")
     args = ap.parse_args()
+    if args.dump_outputs and args.gpus > 1:
+        ap.error("--dump-outputs takes the results of one GPU's step: use it with --gpus 1")
 
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
         # launched plainly (`python bench.py --gpus N`): this process becomes the launcher -- N ranks of this same file through torch.distributed.run
@@ -65,7 +76,7 @@ def main():
         env = dict(os.environ)
         env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus), "--master-addr", "127.0.0.1",
-               "--master-port", str(port), os.path.abspath(__file__), "--gpus", str(args.gpus), "--steps", str(args.steps), "--warmup", str(args.warmup)]
+               "--master-port", str(port), os.path.abspath(__file__), "--gpus", str(args.gpus), "--steps", str(args.steps), "--warmup", str(args.warmup)] + (["--full"] if args.full else [])
         log("bench.py: --gpus %d without a launcher: %s" % (args.gpus, " ".join(cmd[1:])))
         sys.exit(subprocess.call(cmd, env=env))
     import torch
@@ -99,9 +110,9 @@ def main():
 
     n_reads = int(os.environ.get("FMD_BENCH_READS", "50000000"))
     L = 100
-    legs = os.environ.get("FMD_BENCH_LEGS", "overlap,check_left,bsearch,smem,kmer,ecfix" if world == 1 else "overlap").split(",")
+    legs = os.environ.get("FMD_BENCH_LEGS", "overlap,check_left,bsearch,smem,kmer,ecfix" if world == 1 else "overlap").split(",") if args.full else ["overlap"]
 
-    # ---- untimed set-up: synthetic reads in HBM -> GPU index build -> (rank 0, N = 1) .fmd -> drop-in loader.
+    # ---- untimed set-up: synthetic reads in HBM -> GPU index build -> (--full, rank 0) .fmd -> drop-in loader.
     # Every rank builds the same index from the same reads: the full index is replicated, nothing is shared.
     t0 = time.time()
     rd = workload.ReadsOnDevice.synth(n_reads, L, 30, 0.0, dev)
@@ -111,11 +122,11 @@ def main():
     torch.cuda.synchronize()
     t2 = time.time()
     fmd_path = None
-    if rank == 0:   # (N > 1 too: rank 0 prices its own shard -- roofline, CPU baseline, parity -- as the N = 1 line does)
+    if rank == 0 and args.full:   # (N > 1 too: rank 0 prices its own shard -- roofline, CPU baseline, parity -- as the N = 1 line does)
         fmd_path = os.path.join(tempfile.gettempdir(), "fmd_bench_%d_%d.fmd" % (n_reads, os.getpid()))
         workload.write_fmd_from_device_bwt(d_bwt, n_sym, fmd_path, local_rank)
     t3 = time.time()
-    if fmd_path:        # the drop-in path: load fermi's own file format
+    if fmd_path:        # the drop-in path: load fermi's own file format (the same index as from the device BWT)
         index = api.DevIndex.open(fmd_path, local_rank)
     else:
         index = api.DevIndex.from_bwt_dev(d_bwt, n_sym, local_rank)
@@ -143,7 +154,7 @@ def main():
         log("setup: synth in HBM %.1fs, GPU BWT build %.2fs (%d symbols), .fmd write %.1fs, index load+transcode %.2fs (%.2f GB in HBM)"
             % (t1 - t0, t2 - t1, n_sym, t3 - t2, t4 - t3, index.hbm_bytes / 1e9))
 
-    if rank == 0 and os.environ.get("FMD_BENCH_PROBE", "1") != "0":
+    if rank == 0 and args.full and os.environ.get("FMD_BENCH_PROBE", "1") != "0":
         try:
             nl = 1 << 27
             pms = api.probe_gather(8 << 30, 64, nl, iters=3, device=local_rank)
@@ -151,7 +162,8 @@ def main():
         except Exception:
             pass
     keep_fmd = rank == 0 and world == 1 and fmd_path and os.environ.get("FMD_BENCH_PMC", "1") != "0"
-    ovl, job = bench_overlap(torch, api, index, dev, n_reads, L, args.steps, args.warmup, dist, world, rank, fmd_path, local_rank, legs)
+    ovl, job = bench_overlap(torch, api, index, dev, n_reads, L, args.steps, args.warmup, dist, world, rank, fmd_path, local_rank, legs,
+                             full=args.full, dump_dir=args.dump_outputs)
     cl = None
     if rank == 0 and world == 1 and "check_left" in legs:
         cl = bench_check_left(torch, api, job, n_reads, max(1, min(args.steps, 3)), min(args.warmup, 1), fmd_path, ovl, local_rank)
@@ -173,7 +185,7 @@ def main():
     # fmd_ovlp_dist_step (one process per GPU behind the C ABI); this is the other path's rate, host side included, on the same .fmd, once.  The ranks have
     # closed their indexes; rank 0 opens the N replicas itself while the others wait at the barrier.
     product = None
-    if world > 1 or os.environ.get("FMD_BENCH_PRODUCT_TABLE") == "1":
+    if args.full and (world > 1 or os.environ.get("FMD_BENCH_PRODUCT_TABLE") == "1"):
         if rank == 0 and fmd_path and os.path.exists(fmd_path):
             try:
                 from fermi_amd import hostlib
@@ -214,7 +226,7 @@ def main():
                                                                     ", packed records gathered on rank 0 over RCCL inside the step" if world > 1 else ""),
                        "reads": n_reads, "read_len": L, "index_symbols": n_sym, "parallelism": "replicated index, sequence ids sharded x%d" % world},
             "index_build": {"symbols": n_sym, "gpu_bwt_seconds": t2 - t1, "symbols_per_s": n_sym / max(t2 - t1, 1e-9),
-                            "fmd_write_seconds": t3 - t2, "fmd_load_transcode_seconds": t4 - t3, "hbm_bytes": hbm_index},
+                            "fmd_write_seconds": t3 - t2 if fmd_path else None, "fmd_load_transcode_seconds": t4 - t3, "hbm_bytes": hbm_index},
             "kernel_sources_sha": csrc_sha(),
         }
         if pairs_info:

@@ -156,7 +156,9 @@ class OverlapJob:
         return self.gatherer(p["prec"], p["off"], p["var"])
 
 
-def bench_overlap(torch, api, index, dev, n_reads, L, steps, warmup, dist, world, rank, fmd_path, local_rank, legs):
+def bench_overlap(torch, api, index, dev, n_reads, L, steps, warmup, dist, world, rank, fmd_path, local_rank, legs, full, dump_dir):
+    """The headline leg: warm-up + timed steps, the JSON object of the leg; with `full`, the checks, A/B runs, roofline and CPU baseline
+    after the timed steps.  dump_dir (N = 1): dump_outputs of the last timed step, before anything else runs on its buffers."""
     min_match = int(os.environ.get("FMD_BENCH_MINMATCH", "50"))
     n_ids = 2 * n_reads
     # ---- N > 1: the step behind the C ABI (fmd_ovlp_dist_step): pass 1 on the id shard, [the parked strands all-to-all by key,] pass 2 in
@@ -242,7 +244,7 @@ def bench_overlap(torch, api, index, dev, n_reads, L, steps, warmup, dist, world
             dist.all_gather(kms, km)
             per_rank = [float(x.item()) for x in kms]
             gather_note = None
-            if rank == 0:
+            if rank == 0 and full:
                 try:
                     gather_note = fdist.check_table(torch, api, index, djob, n_ids, min_match, L, 4, dev)
                 except Exception as ex:   # the check must not take the benchmark line down
@@ -304,8 +306,8 @@ def bench_overlap(torch, api, index, dev, n_reads, L, steps, warmup, dist, world
     out = None
 
     # ---- N > 1, outside the timed region: rank 0 recomputes a sample of ids itself and compares with what arrived
-    if record_gather is None and world > 1 and rank == 0:
-        gather_note = None
+    gather_note = None
+    if full and record_gather is None and world > 1 and rank == 0:
         from fermi_amd import dist as fdist
         try:
             gather_note = fdist.check_gathered(torch, api, job, gathered[0], n_ids, world)
@@ -313,12 +315,15 @@ def bench_overlap(torch, api, index, dev, n_reads, L, steps, warmup, dist, world
             gather_note = "check failed to run: %r" % (ex,)
     if rank != 0:
         return None, job
-    g_rec = job.rec.cpu().numpy().view(api.OVLP_DT)
+    if dump_dir:
+        dump_outputs(torch, job, dump_dir)
+    g32 = job.rec.view(torch.int32).view(job.n, 16)     # the words of api.OVLP_DT: status 9, n_nei 13, flags 14
     out = {"metric": "reads/sec through unitig overlap discovery (fm_retrieve + fm6_is_contained + fm6_get_nei, both strands of every read)",
            "value": n_reads * steps / wall, "unit": "reads/s", "strands_per_s": n_ids * steps / wall,
            "ms_per_step": wall / steps * 1e3, "min_match": min_match, "batch_strands": job.batch, "strands_this_rank": job.n,
-           "overflow_records": int(((g_rec["flags"] & api.OVLP_F_OVERFLOW) != 0).sum()),
-           "contained": int((g_rec["status"] == -3).sum()), "with_neighbour": int((g_rec["n_nei"] > 0).sum())}
+           "overflow_records": int(((g32[:, 14] & api.OVLP_F_OVERFLOW) != 0).sum().item()),
+           "contained": int((g32[:, 9] == -3).sum().item()), "with_neighbour": int((g32[:, 13] > 0).sum().item())}
+    del g32
     if world > 1:
         if record_gather is not None:
             out["record_gather_rccl"] = record_gather
@@ -329,6 +334,9 @@ def bench_overlap(torch, api, index, dev, n_reads, L, steps, warmup, dist, world
                                          "discovery_kernels_ms_per_step_on_rank0": kern_ms}
         if not fmd_path:
             return out, job
+    if not full:
+        return out, job
+    g_rec = job.rec.cpu().numpy().view(api.OVLP_DT)
     n_loc = job.n               # rows of this rank (all of them at N = 1); everything below is about rank 0's own shard
     ids_host = job.ids.cpu().numpy().astype(np.uint64)
     # ---- the same job without the two-base blocks (FMD_PAIR_USE=0: pass 1 one base per request all the way), same box, same run: time and bytes
@@ -442,6 +450,34 @@ def bench_overlap(torch, api, index, dev, n_reads, L, steps, warmup, dist, world
         except Exception as ex:
             out["host_table_pcie_inclusive"] = {"error": repr(ex)}
     return out, job
+
+
+DUMP_ROWS = 1 << 15     # rows of the sample: 39 MB of .npy at 100 bp
+
+
+def dump_outputs(torch, job, d, rows=DUMP_ROWS, seed=20260928):
+    """What a caller of the step receives, for a fixed random sample of the sequence ids (the same sample in every run of the same size), as
+    .npy files in d: ids.npy (the sampled ids), records.npy (the 16 32-bit words of each record, api.OVLP_DT), neighbours.npy (the 8 32-bit
+    words of each of the max_nei intervals, api.INTV_DT; zero beyond the record's n_nei), sequences.npy (the row's bases, nt6; zero beyond
+    len + ext_len).  float64 holds every 32-bit word exactly; the bases are float32.  What lies beyond a row's used length is scratch of the
+    kernels, not output, and is left out as the id-order A/B leaves it out."""
+    os.makedirs(d, exist_ok=True)
+    n = job.n
+    sel = np.sort(np.random.default_rng(seed).choice(n, min(rows, n), replace=False))
+    sel_d = torch.from_numpy(sel).to(job.dev)
+    rec = job.rec.view(torch.int32).view(n, 16)[sel_d]
+    nn = rec[:, 13].clamp(0, job.max_nei)
+    nei = job.nei.view(torch.int32).view(n, job.max_nei, 8)[sel_d]
+    nei = nei * (torch.arange(job.max_nei, device=job.dev)[None, :] < nn[:, None])[:, :, None]
+    used = (rec[:, 8] + rec[:, 12].clamp(min=0)).clamp(0, job.stride)
+    seq = job.seq.view(n, job.stride)[sel_d]
+    seq = seq * (torch.arange(job.stride, device=job.dev)[None, :] < used[:, None])
+    u32 = lambda t: t.cpu().numpy().view(np.uint32).astype(np.float64)
+    np.save(os.path.join(d, "ids.npy"), job.ids[sel_d].cpu().numpy().astype(np.float64))
+    np.save(os.path.join(d, "records.npy"), u32(rec))
+    np.save(os.path.join(d, "neighbours.npy"), u32(nei))
+    np.save(os.path.join(d, "sequences.npy"), seq.cpu().numpy().astype(np.float32))
+    log("outputs of the last timed step: %d of %d rows in %s" % (len(sel), n, d))
 
 
 def bench_check_left(torch, api, job, n_reads, steps, warmup, fmd_path, ovl, local_rank):

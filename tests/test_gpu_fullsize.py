@@ -35,13 +35,13 @@ def _md5_stream(cmd, env=None):
 
 
 def test_50m_reads_every_leg_bit_exact_on_random_samples(gpu):
-    """bench.py exactly as the driver runs it (default sizes: configs[2] / configs[3] at 5*10^7 reads -- 1.01*10^10 symbols, the 64-bit kernels --, configs[1] at 10^7), one
+    """bench.py --full as the driver runs it (default sizes: configs[2] / configs[3] at 5*10^7 reads -- 1.01*10^10 symbols, the 64-bit kernels --, configs[1] at 10^7), one
     step per leg: what the driver's bench line would only say in a string turns this suite red."""
     env = dict(os.environ, FMD_BENCH_CPU_SAMPLE="200000", FMD_BENCH_CPU_SAMPLE_OVLP="100000", FMD_BENCH_CPU_SAMPLE_SMEM="100000", FMD_BENCH_CPU_SAMPLE_KMER="2048",
                FMD_BENCH_CPU_SAMPLE_ECFIX="100000", FMD_BENCH_CPU_SAMPLE_OVLP_RAW="50000", FMD_BENCH_PROBE="0", FMD_BENCH_PMC="0", FMD_BENCH_HOST_API="0")
     for k in ("FMD_BENCH_READS", "FMD_BENCH_BSEARCH_READS", "FMD_BENCH_LEGS"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env, timeout=900)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0", "--full"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env, timeout=900)
     assert p.returncode == 0, p.stderr.decode()[-2000:]
     d = json.loads(p.stdout.decode().strip().splitlines()[-1])
     assert d["config"]["reads"] == 50_000_000 and d["overlap_discovery"]["strands_this_rank"] == 100_000_000 and d["config"]["index_symbols"] == 10_100_000_000
@@ -120,13 +120,13 @@ def test_10m_reads_cli_md5_equals_the_reference(gpu, tmp_path):
 
 
 def test_bench_n2_path_sharded_ids_and_gather_on_one_gpu(gpu):
-    """`python bench.py --gpus 2` launched PLAINLY, as the driver's N = 1 command is: bench.py becomes its own launcher (N ranks of itself through
+    """`python bench.py --gpus 2 --full` launched PLAINLY, as the driver's N = 1 command is: bench.py becomes its own launcher (N ranks of itself through
     torch.distributed.run, one per GPU), here with both ranks on GPU 0 and gloo instead of RCCL (FMD_BENCH_BACKEND / FMD_BENCH_SHARE_GPU): rank r
     computes the ids i = r (mod 2), the packed rows are gathered on rank 0 inside the timed step, and rank 0 recomputes a sample of rank 1's rows."""
     env = dict(os.environ, FMD_BENCH_READS="1000000", FMD_BENCH_BACKEND="gloo", FMD_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full"],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env, timeout=600)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     d = json.loads([l for l in p.stdout.decode().splitlines() if l.startswith("{")][-1])

@@ -1,6 +1,7 @@
-"""The CPU leg of bench.py's ec_fix line, pinned where /root/reference was compiled (oracle/_ref): the reference's own static ec_fix through
+"""The CPU leg of bench.py's ec_fix line, pinned where the reference was compiled (oracle/_ref): the reference's own static ec_fix through
 oracle/ref_ec_harness.c:refec_fix, its tables filled from the golden solid table of tiny.fmd, must print `fermi correct -t1`'s FASTQ; and bench.py's
-numpy form of the marking rule (correct.c:247-252) must agree with it.  No GPU."""
+numpy form of the marking rule (correct.c:247-252) must agree with it -- with refec_fix run here where oracle/_ref was built, and everywhere with
+its output stored in tests/golden/tiny_refec_fix.npz (tests/golden/make_ref_ecfix.py).  No GPU."""
 import os
 import sys
 
@@ -52,10 +53,8 @@ def test_refec_fix_prints_fermi_correct(gold, oracle_lib, threads, monkeypatch):
     assert n_kept == len(want) and n_kept >= 2000   # (every record of the golden output has been compared)
 
 
-def test_marking_rule_in_numpy_equals_the_reference(gold, oracle_lib):
-    """the oracle's ec_fix (nt6 bases, qualities and info BEFORE the marking: the contract of fmd_ecfix_dev) + bench.mark_corrected == refec_fix (after it)"""
-    if bench.ref_ec_lib() is None:
-        pytest.skip("oracle/_ref/libref_ec.so not built here")
+def _marking_inputs(gold):
+    """tiny.fq's reads of 100 bases and 400 more that the filter rejects"""
     ids, nt6, q = _fixed_len(gold)
     rng = np.random.default_rng(3)
     extra = nt6[:400].copy()                                      # reads the filter rejects: other genomes, reads with a third of their bases changed, Ns
@@ -63,10 +62,18 @@ def test_marking_rule_in_numpy_equals_the_reference(gold, oracle_lib):
     for r in extra[100:300]:
         r[rng.choice(len(r), 35, replace=False)] = rng.integers(1, 5, size=35)
     extra[300:, ::17] = 5
-    nt6 = np.concatenate([nt6, extra]); q = np.concatenate([q, q[:400]])
+    return np.concatenate([nt6, extra]), np.concatenate([q, q[:400]])
+
+
+def test_marking_rule_in_numpy_equals_the_reference(gold, oracle_lib):
+    """the oracle's ec_fix (nt6 bases, qualities and info BEFORE the marking: the contract of fmd_ecfix_dev) + bench.mark_corrected == refec_fix (after it)"""
+    nt6, q = _marking_inputs(gold)
     v = gold.npz("tiny_solid.npz")
-    (txt, q2, info), _, _, _, _, _ = bench.cpu_ecfix(17, 2, 5, _sorted_trip(v), nt6, q)
+    want = gold.npz("tiny_refec_fix.npz")
+    if bench.ref_ec_lib() is not None:
+        (txt, q2, info), _, _, _, kind, _ = bench.cpu_ecfix(17, 2, 5, _sorted_trip(v), nt6, q)
+        assert kind == "reference" and np.array_equal(txt, want["text"]) and np.array_equal(q2, want["qual"]) and np.array_equal(info, want["info"])
     s, qq, off, inf = orcbind.ec_fix(17, v["w17_o3_bucket"], v["w17_o3_key"], v["w17_o3_val"], list(nt6), list(q))
     m_txt, m_q, m_inf = bench.mark_corrected(nt6, s.reshape(nt6.shape), qq.reshape(nt6.shape), inf)
-    assert np.array_equal(m_txt, txt) and np.array_equal(m_q, q2) and np.array_equal(m_inf, info)
+    assert np.array_equal(m_txt, want["text"]) and np.array_equal(m_q, want["qual"]) and np.array_equal(m_inf, want["info"])
     assert (m_txt >= ord("a")).sum() > 1000 and (m_inf >> 16 & 1).sum() > 100

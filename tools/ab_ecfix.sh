@@ -2,10 +2,11 @@
 # same-box A/B of builds of the library over the ec_fix leg (k-mer harvest for its table, then k_ecfix over 5*10^7 raw reads; PMC traffic measured in the run):
 #   tools/ab_ecfix.sh libA.so libB.so ...
 export FMD_BENCH_CPU_SAMPLE=20000 FMD_BENCH_CPU_SAMPLE_KMER=256 FMD_BENCH_PROBE=1
-mkdir -p gpurun_out/ab_ecfix
+OUT=${OUT:-out}/ab_ecfix
+mkdir -p $OUT
 for lib in "$@"; do
-  FMD_HIP_LIB=$PWD/fermi_amd/lib/$lib FMD_BENCH_LEGS=kmer,ecfix timeout 900 python bench.py --steps 3 --warmup 1 > gpurun_out/ab_ecfix/$lib.json 2> gpurun_out/ab_ecfix/$lib.err
-  python - $lib gpurun_out/ab_ecfix/$lib.json <<'PY'
+  FMD_HIP_LIB=$PWD/fermi_amd/lib/$lib FMD_BENCH_LEGS=kmer,ecfix timeout 900 python bench.py --steps 3 --warmup 1 --full > $OUT/$lib.json 2> $OUT/$lib.err
+  python - $lib $OUT/$lib.json <<'PY'
 import json, sys
 try:
     d = json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])

@@ -6,7 +6,7 @@ for lib in "$@"; do
   for pass in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU" "SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SMEM SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE"; do
     tag=$(echo $pass | cut -d' ' -f1)
     rm -rf $OUT/$lib.$tag
-    FMD_HIP_LIB=$PWD/fermi_amd/lib/$lib timeout 900 rocprofv3 --pmc $pass --output-format csv -d $OUT/$lib.$tag -o t -- python bench.py --steps 1 --warmup 0 > /dev/null 2> $OUT/$lib.$tag.err
+    FMD_HIP_LIB=$PWD/fermi_amd/lib/$lib timeout 900 rocprofv3 --pmc $pass --output-format csv -d $OUT/$lib.$tag -o t -- python bench.py --steps 1 --warmup 0 --full > /dev/null 2> $OUT/$lib.$tag.err
     f=$(find $OUT/$lib.$tag -name "*counter_collection.csv" | head -1)
     python - "$lib" "$f" <<'PY'
 import csv, sys
