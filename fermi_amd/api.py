@@ -38,6 +38,7 @@ ABI_SYMBOLS = [
     "fmd_comm_rccl_unique_id", "fmd_comm_rccl_init", "fmd_comm_rccl_version", "fmd_comm_rccl_count", "fmd_comm_free",
     "fmd_ovlp_side_work_bytes", "fmd_ovlp_rerun_overflow_dev",
     "fmd_ovlp_dist_new", "fmd_ovlp_dist_step", "fmd_ovlp_dist_table", "fmd_ovlp_dist_local", "fmd_ovlp_dist_free",
+    "fmd_dev_open_file_ex", "fmd_dev_open_bwt_ex", "fmd_merge_work_bytes", "fmd_merge_walk_dev", "fmd_merge_interleave_dev", "fmd_dev_merge", "fmd_dev_merge_ex", "fmd_memset_dev",
 ]
 
 
@@ -70,6 +71,14 @@ def _configure(L):
     L.fmd_dev_open_rle6.argtypes = [C.c_int, vp, C.c_uint64, C.POINTER(vp)]
     L.fmd_dev_open_bwt.argtypes = [C.c_int, vp, C.c_uint64, C.POINTER(vp)]
     L.fmd_dev_open_bwt_dev.argtypes = [C.c_int, vp, C.c_uint64, C.POINTER(vp)]
+    L.fmd_dev_open_file_ex.argtypes = [C.c_int, C.c_char_p, C.c_uint, C.POINTER(vp)]
+    L.fmd_dev_open_bwt_ex.argtypes = [C.c_int, vp, C.c_uint64, C.c_uint, C.POINTER(vp)]
+    L.fmd_merge_work_bytes.restype = sz; L.fmd_merge_work_bytes.argtypes = [C.c_uint64]
+    L.fmd_merge_walk_dev.argtypes = [vp, vp, vp, vp, vp, sz, C.POINTER(C.c_int)]
+    L.fmd_merge_interleave_dev.argtypes = [vp, vp, vp, vp, vp, C.c_uint64, C.c_uint64, vp]
+    L.fmd_dev_merge.argtypes = [vp, vp, C.POINTER(vp)]
+    L.fmd_dev_merge_ex.argtypes = [vp, vp, C.c_uint, C.POINTER(vp)]
+    L.fmd_memset_dev.argtypes = [vp, C.c_int, sz, vp]
     L.fmd_dev_close.restype = None; L.fmd_dev_close.argtypes = [vp]
     L.fmd_dev_trim.restype = C.c_uint64; L.fmd_dev_trim.argtypes = [vp]
     L.fmd_dev_info.argtypes = [vp, C.POINTER(Info)]
@@ -256,6 +265,20 @@ class DevIndex:
         h = C.c_void_p()
         check(lib().fmd_dev_open_rle6(device, _ptr(runs), len(runs), C.byref(h)))
         return cls(h)
+
+    @classmethod
+    def open_bare(cls, fn, device=0):
+        """rld_restore without the prefix and tail tables (fmd_dev_open_file_ex, FMD_OPEN_NO_TABLES): enough to rank, decode, merge"""
+        h = C.c_void_p()
+        check(lib().fmd_dev_open_file_ex(device, fn.encode(), 1, C.byref(h)))
+        return cls(h)
+
+    def merge(self, other, tables=True):
+        """fm_merge (merge.c:100): a new resident index of this index's sequences followed by other's; both stay as they are
+        (tables=False: without the prefix and tail tables, fmd_dev_merge_ex(.., FMD_OPEN_NO_TABLES))"""
+        h = C.c_void_p()
+        check(lib().fmd_dev_merge_ex(self.h, other.h, 0 if tables else 1, C.byref(h)))
+        return DevIndex(h)
 
     def refresh_info(self):
         """cnt / mcnt / bytes again (the handle may have grown: fmd_dev_build_pairs)"""

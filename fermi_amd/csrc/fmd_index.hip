@@ -357,8 +357,8 @@ static int dev_alloc_index(int device, uint64_t n_sym, fmd_dev **out)
     return FMD_OK;
 }
 
-// counts -> scan -> meta; also fills cnt/mcnt from the device counts
-static int finish_index(fmd_dev *h)
+// counts -> scan -> meta; also fills cnt/mcnt from the device counts; tables = 0: no prefix / tail table (FMD_OPEN_NO_TABLES)
+static int finish_index(fmd_dev *h, int tables = 1)
 {
     const uint64_t nb = h->n_blocks;
     fmd_bc_t *bc = nullptr; uint64_t *acc = nullptr;
@@ -389,8 +389,8 @@ static int finish_index(fmd_dev *h)
         else if (h->cnt[6] != h->mcnt[0]) rc = FMD_E_FORMAT;
     }
     hipFree(bc); hipFree(acc);
-    if (rc == FMD_OK) rc = build_ptab(h);
-    if (rc == FMD_OK) rc = build_tail(h);
+    if (rc == FMD_OK && tables) rc = build_ptab(h);
+    if (rc == FMD_OK && tables) rc = build_tail(h);
     return rc;
 }
 
@@ -402,7 +402,7 @@ int fmd_index_alloc(int device, uint64_t n_sym, fmd_dev **out)
     if (rc == FMD_OK) (*out)->mcnt[0] = n_sym;
     return rc;
 }
-int fmd_index_finish(fmd_dev *h) { return finish_index(h); }
+int fmd_index_finish(fmd_dev *h, int tables) { return finish_index(h, tables); }
 // one thread per 32-position word that the slice [first, first + m) touches; border words are shared with the
 // neighbouring slices, which are written before / after this launch on the same stream: plain OR
 __global__ void k_slice_to_planes(const uint8_t *__restrict__ slice, uint64_t first, uint64_t m, uint4 *__restrict__ blocks)
@@ -430,7 +430,7 @@ int fmd_index_put_slice(fmd_dev *h, hipStream_t st, const uint8_t *d_slice, uint
     return hipGetLastError() == hipSuccess ? FMD_OK : FMD_E_HIP;
 }
 
-extern "C" int fmd_dev_open_bwt_dev(int device, const uint8_t *d_bwt, uint64_t n, fmd_dev_t **out)
+static int open_bwt_dev(int device, const uint8_t *d_bwt, uint64_t n, int tables, fmd_dev_t **out)
 {
     if (!d_bwt || !out) return FMD_E_ARG;
     fmd_dev *h = nullptr;
@@ -439,13 +439,14 @@ extern "C" int fmd_dev_open_bwt_dev(int device, const uint8_t *d_bwt, uint64_t n
     h->mcnt[0] = n;
     const uint64_t n_chunks = (n + 31) / 32;
     k_bwt_to_planes<<<nblk(n_chunks, 256), 256>>>(d_bwt, n, h->blocks, n_chunks);
-    rc = finish_index(h);
+    rc = finish_index(h, tables);
     if (rc) { fmd_dev_close(h); return rc; }
     *out = h;
     return FMD_OK;
 }
+extern "C" int fmd_dev_open_bwt_dev(int device, const uint8_t *d_bwt, uint64_t n, fmd_dev_t **out) { return open_bwt_dev(device, d_bwt, n, 1, out); }
 
-extern "C" int fmd_dev_open_bwt(int device, const uint8_t *bwt, uint64_t n, fmd_dev_t **out)
+static int open_bwt(int device, const uint8_t *bwt, uint64_t n, int tables, fmd_dev_t **out)
 {
     if (!bwt || !out) return FMD_E_ARG;
     if (fmd_device_count() <= 0) return FMD_E_NODEV;
@@ -453,12 +454,13 @@ extern "C" int fmd_dev_open_bwt(int device, const uint8_t *bwt, uint64_t n, fmd_
     uint8_t *d = nullptr;
     FMD_HIP_TRY(hipMalloc((void **)&d, n + 64));
     hipError_t e = hipMemcpy(d, bwt, n, hipMemcpyHostToDevice);
-    int rc = e == hipSuccess ? fmd_dev_open_bwt_dev(device, d, n, out) : FMD_E_HIP;
+    int rc = e == hipSuccess ? open_bwt_dev(device, d, n, tables, out) : FMD_E_HIP;
     hipFree(d);
     return rc;
 }
+extern "C" int fmd_dev_open_bwt(int device, const uint8_t *bwt, uint64_t n, fmd_dev_t **out) { return open_bwt(device, bwt, n, 1, out); }
 
-extern "C" int fmd_dev_open_rle6(int device, const uint8_t *runs, uint64_t n_bytes, fmd_dev_t **out)
+static int open_rle6(int device, const uint8_t *runs, uint64_t n_bytes, int tables, fmd_dev_t **out)
 {
     if (!runs || !out || n_bytes == 0) return FMD_E_ARG;
     if (fmd_device_count() <= 0) return FMD_E_NODEV;
@@ -484,16 +486,20 @@ extern "C" int fmd_dev_open_rle6(int device, const uint8_t *runs, uint64_t n_byt
     if (rc) goto done;
     h->mcnt[0] = n_sym;
     k_rle6_scatter<<<nblk(n_bytes, 256), 256>>>(d_runs, n_bytes, d_start, (uint32_t *)h->blocks, d_tot);
-    rc = finish_index(h);
+    // the runs go before the counts' scratch comes (hipFree waits for the scatter): the load's peak is the larger of the two, not their sum
+    hipFree(d_runs); hipFree(d_len); hipFree(d_start); hipFree(d_tot);
+    d_runs = nullptr; d_len = d_start = d_tot = nullptr;
+    rc = finish_index(h, tables);
 done:
     hipFree(d_runs); hipFree(d_len); hipFree(d_start); hipFree(d_tot);
     if (rc) { if (h) fmd_dev_close(h); return rc; }
     *out = h;
     return FMD_OK;
 }
+extern "C" int fmd_dev_open_rle6(int device, const uint8_t *runs, uint64_t n_bytes, fmd_dev_t **out) { return open_rle6(device, runs, n_bytes, 1, out); }
 
 // The payload words of an RLD\2 file, already in device memory ((n_words / 8 + 1) * 64 bytes, zero behind the payload): the index.  Frees d_w.
-static int open_rld_words_dev(int device, uint64_t *d_w, uint64_t n_words, const uint64_t mcnt[7], fmd_dev_t **out)
+static int open_rld_words_dev(int device, uint64_t *d_w, uint64_t n_words, const uint64_t mcnt[7], int tables, fmd_dev_t **out)
 {
     // blocks 0 .. last/8-1 carry payload; the block at word `last` is header-only (rld.h:64)
     const uint64_t n_rld = n_words / 8;
@@ -515,7 +521,10 @@ static int open_rld_words_dev(int device, uint64_t *d_w, uint64_t n_words, const
         hipMemcpy(tot, d_tot, 16, hipMemcpyDeviceToHost);
         if (tot[1] || tot[0] != mcnt[0]) { rc = FMD_E_FORMAT; goto done; }
     }
-    rc = finish_index(h);
+    // the payload goes before the counts' scratch comes: the load's peak is the larger of the two, not their sum
+    hipFree(d_w); hipFree(d_size); hipFree(d_start); hipFree(d_tot);
+    d_w = d_size = d_start = d_tot = nullptr;
+    rc = finish_index(h, tables);
     if (rc == FMD_OK)
         for (int s = 1; s < 7; ++s) if (h->mcnt[s] != mcnt[s]) rc = FMD_E_FORMAT; // header vs decoded stream
 done:
@@ -536,7 +545,7 @@ extern "C" int fmd_dev_open_rld(int device, const uint64_t *payload, uint64_t n_
     FMD_HIP_TRY(hipMalloc((void **)&d_w, (n_rld + 1) * 64));
     hipMemset(d_w, 0, (n_rld + 1) * 64);
     hipMemcpy(d_w, payload, n_words * 8, hipMemcpyHostToDevice);
-    return open_rld_words_dev(device, d_w, n_words, mcnt, out);
+    return open_rld_words_dev(device, d_w, n_words, mcnt, 1, out);
 }
 
 // The payload of a large .fmd goes from the file to the device in pieces, several threads each reading a piece into its own pinned buffer and sending it
@@ -573,7 +582,7 @@ static int upload_payload(int device, int fd, off_t at, uint64_t bytes, uint8_t 
 // .fmd file: header = "RLD\2", u32 asize<<16|sbits, u64 0, u64 n_bytes, u64 n_frames, u64 mcnt[1..6]
 // (rld.c:242-263); anything else is treated as a raw run-length byte stream after a 4-byte
 // magic, as rld_restore does (rld.c:295-308).
-extern "C" int fmd_dev_open_file(int device, const char *fn, fmd_dev_t **out)
+static int open_file(int device, const char *fn, int tables, fmd_dev_t **out)
 {
     if (!fn || !out) return FMD_E_ARG;
     FILE *fp = fopen(fn, "rb");
@@ -607,7 +616,7 @@ extern "C" int fmd_dev_open_file(int device, const char *fn, fmd_dev_t **out)
             rc = upload_payload(device, fileno(fp), at, n_words * 8, (uint8_t *)d_w);
             fclose(fp); // the rank frames that follow are not needed: the device layout has none
             if (rc) { hipFree(d_w); return rc; }
-            return open_rld_words_dev(device, d_w, n_words, mcnt, out);
+            return open_rld_words_dev(device, d_w, n_words, mcnt, tables, out);
         }
     } else {
         fseek(fp, 0, SEEK_END);
@@ -618,10 +627,22 @@ extern "C" int fmd_dev_open_file(int device, const char *fn, fmd_dev_t **out)
         if (!buf) { fclose(fp); return FMD_E_NOMEM; }
         if (fread(buf, 1, (size_t)sz - 4, fp) != (size_t)sz - 4) { free(buf); fclose(fp); return FMD_E_IO; }
         fclose(fp);
-        rc = fmd_dev_open_rle6(device, buf, (uint64_t)sz - 4, out);
+        rc = open_rle6(device, buf, (uint64_t)sz - 4, tables, out);
         free(buf);
         return rc;
     }
+}
+extern "C" int fmd_dev_open_file(int device, const char *fn, fmd_dev_t **out) { return open_file(device, fn, 1, out); }
+// the same without the prefix and tail tables (FMD_OPEN_NO_TABLES): an index that is only ranked and decoded -- the inputs of a merge
+extern "C" int fmd_dev_open_file_ex(int device, const char *fn, unsigned flags, fmd_dev_t **out)
+{
+    if (flags & ~FMD_OPEN_NO_TABLES) return FMD_E_ARG;
+    return open_file(device, fn, !(flags & FMD_OPEN_NO_TABLES), out);
+}
+extern "C" int fmd_dev_open_bwt_ex(int device, const uint8_t *bwt, uint64_t n, unsigned flags, fmd_dev_t **out)
+{
+    if (flags & ~FMD_OPEN_NO_TABLES) return FMD_E_ARG;
+    return open_bwt(device, bwt, n, !(flags & FMD_OPEN_NO_TABLES), out);
 }
 
 // ---- inspection: what `fermi chkbwt -p / -r` and the tests need --------------------------------
@@ -775,6 +796,12 @@ extern "C" int fmd_memcpy_d2h(void *h_dst, const void *d_src, size_t bytes, void
     return FMD_OK;
 }
 
+extern "C" int fmd_memset_dev(void *d_dst, int value, size_t bytes, void *stream)
+{
+    if (!d_dst && bytes) return FMD_E_ARG;
+    FMD_HIP_TRY(hipMemsetAsync(d_dst, value, bytes, (hipStream_t)stream));
+    return FMD_OK;
+}
 extern "C" int fmd_dev_sync(const fmd_dev_t *h, void *stream)
 {
     if (!h) return FMD_E_ARG;

@@ -73,7 +73,7 @@ void fmd_scratch_release(fmd_dev *h, void *p);
 // the in-place index builder's hooks into fmd_index.hip
 int fmd_index_alloc(int device, uint64_t n_sym, fmd_dev **out);
 int fmd_index_put_slice(fmd_dev *h, hipStream_t st, const uint8_t *d_slice, uint64_t first, uint64_t m);
-int fmd_index_finish(fmd_dev *h);
+int fmd_index_finish(fmd_dev *h, int tables = 1);   // tables = 0: no prefix / tail table (FMD_OPEN_NO_TABLES)
 
 // the two-base blocks (fmd_pair.hip): built when forced (fmd_dev_build_pairs) or FMD_PAIR asks, and they fit; FMD_OK either way (h->pair says)
 int fmd_pairs_ensure(fmd_dev *h, int force);

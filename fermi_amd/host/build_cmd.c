@@ -2,7 +2,9 @@
  * sequences, convert to nt6, trim even-length self-reverse-complement reads by one base unless -O
  * (cmd.c:457-463), build the BWT of  read $ revcomp $ ...  on the GPU (fmd_build_bwt) and write the
  * RLD\2 container the reference writes (rld_writer.c).  The output file is byte-identical to
- * `fermi build`'s; -b (block size) other than 3 and -i (append to an index) are not supported. */
+ * `fermi build`'s; -b (block size) other than 3 is not supported.  With -i FILE (cmd.c:390-397: fm_build appends to
+ * the loaded index through fm_merge, build.c:40) the new reads' BWT is built the same way and merged after FILE's
+ * sequences on the GPU (merge_cmd.c). */
 #define _GNU_SOURCE
 #include <limits.h>
 #include <pthread.h>
@@ -39,7 +41,23 @@ static void *prep_main(void *d)
 typedef struct { uint8_t *dst; const fmdh_ppart_t *p; } cpy_t;
 static void *cpy_main(void *d) { cpy_t *c = (cpy_t *)d; memcpy(c->dst, c->p->seq, c->p->bytes); return 0; }
 
+/* the new reads' BWT (host bytes) after the sequences of the index `append` -> out_path */
+static int append_bwt(const char *append, const uint8_t *bwt, uint64_t n_sym, int device, const char *out_path)
+{
+    fmd_dev_t *h0 = 0, *h1 = 0;
+    int rc = fmd_dev_open_file_ex(device, append, FMD_OPEN_NO_TABLES, &h0);
+    if (rc) { fprintf(stderr, "[E::%s] Fail to open the index file `%s': %s.\n", __func__, append, fmd_strerror(rc)); return 1; }
+    rc = fmd_dev_open_bwt_ex(device, bwt, n_sym, FMD_OPEN_NO_TABLES, &h1);
+    if (rc) { fprintf(stderr, "[E::%s] %s\n", __func__, fmd_strerror(rc)); fmd_dev_close(h0); return 1; }
+    return fmdh_merge_pair_to_file(h0, h1, out_path);
+}
+
 int fmdh_build(const char *fa_path, const char *out_path, int device, int max_len, int no_fr)
+{
+    return fmdh_build_append(fa_path, out_path, device, max_len, no_fr, 0);
+}
+
+int fmdh_build_append(const char *fa_path, const char *out_path, int device, int max_len, int no_fr, const char *append)
 {
     const int timing = getenv("FMD_TIMING") != 0;
     const double t0 = now_s();
@@ -92,7 +110,7 @@ int fmdh_build(const char *fa_path, const char *out_path, int device, int max_le
     uint64_t n_sym = 0;
     const double t1 = now_s();
     double t2;
-    if (getenv("FMD_BUILD_RUNS")) {
+    if (getenv("FMD_BUILD_RUNS") && !append) {
         /* Opt-in (FMD_BUILD_RUNS=1): the BWT stays on the device and leaves it as runs (`len << 3 | sym` bytes, fmd_bwt_to_rle6) instead of a byte per
          * symbol; the container written from them is the same file (neighbouring runs of one symbol are merged by every reader of that stream,
          * rld_writer.c).  Measured (tools/ab_build.py, profiles/r4_e2e): 10^7 reads 3.5 s against 4.2 s, but at 5*10^7 the forty chunks of run-length
@@ -124,6 +142,7 @@ int fmdh_build(const char *fa_path, const char *out_path, int device, int max_le
         rc = bwt ? fmd_build_bwt(device, n, bases, off, bwt, &n_sym) : FMD_E_NOMEM;
         t2 = now_s();
         if (rc) fprintf(stderr, "[E::%s] BWT construction failed: %s\n", __func__, fmd_strerror(rc));
+        else if (append) rc = append_bwt(append, bwt, n_sym, device, out_path);
         else {
             rc = fmdh_write_rld_from_bwt(bwt, n_sym, out_path);
             if (rc) fprintf(stderr, "[E::%s] cannot write `%s'\n", __func__, out_path);

@@ -337,6 +337,13 @@ int fmdh_slim_build_dev(fmd_dev_t *dev, int min_match, fmdh_slim_t **out, uint64
 
 /* `fermi build -o out.fmd <in.fa>` (cmd.c:378-484); no_fr = trim palindromes (default 1) */
 int fmdh_build(const char *fa_path, const char *out_path, int device, int max_len, int no_fr);
+/* the same merged after the sequences of the index `append` (`fermi build -i`, cmd.c:390-397); append = NULL: fmdh_build */
+int fmdh_build_append(const char *fa_path, const char *out_path, int device, int max_len, int no_fr, const char *append);
+/* merge_cmd.c: `fermi merge` (cmd.c:335-376) of n_in >= 2 .fmd files, left to right, into out_path ("-" = stdout);
+ * `fermi recode` (cmd.c:674-685); h0's sequences then h1's into out_path -- both handles are closed, whatever happens */
+int fmdh_merge(int n_in, char *const *in, const char *out_path, int device);
+int fmdh_recode(const char *in, int device, const char *out_path);
+int fmdh_merge_pair_to_file(fmd_dev_t *h0, fmd_dev_t *h1, const char *out_path);
 
 /* `fermi correct` (cmd.c:253-291, correct.c:305-456); defaults = cmd.c:258 */
 typedef struct { int w, min_occ, keep_bad, is_paired, trim_l, step; float max_corr; } fmdh_ecopt_t; /* = fmecopt_t, fermi.h:26-29 */

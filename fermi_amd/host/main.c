@@ -84,7 +84,7 @@ static int parse_gpus(const char *arg, int *devices, int max)
 static int main_build(int argc, char *argv[]) /* cmd.c:378-484 */
 {
     int c, force = 0, max_len = 0x7fffffff, no_fr = 1, device = 0;
-    const char *out = "-";
+    const char *out = "-", *append = 0;
     while ((c = getopt(argc, argv, "fb:o:i:s:l:Og:")) >= 0) {
         switch (c) {
         case 'f': force = 1; break;
@@ -94,12 +94,19 @@ static int main_build(int argc, char *argv[]) /* cmd.c:378-484 */
         case 's': break;   /* symbols per SA-IS block: the GPU sorts everything at once */
         case 'g': device = atoi(optarg); break;
         case 'b': if (atoi(optarg) != 3) { fprintf(stderr, "[E::%s] only -b 3 is supported\n", __func__); return 1; } break;
-        case 'i': fprintf(stderr, "[E::%s] -i (append to an index) is not supported\n", __func__); return 1;
+        case 'i': {
+            FILE *fp = fopen(optarg, "rb");
+            if (!fp) { fprintf(stderr, "[E::%s] Fail to open the index file `%s'.\n", __func__, optarg); return 1; }
+            fclose(fp);
+            append = optarg;
+            break;
+        }
         }
     }
     if (argc == optind) {
         fprintf(stderr, "\nUsage:   fermi-amd build [options] <in.fa>\n\n");
         fprintf(stderr, "Options: -f        force to overwrite the output file (effective with -o)\n");
+        fprintf(stderr, "         -i FILE   append the FM-index to the existing FILE [null]\n");
         fprintf(stderr, "         -l INT    trim read down to INT bp [inf]\n");
         fprintf(stderr, "         -o FILE   output file name [stdout]\n");
         fprintf(stderr, "         -O        do not trim 1bp for reads whose forward and reverse are identical\n");
@@ -110,7 +117,43 @@ static int main_build(int argc, char *argv[]) /* cmd.c:378-484 */
         FILE *fp = fopen(out, "rb");
         if (fp) { fclose(fp); fprintf(stderr, "[E::%s] File `%s' exists. Please use `-f' to overwrite.\n", __func__, out); return 1; }
     }
-    return fmdh_build(argv[optind], out, device, max_len, no_fr);
+    return append ? fmdh_build_append(argv[optind], out, device, max_len, no_fr, append) : fmdh_build(argv[optind], out, device, max_len, no_fr);
+}
+
+static int main_merge(int argc, char *argv[]) /* cmd.c:335-376 */
+{
+    int c, force = 0, device = 0;
+    const char *out = "-";
+    while ((c = getopt(argc, argv, "fo:t:g:")) >= 0) {
+        switch (c) {
+        case 'f': force = 1; break;
+        case 'o': out = optarg; break;
+        case 't': if (atoi(optarg) > 0) setenv("FMD_RLD_THREADS", optarg, 1); break;   /* threads of the host encoder (rld_writer.c) */
+        case 'g': device = atoi(optarg); break;
+        }
+    }
+    if (optind + 2 > argc) {
+        fprintf(stderr, "\n");
+        fprintf(stderr, "Usage:   fermi-amd merge [-f] [-o out.bwt] [-t nThreads] [-g GPU] <in0.bwt> <in1.bwt> [...]\n\n");
+        fprintf(stderr, "Options: -f        force to overwrite the output file (effective with -o)\n");
+        fprintf(stderr, "         -o FILE   output file name [null]\n");
+        fprintf(stderr, "         -t INT    number of threads of the host encoder [16]\n");
+        fprintf(stderr, "         -g INT    GPU to use [0]\n\n");
+        return 1;
+    }
+    if (strcmp(out, "-") && !force) {
+        FILE *fp = fopen(out, "r");
+        if (fp) { fclose(fp); fprintf(stderr, "[E::%s] File `%s' exists. Please use `-f' to overwrite.\n", __func__, out); return 1; }
+    }
+    return fmdh_merge(argc - optind, argv + optind, out, device);
+}
+
+static int main_recode(int argc, char *argv[]) /* cmd.c:674-685 */
+{
+    int c, device = 0;
+    while ((c = getopt(argc, argv, "g:")) >= 0) if (c == 'g') device = atoi(optarg);
+    if (optind == argc) { fprintf(stderr, "Usage: fermi-amd recode [-g GPU] <in.rld>\n"); return 1; }
+    return fmdh_recode(argv[optind], device, "-");
 }
 
 static int main_exact(int argc, char *argv[]) /* cmd.c:292-331 */
@@ -290,6 +333,8 @@ int main(int argc, char *argv[])
         fprintf(stderr, "\nProgram: fermi-amd (FMD-index hot path of fermi on AMD MI355X)\n\n");
         fprintf(stderr, "Usage:   fermi-amd <command> [arguments]\n\n");
         fprintf(stderr, "Command: build      generate the FMD-index (fermi build)\n");
+        fprintf(stderr, "         merge      merge FMD-indexes (fermi merge)\n");
+        fprintf(stderr, "         recode     RLE\\6 -> RLD\\2 (fermi recode)\n");
         fprintf(stderr, "         seqsort    rank -> read index map for `unitig -r` (fermi seqsort)\n");
         fprintf(stderr, "         unitig     construct unitigs (fermi unitig)\n");
         fprintf(stderr, "         correct    error correction (fermi correct)\n");
@@ -314,6 +359,8 @@ int main(int argc, char *argv[])
     if (timing) fprintf(stderr, "[M::main] the runtime is up: %.3f s\n", main_now() - t_start);
     if (strcmp(argv[1], "unitig") == 0) rc = main_unitig(argc - 1, argv + 1);
     else if (strcmp(argv[1], "build") == 0) rc = main_build(argc - 1, argv + 1);
+    else if (strcmp(argv[1], "merge") == 0) rc = main_merge(argc - 1, argv + 1);
+    else if (strcmp(argv[1], "recode") == 0) rc = main_recode(argc - 1, argv + 1);
     else if (strcmp(argv[1], "seqsort") == 0) rc = main_seqsort(argc - 1, argv + 1);
     else if (strcmp(argv[1], "exact") == 0) rc = main_exact(argc - 1, argv + 1);
     else if (strcmp(argv[1], "correct") == 0) rc = main_correct(argc - 1, argv + 1);

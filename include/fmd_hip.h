@@ -64,6 +64,12 @@ int fmd_dev_open_rld(int device, const uint64_t *payload, uint64_t n_words,
 int fmd_dev_open_rle6(int device, const uint8_t *runs, uint64_t n_bytes, fmd_dev_t **out); /* len<<3|sym bytes (ropebwt.c:132) */
 int fmd_dev_open_bwt(int device, const uint8_t *bwt, uint64_t n, fmd_dev_t **out);          /* plain nt6 BWT string, host */
 int fmd_dev_open_bwt_dev(int device, const uint8_t *d_bwt, uint64_t n, fmd_dev_t **out);    /* same, already in HBM */
+/* the same without the prefix and tail tables (FMD_OPEN_NO_TABLES; flags = 0: what the entries above build): an index that is
+ * only ranked and decoded -- the inputs of fmd_dev_merge -- needs neither, and at 2^31 symbols and more they are 4.3 GB + 8 bytes
+ * per sequence.  Every entry point works on such a handle; the overlap and search jobs take the steps the tables would save. */
+#define FMD_OPEN_NO_TABLES 1u
+int fmd_dev_open_file_ex(int device, const char *fn, unsigned flags, fmd_dev_t **out);
+int fmd_dev_open_bwt_ex(int device, const uint8_t *bwt, uint64_t n, unsigned flags, fmd_dev_t **out);
 void fmd_dev_close(fmd_dev_t *h);
 /* the work areas the handle keeps between calls of the host-buffer entries (fmd_*_batch, the table jobs) back to the device; -> bytes released.
  * (The reference's per-call vectors are freed per call, e.g. unitig.c:321-325; the handle keeps them because allocating 10-100 GB per call costs more than the call.) */
@@ -510,11 +516,31 @@ int fmd_builder_new(int device, uint64_t n_reads, uint32_t read_len, fmd_builder
 int fmd_builder_add_dev(fmd_builder_t *b, void *stream, uint64_t n, const uint8_t *d_reads);
 int fmd_builder_finish(fmd_builder_t *b, fmd_dev_t **out);
 void fmd_builder_free(fmd_builder_t *b);
+/* ---- merging two indexes: fm_merge (merge.c:100-134), fm_compute_gap_bits (merge.c:33-96) ------------------------------
+ * The merged index holds the sequences of h0 followed by those of h1 (what `fermi merge h0 h1`, `fermi build -i h0` and
+ * `fermi build` of the concatenated reads write).  Both handles on one device (FMD_E_ARG otherwise); neither is changed.
+ * n_tot = n0 + n1 symbols.  The smaller index (h1 on a tie) is the WALKED one: every sequence of it is LF-walked beside
+ * its insertion row in the other, and the rows it lands on are set in d_bits.
+ * walk: d_bits = (n_tot + 63) / 64 words, zeroed by the caller; bit p set = merged row p comes from the walked index
+ *       (*walked = 0: h0, 1: h1; may be NULL).  It also leaves the prefix counts of d_bits in d_work (work_bytes >=
+ *       fmd_merge_work_bytes(n_tot)), which the interleave reads.
+ * interleave: merged BWT[first, first + n) as nt6 bytes into d_out, from d_bits / d_work of a walk of the same two handles.
+ * Both enqueue on `stream` and return; they allocate nothing.  fmd_dev_merge: the whole merge into a new resident index
+ * (FMD_E_NOMEM when the inputs, the merged index and the bit array do not fit together); fmd_dev_merge_ex with
+ * FMD_OPEN_NO_TABLES: the same without the prefix and tail tables (a result that is only merged again or decoded). */
+size_t fmd_merge_work_bytes(uint64_t n_tot);
+int fmd_merge_walk_dev(fmd_dev_t *h0, fmd_dev_t *h1, void *stream, uint64_t *d_bits, void *d_work, size_t work_bytes, int *walked);
+int fmd_merge_interleave_dev(fmd_dev_t *h0, fmd_dev_t *h1, void *stream, const uint64_t *d_bits, const void *d_work,
+                             uint64_t first, uint64_t n, uint8_t *d_out);
+int fmd_dev_merge(fmd_dev_t *h0, fmd_dev_t *h1, fmd_dev_t **out);
+int fmd_dev_merge_ex(fmd_dev_t *h0, fmd_dev_t *h1, unsigned flags, fmd_dev_t **out);
+
 /* device memory for C hosts (the reference has no device; these are what a cgo/C caller uses to
  * stage batches): plain hipMalloc / hipMemcpyAsync behind the ABI. */
 int fmd_dev_malloc(int device, size_t bytes, void **d_ptr);
 int fmd_memcpy_h2d(void *d_dst, const void *h_src, size_t bytes, void *stream);
 int fmd_memcpy_d2h(void *h_dst, const void *d_src, size_t bytes, void *stream);
+int fmd_memset_dev(void *d_dst, int value, size_t bytes, void *stream);   /* hipMemsetAsync: enqueued, not synchronised (the zeroed bit array of fmd_merge_walk_dev) */
 /* device BWT -> host RLE\6 byte stream (`len<<3|sym`, ropebwt.c:132-136); *h_rle6 is malloc'ed,
  * release with fmd_host_free().  Prefix it with "RLE\6" and it is a .fmd the reference loads. */
 int fmd_bwt_to_rle6(int device, const uint8_t *d_bwt, uint64_t n, uint8_t **h_rle6, uint64_t *n_bytes);
