@@ -39,6 +39,7 @@ ABI_SYMBOLS = [
     "fmd_ovlp_side_work_bytes", "fmd_ovlp_rerun_overflow_dev",
     "fmd_ovlp_dist_new", "fmd_ovlp_dist_step", "fmd_ovlp_dist_table", "fmd_ovlp_dist_local", "fmd_ovlp_dist_free",
     "fmd_dev_open_file_ex", "fmd_dev_open_bwt_ex", "fmd_merge_work_bytes", "fmd_merge_walk_dev", "fmd_merge_interleave_dev", "fmd_dev_merge", "fmd_dev_merge_ex", "fmd_memset_dev",
+    "fmd_contrast_work_bytes", "fmd_contrast_dev", "fmd_contrast", "fmd_sub_work_bytes", "fmd_sub_mark_dev", "fmd_sub_select_dev", "fmd_dev_sub",
 ]
 
 
@@ -79,6 +80,13 @@ def _configure(L):
     L.fmd_dev_merge.argtypes = [vp, vp, C.POINTER(vp)]
     L.fmd_dev_merge_ex.argtypes = [vp, vp, C.c_uint, C.POINTER(vp)]
     L.fmd_memset_dev.argtypes = [vp, C.c_int, sz, vp]
+    L.fmd_contrast_work_bytes.restype = sz; L.fmd_contrast_work_bytes.argtypes = [C.c_uint64]
+    L.fmd_contrast_dev.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, sz, C.c_uint64, vp]
+    L.fmd_contrast.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(vp), C.POINTER(vp)]
+    L.fmd_sub_work_bytes.restype = sz; L.fmd_sub_work_bytes.argtypes = [C.c_uint64]
+    L.fmd_sub_mark_dev.argtypes = [vp, vp, vp, vp, vp, sz, vp]
+    L.fmd_sub_select_dev.argtypes = [vp, vp, vp, vp, C.c_int, C.c_uint64, C.c_uint64, vp]
+    L.fmd_dev_sub.argtypes = [vp, vp, C.c_int, C.c_uint, C.POINTER(vp)]
     L.fmd_dev_close.restype = None; L.fmd_dev_close.argtypes = [vp]
     L.fmd_dev_trim.restype = C.c_uint64; L.fmd_dev_trim.argtypes = [vp]
     L.fmd_dev_info.argtypes = [vp, C.POINTER(Info)]
@@ -278,6 +286,28 @@ class DevIndex:
         (tables=False: without the prefix and tail tables, fmd_dev_merge_ex(.., FMD_OPEN_NO_TABLES))"""
         h = C.c_void_p()
         check(lib().fmd_dev_merge_ex(self.h, other.h, 0 if tables else 1, C.byref(h)))
+        return DevIndex(h)
+
+    def contrast(self, other, k=55, min_occ=3):
+        """fm6_contrast (cmp.c:94): (bits0, bits1), np.uint64 words with one bit per sequence of this index / of other in SORTED order
+        (bit i = the i-th '$' of the BWT; fm6_sub_conv with the `seqsort` ranks turns it into sequence numbers): set where the sequence runs through a string of up to k bases that the other index lacks"""
+        a, b = C.c_void_p(), C.c_void_p()
+        check(lib().fmd_contrast(self.h, other.h, k, min_occ, C.byref(a), C.byref(b)))
+        out = []
+        for p, d in ((a, self), (b, other)):
+            nw = (int(d.mcnt[1]) + 63) // 64
+            out.append(np.ctypeslib.as_array((C.c_uint64 * max(nw, 1)).from_address(p.value))[:nw].astype(np.uint64, copy=True))
+            lib().fmd_host_free(p)
+        return out[0], out[1]
+
+    def sub(self, bits, complement=False, tables=True):
+        """fm_sub (sub.c:71): a new resident index of the sequences whose bit (by sequence number = sentinel row) is set in `bits` -- complement=True: of
+        the others, `fermi sub -c` -- (tables=False: without the prefix and tail tables)"""
+        bits = np.ascontiguousarray(bits, dtype=np.uint64)
+        if len(bits) != (int(self.mcnt[1]) + 63) // 64:
+            raise FmdError("sub: the bit array has %d words, the index %d sequences" % (len(bits), int(self.mcnt[1])))
+        h = C.c_void_p()
+        check(lib().fmd_dev_sub(self.h, _ptr(bits), int(bool(complement)), 0 if tables else 1, C.byref(h)))
         return DevIndex(h)
 
     def refresh_info(self):

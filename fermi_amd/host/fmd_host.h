@@ -344,6 +344,11 @@ int fmdh_build_append(const char *fa_path, const char *out_path, int device, int
 int fmdh_merge(int n_in, char *const *in, const char *out_path, int device);
 int fmdh_recode(const char *in, int device, const char *out_path);
 int fmdh_merge_pair_to_file(fmd_dev_t *h0, fmd_dev_t *h1, const char *out_path);
+/* contrast_cmd.c: `fermi contrast` (cmd.c:589-638; the two sides in argv order: index, rank file, output bit array), `fermi sub`
+ * (cmd.c:640-672; out_path "-" = stdout) and `fermi bitand` (cmd.c:717-743; no GPU) */
+int fmdh_contrast(const char *const fmd[2], const char *const rank_fn[2], const char *const out[2], int k, int min_occ, int device);
+int fmdh_sub(const char *fmd_path, const char *bits_path, int is_comp, int device, const char *out_path);
+int fmdh_bitand(int n_in, char *const *in, FILE *out);
 
 /* `fermi correct` (cmd.c:253-291, correct.c:305-456); defaults = cmd.c:258 */
 typedef struct { int w, min_occ, keep_bad, is_paired, trim_l, step; float max_corr; } fmdh_ecopt_t; /* = fmecopt_t, fermi.h:26-29 */

@@ -156,6 +156,51 @@ static int main_recode(int argc, char *argv[]) /* cmd.c:674-685 */
     return fmdh_recode(argv[optind], device, "-");
 }
 
+static int main_contrast(int argc, char *argv[]) /* cmd.c:589-638 */
+{
+    int c, min_occ = 3, k = 55, device = 0;
+    while ((c = getopt(argc, argv, "k:o:t:g:")) >= 0) {
+        switch (c) {
+        case 'k': k = atoi(optarg); break;
+        case 'o': min_occ = atoi(optarg); break;
+        case 't': break;                 /* worker threads of the reference's walk: the GPU does it, the output does not depend on it */
+        case 'g': device = atoi(optarg); break;
+        }
+    }
+    if (optind + 6 > argc) {
+        fprintf(stderr, "\nUsage:   fermi-amd contrast [options] <idx1.fmd> <idx1.rank> <1-2.sub> <idx2.fmd> <idx2.rank> <2-1.sub>\n\n");
+        fprintf(stderr, "Options: -o INT    minimum occurrence [%d]\n", min_occ);
+        fprintf(stderr, "         -t INT    accepted, no effect (the walk runs on the GPU)\n");
+        fprintf(stderr, "         -k INT    k-mer length [%d]\n", k);
+        fprintf(stderr, "         -g INT    GPU to use [0]\n\n");
+        return 1;
+    }
+    {
+        const char *fmd[2] = {argv[optind], argv[optind + 3]}, *rank[2] = {argv[optind + 1], argv[optind + 4]}, *out[2] = {argv[optind + 2], argv[optind + 5]};
+        return fmdh_contrast(fmd, rank, out, k, min_occ, device);
+    }
+}
+
+static int main_sub(int argc, char *argv[]) /* cmd.c:640-672 */
+{
+    int c, is_comp = 0, device = 0;
+    while ((c = getopt(argc, argv, "ct:g:")) >= 0) {
+        switch (c) {
+        case 'c': is_comp = 1; break;
+        case 't': if (atoi(optarg) > 0) setenv("FMD_RLD_THREADS", optarg, 1); break;   /* threads of the host encoder (rld_writer.c) */
+        case 'g': device = atoi(optarg); break;
+        }
+    }
+    if (optind + 2 > argc) { fprintf(stderr, "Usage: fermi-amd sub [-c] [-t nThreads] [-g GPU] <in.fmd> <array.bits>\n"); return 1; }
+    return fmdh_sub(argv[optind], argv[optind + 1], is_comp, device, "-");
+}
+
+static int main_bitand(int argc, char *argv[]) /* cmd.c:717-743 */
+{
+    if (argc < 3) { fprintf(stderr, "Usage: fermi-amd bitand <in1.bit> <in2.bit> [...]\n"); return 1; }
+    return fmdh_bitand(argc - 1, argv + 1, stdout);
+}
+
 static int main_exact(int argc, char *argv[]) /* cmd.c:292-331 */
 {
     int c, self_match = 0, devices[FMDH_MAX_GPUS] = {0}, n_dev = 1;
@@ -335,6 +380,9 @@ int main(int argc, char *argv[])
         fprintf(stderr, "Command: build      generate the FMD-index (fermi build)\n");
         fprintf(stderr, "         merge      merge FMD-indexes (fermi merge)\n");
         fprintf(stderr, "         recode     RLE\\6 -> RLD\\2 (fermi recode)\n");
+        fprintf(stderr, "         contrast   reads with k-mers the other index lacks (fermi contrast)\n");
+        fprintf(stderr, "         sub        sub-index of selected reads (fermi sub)\n");
+        fprintf(stderr, "         bitand     AND of bit arrays, no GPU needed (fermi bitand)\n");
         fprintf(stderr, "         seqsort    rank -> read index map for `unitig -r` (fermi seqsort)\n");
         fprintf(stderr, "         unitig     construct unitigs (fermi unitig)\n");
         fprintf(stderr, "         correct    error correction (fermi correct)\n");
@@ -351,6 +399,7 @@ int main(int argc, char *argv[])
     const int timing = getenv("FMD_TIMING") != 0;
     int rc;
     setvbuf(stdout, 0, _IOFBF, 4 << 20); /* the outputs are hundreds of MB of short lines */
+    if (strcmp(argv[1], "bitand") == 0) return main_bitand(argc - 1, argv + 1);   /* host only: runs where there is no GPU */
     { const int node = stay_on_one_node(argv[1]); if (timing && node >= 0) fprintf(stderr, "[M::main] the process stays on NUMA node %d\n", node); }
     if (fmd_device_count() <= 0) {
         fprintf(stderr, "[E::main] %s\n", fmd_strerror(FMD_E_NODEV));
@@ -361,6 +410,8 @@ int main(int argc, char *argv[])
     else if (strcmp(argv[1], "build") == 0) rc = main_build(argc - 1, argv + 1);
     else if (strcmp(argv[1], "merge") == 0) rc = main_merge(argc - 1, argv + 1);
     else if (strcmp(argv[1], "recode") == 0) rc = main_recode(argc - 1, argv + 1);
+    else if (strcmp(argv[1], "contrast") == 0) rc = main_contrast(argc - 1, argv + 1);
+    else if (strcmp(argv[1], "sub") == 0) rc = main_sub(argc - 1, argv + 1);
     else if (strcmp(argv[1], "seqsort") == 0) rc = main_seqsort(argc - 1, argv + 1);
     else if (strcmp(argv[1], "exact") == 0) rc = main_exact(argc - 1, argv + 1);
     else if (strcmp(argv[1], "correct") == 0) rc = main_correct(argc - 1, argv + 1);

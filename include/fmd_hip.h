@@ -535,6 +535,39 @@ int fmd_merge_interleave_dev(fmd_dev_t *h0, fmd_dev_t *h1, void *stream, const u
 int fmd_dev_merge(fmd_dev_t *h0, fmd_dev_t *h1, fmd_dev_t **out);
 int fmd_dev_merge_ex(fmd_dev_t *h0, fmd_dev_t *h1, unsigned flags, fmd_dev_t **out);
 
+/* ---- contrast assembly: fm6_contrast (cmp.c:94-126: contrast_core cmp.c:45-76, descend cmp.c:10-20, collect_tips cmp.c:22-43) --------
+ * The reads of each index that carry a string of up to k bases which the other index lacks, as one bit per sequence IN SORTED ORDER:
+ * bit i = the sequence whose '$' is the i-th of the BWT (the rows ok[0].x[0] .. of a backward extension, cmp.c:32-39) -- the array before
+ * fm6_sub_conv (cmp.c:128-144), which the caller applies with the .rank file (`seqsort`): bit i -> bit rank[i] >> 2, the sequence's number.  A string counts as present in an index
+ * only while it or the other side has >= min_occ occurrences on the way down (cmp.c:68).  Both handles on one device; the same
+ * handle twice is legal (all-zero arrays).  k <= 4 (cmp.c:101), min_occ < 1 and a null handle are FMD_E_ARG.
+ * fmd_contrast_dev: enqueues on `stream` and returns; allocates nothing.  d_sub0 / d_sub1: (n_seq + 63) / 64 words each, zeroed by
+ *   the caller, OR-ed into.  The trie is walked level by level through lists of `cap` entries each (>= 1024) in d_work
+ *   (work_bytes >= fmd_contrast_work_bytes(cap)); seed_mask (bit c-1 = base c, 0xf = all) restricts the walk to the strings that END
+ *   in one of those bases: the parts are disjoint and the union of their bits is the whole result.  d_status (device, 4 x u64):
+ *   [0] pair nodes expanded, [1] overflow flag -- a list was full: every bit set is right but some are missing, call again with a
+ *   larger cap or part by part into the same arrays --, [2] / [3] tip nodes expanded in h0 / h1.
+ * fmd_contrast: the host form; runs again with larger lists, or in four parts, until nothing overflows.  *sub0 / *sub1 are
+ *   malloc'ed (fmd_host_free). */
+size_t fmd_contrast_work_bytes(uint64_t cap);
+int fmd_contrast_dev(fmd_dev_t *h0, fmd_dev_t *h1, void *stream, int k, int min_occ, int seed_mask, uint64_t *d_sub0, uint64_t *d_sub1,
+                     void *d_work, size_t work_bytes, uint64_t cap, uint64_t *d_status);
+int fmd_contrast(fmd_dev_t *h0, fmd_dev_t *h1, int k, int min_occ, uint64_t **sub0, uint64_t **sub1);
+/* ---- the sub-index of selected sequences: fm_sub (sub.c:71-97: set_bits sub.c:14-28, gen_idx sub.c:30-55) -------------------------
+ * d_sub: one bit per sequence of h by its NUMBER, which is its sentinel's row ((n_seq + 63) / 64 words: what `fermi contrast` /
+ * `bitand` write behind their 8-byte length, i.e. after fm6_sub_conv).  Both strands of a read must be selected together for the result to be an FMD index (the reference does not check).
+ * mark: every selected sequence is LF-walked and the rows it visits are set in d_bits ((n_sym + 63) / 64 words, zeroed by the
+ *       caller); it leaves the prefix counts of d_bits in d_work (work_bytes >= fmd_sub_work_bytes(n_sym)) and the number of set
+ *       bits in *d_n_kept (device; may be NULL) -- the symbols of the sub-index; of its complement: n_sym minus that.
+ * select: rows [first, first + n) of the sub-index (is_comp: of the index of the sequences NOT selected, `fermi sub -c`) as nt6 bytes
+ *       into d_out, from d_bits / d_work of a mark of the same handle.
+ * Both enqueue on `stream` and return; they allocate nothing.  fmd_dev_sub: the whole of it, from a host bit array into a new
+ * resident index (flags as fmd_dev_merge_ex; FMD_E_ARG when no sequence is kept). */
+size_t fmd_sub_work_bytes(uint64_t n_sym);
+int fmd_sub_mark_dev(fmd_dev_t *h, void *stream, const uint64_t *d_sub, uint64_t *d_bits, void *d_work, size_t work_bytes, uint64_t *d_n_kept);
+int fmd_sub_select_dev(fmd_dev_t *h, void *stream, const uint64_t *d_bits, const void *d_work, int is_comp, uint64_t first, uint64_t n, uint8_t *d_out);
+int fmd_dev_sub(fmd_dev_t *h, const uint64_t *sub, int is_comp, unsigned flags, fmd_dev_t **out);
+
 /* device memory for C hosts (the reference has no device; these are what a cgo/C caller uses to
  * stage batches): plain hipMalloc / hipMemcpyAsync behind the ABI. */
 int fmd_dev_malloc(int device, size_t bytes, void **d_ptr);
