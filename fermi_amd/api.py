@@ -40,6 +40,8 @@ ABI_SYMBOLS = [
     "fmd_ovlp_dist_new", "fmd_ovlp_dist_step", "fmd_ovlp_dist_table", "fmd_ovlp_dist_local", "fmd_ovlp_dist_free",
     "fmd_dev_open_file_ex", "fmd_dev_open_bwt_ex", "fmd_merge_work_bytes", "fmd_merge_walk_dev", "fmd_merge_interleave_dev", "fmd_dev_merge", "fmd_dev_merge_ex", "fmd_memset_dev",
     "fmd_contrast_work_bytes", "fmd_contrast_dev", "fmd_contrast", "fmd_sub_work_bytes", "fmd_sub_mark_dev", "fmd_sub_select_dev", "fmd_dev_sub",
+    "fmd_fltuniq_table_bytes", "fmd_fltuniq_count_dev", "fmd_fltuniq_test_dev", "fmd_fltuniq", "fmd_fltuniq_table",
+    "fmd_fltuniq_open", "fmd_fltuniq_slot", "fmd_fltuniq_count", "fmd_fltuniq_test", "fmd_fltuniq_sync", "fmd_fltuniq_export", "fmd_fltuniq_close",
 ]
 
 
@@ -87,6 +89,18 @@ def _configure(L):
     L.fmd_sub_mark_dev.argtypes = [vp, vp, vp, vp, vp, sz, vp]
     L.fmd_sub_select_dev.argtypes = [vp, vp, vp, vp, C.c_int, C.c_uint64, C.c_uint64, vp]
     L.fmd_dev_sub.argtypes = [vp, vp, C.c_int, C.c_uint, C.POINTER(vp)]
+    L.fmd_fltuniq_table_bytes.restype = sz; L.fmd_fltuniq_table_bytes.argtypes = [C.c_int]
+    L.fmd_fltuniq_count_dev.argtypes = [C.c_int, vp, C.c_int, vp, u64p, C.c_uint64, u64p]
+    L.fmd_fltuniq_test_dev.argtypes = [C.c_int, vp, C.c_int, vp, u64p, C.c_uint64, u64p, vp]
+    L.fmd_fltuniq.argtypes = [C.c_int, C.c_int, vp, u64p, C.c_uint64, vp]
+    L.fmd_fltuniq_table.argtypes = [C.c_int, C.c_int, vp, u64p, C.c_uint64, u64p]
+    L.fmd_fltuniq_open.argtypes = [C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.POINTER(vp)]
+    L.fmd_fltuniq_slot.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+    L.fmd_fltuniq_count.argtypes = [vp, C.c_uint64]
+    L.fmd_fltuniq_test.argtypes = [vp, C.c_uint64, vp]
+    L.fmd_fltuniq_sync.argtypes = [vp, vp]
+    L.fmd_fltuniq_export.argtypes = [vp, C.c_uint64, C.c_uint64, u64p]
+    L.fmd_fltuniq_close.restype = None; L.fmd_fltuniq_close.argtypes = [vp]
     L.fmd_dev_close.restype = None; L.fmd_dev_close.argtypes = [vp]
     L.fmd_dev_trim.restype = C.c_uint64; L.fmd_dev_trim.argtypes = [vp]
     L.fmd_dev_info.argtypes = [vp, C.POINTER(Info)]
@@ -576,6 +590,30 @@ def build_bwt(seqs, device=0):
     check(lib().fmd_build_bwt(device, n, _ptr(flat), _ptr(off), _ptr(bwt), C.byref(n_sym)))
     assert n_sym.value == len(bwt)
     return bwt
+
+
+def fltuniq_table_words(k):
+    """64-bit words of the k-mer state table of `fltuniq` (seq.c:161); raises for a k outside the range"""
+    nb = lib().fmd_fltuniq_table_bytes(int(k))
+    if nb == 0:
+        check(FMD_E_ARG)
+    return nb // 8
+
+
+def fltuniq_pass(seqs, k, device=0):
+    """main_fltuniq's verdict per read (seq.c:192-199) over nt6 reads: numpy bool, True = no non-base and no k-mer seen only once"""
+    flat, off = flatten_reads(seqs)
+    ok = np.zeros(max(len(off) - 1, 1), dtype=np.uint8)
+    check(lib().fmd_fltuniq(device, int(k), _ptr(flat), _ptr(off), len(off) - 1, _ptr(ok)))
+    return ok[:len(off) - 1].astype(bool)
+
+
+def fltuniq_table(seqs, k, device=0):
+    """the 2-bit k-mer states after pass 1 (seq.c:164-175) as the reference's flags[]: uint64 words"""
+    flat, off = flatten_reads(seqs)
+    tab = np.zeros(fltuniq_table_words(k), dtype=np.uint64)
+    check(lib().fmd_fltuniq_table(device, int(k), _ptr(flat), _ptr(off), len(off) - 1, _ptr(tab)))
+    return tab
 
 
 def probe_gather(ws_bytes, line_bytes, n_access, iters=3, device=0):

@@ -349,6 +349,15 @@ int fmdh_merge_pair_to_file(fmd_dev_t *h0, fmd_dev_t *h1, const char *out_path);
 int fmdh_contrast(const char *const fmd[2], const char *const rank_fn[2], const char *const out[2], int k, int min_occ, int device);
 int fmdh_sub(const char *fmd_path, const char *bits_path, int is_comp, int device, const char *out_path);
 int fmdh_bitand(int n_in, char *const *in, FILE *out);
+/* readprep_cmd.c: the read-preparation commands, argv as the reference's main_* take it (argv[0] = the command's name), output on stdout:
+ * `fermi fltuniq [-k INT] <in.fa>` (seq.c:122-210; -g GPU; the table and both passes on the GPU, the file streamed twice in batches),
+ * and, without a GPU, `trimseq` (seq.c:289-373), `pe2cofq` (seq.c:257-287), `splitfa` (seq.c:79-120), `cnt2qual` (cmd.c:13-45) */
+int fmdh_main_fltuniq(int argc, char *argv[]);
+int fmdh_main_trimseq(int argc, char *argv[]);
+int fmdh_main_pe2cofq(int argc, char *argv[]);
+int fmdh_main_splitfa(int argc, char *argv[]);
+int fmdh_main_cnt2qual(int argc, char *argv[]);
+int fmdh_fltuniq_auto_k(long long file_bytes);   /* the k `fltuniq` takes for an input file of that many bytes on disk (seq.c:147-150) */
 
 /* `fermi correct` (cmd.c:253-291, correct.c:305-456); defaults = cmd.c:258 */
 typedef struct { int w, min_occ, keep_bad, is_paired, trim_l, step; float max_corr; } fmdh_ecopt_t; /* = fmecopt_t, fermi.h:26-29 */

@@ -383,6 +383,11 @@ int main(int argc, char *argv[])
         fprintf(stderr, "         contrast   reads with k-mers the other index lacks (fermi contrast)\n");
         fprintf(stderr, "         sub        sub-index of selected reads (fermi sub)\n");
         fprintf(stderr, "         bitand     AND of bit arrays, no GPU needed (fermi bitand)\n");
+        fprintf(stderr, "         pe2cofq    interleave two mate files under one name, no GPU needed (fermi pe2cofq)\n");
+        fprintf(stderr, "         trimseq    trim / drop reads by quality, no GPU needed (fermi trimseq)\n");
+        fprintf(stderr, "         splitfa    deal read pairs to N files, no GPU needed (fermi splitfa)\n");
+        fprintf(stderr, "         cnt2qual   occurrence counts -> qualities, no GPU needed (fermi cnt2qual)\n");
+        fprintf(stderr, "         fltuniq    drop reads that hold a k-mer seen once, and their mates (fermi fltuniq)\n");
         fprintf(stderr, "         seqsort    rank -> read index map for `unitig -r` (fermi seqsort)\n");
         fprintf(stderr, "         unitig     construct unitigs (fermi unitig)\n");
         fprintf(stderr, "         correct    error correction (fermi correct)\n");
@@ -400,8 +405,12 @@ int main(int argc, char *argv[])
     int rc;
     setvbuf(stdout, 0, _IOFBF, 4 << 20); /* the outputs are hundreds of MB of short lines */
     if (strcmp(argv[1], "bitand") == 0) return main_bitand(argc - 1, argv + 1);   /* host only: runs where there is no GPU */
+    if (strcmp(argv[1], "trimseq") == 0) return fmdh_main_trimseq(argc - 1, argv + 1);
+    if (strcmp(argv[1], "pe2cofq") == 0) return fmdh_main_pe2cofq(argc - 1, argv + 1);
+    if (strcmp(argv[1], "splitfa") == 0) return fmdh_main_splitfa(argc - 1, argv + 1);
+    if (strcmp(argv[1], "cnt2qual") == 0) return fmdh_main_cnt2qual(argc - 1, argv + 1);
     { const int node = stay_on_one_node(argv[1]); if (timing && node >= 0) fprintf(stderr, "[M::main] the process stays on NUMA node %d\n", node); }
-    if (fmd_device_count() <= 0) {
+    if (strcmp(argv[1], "fltuniq") != 0 && fmd_device_count() <= 0) {   /* (fltuniq looks at its arguments first, as the reference does, then for the device) */
         fprintf(stderr, "[E::main] %s\n", fmd_strerror(FMD_E_NODEV));
         return 1;
     }
@@ -412,6 +421,7 @@ int main(int argc, char *argv[])
     else if (strcmp(argv[1], "recode") == 0) rc = main_recode(argc - 1, argv + 1);
     else if (strcmp(argv[1], "contrast") == 0) rc = main_contrast(argc - 1, argv + 1);
     else if (strcmp(argv[1], "sub") == 0) rc = main_sub(argc - 1, argv + 1);
+    else if (strcmp(argv[1], "fltuniq") == 0) rc = fmdh_main_fltuniq(argc - 1, argv + 1);
     else if (strcmp(argv[1], "seqsort") == 0) rc = main_seqsort(argc - 1, argv + 1);
     else if (strcmp(argv[1], "exact") == 0) rc = main_exact(argc - 1, argv + 1);
     else if (strcmp(argv[1], "correct") == 0) rc = main_correct(argc - 1, argv + 1);

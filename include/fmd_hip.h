@@ -568,6 +568,40 @@ int fmd_sub_mark_dev(fmd_dev_t *h, void *stream, const uint64_t *d_sub, uint64_t
 int fmd_sub_select_dev(fmd_dev_t *h, void *stream, const uint64_t *d_bits, const void *d_work, int is_comp, uint64_t first, uint64_t n, uint8_t *d_out);
 int fmd_dev_sub(fmd_dev_t *h, const uint64_t *sub, int is_comp, unsigned flags, fmd_dev_t **out);
 
+/* ---- `fermi fltuniq`: the k-mer table and the verdict per read (main_fltuniq, seq.c:122-210) ---------------------------------------
+ * Reads as fmd_ecfix_* takes them: read i = bytes [off[i], off[i+1]) of seqs, nt6 codes (1..4 = A C G T; every other byte is a non-base:
+ * the reference indexes seq_nt6_table with bytes >= 128 out of range, seq.c:168 -- undefined there).  Forward strand only.
+ * The table is the reference's flags[] (seq.c:161, :172) word for word: 2 bits per k-mer, k-mer z (first base most significant) at bits
+ * [(z & 31) << 1, +2) of 64-bit word z >> 5; 0 = absent, 1 = seen once, 3 = seen more than once.  fmd_fltuniq_table_bytes(k) = 4^k / 4
+ * bytes (16 GiB at k = 18), 0 for a k outside 3..20 (below 3 the reference's table has no word).
+ * count (seq.c:164-175): every window of k bases of every read raises its state; any number of calls on one table zeroed by the caller
+ *   (fmd_memset_dev) -- a state depends only on how often its k-mer occurs in all of them, not on the order or on where the batches were
+ *   cut (DESIGN.md "fltuniq").
+ * test (seq.c:192-199): d_pass[i] = 1 when read i holds no non-base and every window of k bases has state 3 (reads shorter than k: when
+ *   they hold no non-base), else 0.  The table is only read.
+ * Both enqueue on `stream` and return; they allocate nothing.  A k outside the range and null pointers are FMD_E_ARG.
+ * fmd_fltuniq / fmd_fltuniq_table: the host forms -- both passes over reads in host memory (pass[n_reads]), or pass 1 and the table
+ *   copied out (table_bytes(k) / 8 words); FMD_E_NOMEM when the table does not fit the device.
+ * fmd_fltuniq_t: a streamed run for input larger than memory (what `fermi-amd fltuniq` uses).  open allocates and zeroes the table and
+ *   two staging slots of max_bytes bases and max_reads reads in pinned host memory; slot hands out the next one (off[0] must be 0;
+ *   waits until its previous work is done); count / test upload the slot last handed out and enqueue its kernel -- the caller fills the
+ *   next slot meanwhile; the first test waits for every count.  pass[] of a test is filled when its slot comes round again or at
+ *   sync; sync also reports the milliseconds the count and the test kernels took so far.  export copies table words out. */
+typedef struct fmd_fltuniq_run fmd_fltuniq_t;
+size_t fmd_fltuniq_table_bytes(int k);
+int fmd_fltuniq_count_dev(int device, void *stream, int k, const uint8_t *d_seqs, const uint64_t *d_off, uint64_t n_reads, uint64_t *d_table);
+int fmd_fltuniq_test_dev(int device, void *stream, int k, const uint8_t *d_seqs, const uint64_t *d_off, uint64_t n_reads, const uint64_t *d_table,
+                         uint8_t *d_pass);
+int fmd_fltuniq(int device, int k, const uint8_t *seqs, const uint64_t *off, uint64_t n_reads, uint8_t *pass);
+int fmd_fltuniq_table(int device, int k, const uint8_t *seqs, const uint64_t *off, uint64_t n_reads, uint64_t *table);
+int fmd_fltuniq_open(int device, int k, uint64_t max_bytes, uint64_t max_reads, fmd_fltuniq_t **out);
+int fmd_fltuniq_slot(fmd_fltuniq_t *f, uint8_t **seqs, uint64_t **off);
+int fmd_fltuniq_count(fmd_fltuniq_t *f, uint64_t n_reads);
+int fmd_fltuniq_test(fmd_fltuniq_t *f, uint64_t n_reads, uint8_t *pass);
+int fmd_fltuniq_sync(fmd_fltuniq_t *f, double kernel_ms[2]);
+int fmd_fltuniq_export(fmd_fltuniq_t *f, uint64_t first_word, uint64_t n_words, uint64_t *table);
+void fmd_fltuniq_close(fmd_fltuniq_t *f);
+
 /* device memory for C hosts (the reference has no device; these are what a cgo/C caller uses to
  * stage batches): plain hipMalloc / hipMemcpyAsync behind the ABI. */
 int fmd_dev_malloc(int device, size_t bytes, void **d_ptr);
