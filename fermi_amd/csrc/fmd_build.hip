@@ -84,19 +84,8 @@ __global__ void k_seq_ends(size_t n_reads, const uint64_t *__restrict__ off, uin
     }
 }
 
-// blocks for n items, t threads each: at most 2^31 threads per launch (the dispatch packet counts work-items in 32
-// bits; the kernels above loop with a grid stride)
-static inline unsigned nblk(uint64_t n, unsigned t)
-{
-    const uint64_t b = (n + t - 1) / t, cap = (1ull << 31) / t;
-    return (unsigned)(b < cap ? (b ? b : 1) : cap);
-}
-
 #include <time.h>
 static double bt_now(hipStream_t st, bool on) { if (!on) return 0; hipStreamSynchronize(st); struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return (double)t.tv_sec + 1e-9 * (double)t.tv_nsec; }
-struct DevPtr { void *p = nullptr; ~DevPtr() { if (p) hipFree(p); } };
-#define DALLOC(buf, bytes) do { hipError_t e__ = hipMalloc(&(buf).p, (bytes) ? (bytes) : 16); \
-    if (e__ != hipSuccess) { fmd_set_hip_error(e__, "hipMalloc(" #buf ")"); return FMD_E_NOMEM; } } while (0)
 
 
 // ------------------------------------------------------------------ >= 2^32 symbols: bucketed
@@ -372,18 +361,18 @@ static int build_bucketed(hipStream_t st, Text text, uint64_t n, uint32_t max_le
     std::vector<uint32_t> codes;
     prefix_codes(depth, codes);
     uint64_t done = 0, cap = 0;
-    DevPtr ids_a, ids_b, keys_a, keys_b, tmp, stmp, slice;     // grown to the largest bucket met so far
+    FmdDevBuf ids_a, ids_b, keys_a, keys_b, tmp, stmp, slice;     // grown to the largest bucket met so far
     size_t tb = 0, sb = 0;
     const uint64_t n_tiles = (n + (1ull << SEL_TILE_SHIFT) - 1) >> SEL_TILE_SHIFT;
-    DevPtr tile_cnt, tile_off;
-    DALLOC(tile_cnt, n_tiles * 8); DALLOC(tile_off, n_tiles * 8);
+    FmdDevBuf tile_cnt, tile_off;
+    FMD_TRY(tile_cnt.alloc(n_tiles * 8)); FMD_TRY(tile_off.alloc(n_tiles * 8));
     FMD_HIP_TRY(fmd_exclusive_sum(nullptr, tb, (uint64_t *)tile_cnt.p, (uint64_t *)tile_off.p, (size_t)n_tiles, st));
-    DALLOC(tmp, tb);
+    FMD_TRY(tmp.alloc(tb));
     const unsigned sel_grid = (unsigned)(n_tiles / 4 + 1 < 65536 ? n_tiles / 4 + 1 : 65536);
     std::vector<unsigned long long> sizes((size_t)1 << (3 * depth), 0ull);
     {
-        DevPtr hist;
-        DALLOC(hist, sizes.size() * 8);
+        FmdDevBuf hist;
+        FMD_TRY(hist.alloc(sizes.size() * 8));
         FMD_HIP_TRY(hipMemsetAsync(hist.p, 0, sizes.size() * 8, st));
         // a block counts at most 2^32 - 1 positions per bin in LDS: grid-stride over n with 4096 blocks x 1024 threads is far below that
         k_prefix_hist<<<4096, 1024, sizes.size() * 4, st>>>(text, n, depth, (unsigned long long *)hist.p);
@@ -396,14 +385,13 @@ static int build_bucketed(hipStream_t st, Text text, uint64_t n, uint32_t max_le
         const uint64_t m = sizes[code];                      // from the histogram; the positions follow, ascending
         if (m == 0) continue;
         if (m > cap) {                                      // grow: release first, the arrays are the bulk of the footprint
-            hipFree(ids_a.p); hipFree(ids_b.p); hipFree(keys_a.p); hipFree(keys_b.p); hipFree(stmp.p); hipFree(slice.p);
-            ids_a.p = ids_b.p = keys_a.p = keys_b.p = stmp.p = slice.p = nullptr;
+            ids_a.reset(); ids_b.reset(); keys_a.reset(); keys_b.reset(); stmp.reset(); slice.reset();
             cap = m + m / 16;
-            DALLOC(ids_a, cap * 8); DALLOC(ids_b, cap * 8); DALLOC(keys_a, cap * 8); DALLOC(keys_b, cap * 8);
-            if (!bwt_direct) DALLOC(slice, cap + 64);
+            FMD_TRY(ids_a.alloc(cap * 8)); FMD_TRY(ids_b.alloc(cap * 8)); FMD_TRY(keys_a.alloc(cap * 8)); FMD_TRY(keys_b.alloc(cap * 8));
+            if (!bwt_direct) FMD_TRY(slice.alloc(cap + 64));
             FMD_HIP_TRY(fmd_sort_pairs(nullptr, sb, (uint64_t *)keys_a.p, (uint64_t *)keys_b.p, (uint64_t *)ids_a.p,
                                                           (uint64_t *)ids_b.p, (size_t)cap, 0, 63, st));
-            DALLOC(stmp, sb);
+            FMD_TRY(stmp.alloc(sb));
         }
         if (tm) { t1 = bt_now(st, tm); t_alloc += t1 - t0; t0 = t1; }
         launch_tile_count(st, sel_grid, text, n, depth, code, n_tiles, (uint64_t *)tile_cnt.p);
@@ -438,8 +426,8 @@ static int build_bucketed(hipStream_t st, Text text, uint64_t n, uint32_t max_le
                         if (uniform_len) k_part_scatter<<<sel_grid, 256, 0, st>>>(cur, m, ru, o0, m_tiles, (const uint64_t *)tile_off.p, z, nxt);
                         else k_part_scatter<<<sel_grid, 256, 0, st>>>(cur, m, rr, o0, m_tiles, (const uint64_t *)tile_off.p, z, nxt);
                         if (tm) { t1 = bt_now(st, tm); t_sel += t1 - t0; t0 = t1; }
-                        if (uniform_len) k_chunk_keys64<<<nblk(m - z, 256), 256, 0, st>>>(text, n_wide, m - z, nxt + z, ch, ru, (uint64_t *)keys_a.p);
-                        else k_chunk_keys64<<<nblk(m - z, 256), 256, 0, st>>>(text, n_wide, m - z, nxt + z, ch, rr, (uint64_t *)keys_a.p);
+                        if (uniform_len) k_chunk_keys64<<<fmd_nblk(m - z, 256), 256, 0, st>>>(text, n_wide, m - z, nxt + z, ch, ru, (uint64_t *)keys_a.p);
+                        else k_chunk_keys64<<<fmd_nblk(m - z, 256), 256, 0, st>>>(text, n_wide, m - z, nxt + z, ch, rr, (uint64_t *)keys_a.p);
                         if (tm) { t1 = bt_now(st, tm); t_keys += t1 - t0; t0 = t1; }
                         FMD_HIP_TRY(fmd_sort_pairs(stmp.p, sb_m, (uint64_t *)keys_a.p, (uint64_t *)keys_b.p, nxt + z, cur + z, (size_t)(m - z), 0, 63, st));
                         FMD_HIP_TRY(hipMemcpyAsync(cur, nxt, z * 8, hipMemcpyDeviceToDevice, st));   // (the result is in `cur` again: no swap)
@@ -447,8 +435,8 @@ static int build_bucketed(hipStream_t st, Text text, uint64_t n, uint32_t max_le
                         continue;
                     }
                 }
-                if (uniform_len) k_chunk_keys64<<<nblk(m, 256), 256, 0, st>>>(text, n_wide, m, cur, ch, RemUniform{max_len + 1}, (uint64_t *)keys_a.p);
-                else k_chunk_keys64<<<nblk(m, 256), 256, 0, st>>>(text, n_wide, m, cur, ch, rr, (uint64_t *)keys_a.p);
+                if (uniform_len) k_chunk_keys64<<<fmd_nblk(m, 256), 256, 0, st>>>(text, n_wide, m, cur, ch, RemUniform{max_len + 1}, (uint64_t *)keys_a.p);
+                else k_chunk_keys64<<<fmd_nblk(m, 256), 256, 0, st>>>(text, n_wide, m, cur, ch, rr, (uint64_t *)keys_a.p);
                 // the first `depth` symbols are equal inside a bucket: chunk 0 sorts on the bits below them only
                 const int end_bit = ch == 0 ? 63 - 3 * (depth < 21 ? depth : 21) : 63;
                 if (tm) { t1 = bt_now(st, tm); t_keys += t1 - t0; t0 = t1; }
@@ -457,9 +445,9 @@ static int build_bucketed(hipStream_t st, Text text, uint64_t n, uint32_t max_le
                 if (tm) { t1 = bt_now(st, tm); t_sort += t1 - t0; t0 = t1; }
             }
         }
-        if (bwt_direct) k_emit_bwt64<<<nblk(m, 256), 256, 0, st>>>(text, cur, m, bwt_direct + done);
+        if (bwt_direct) k_emit_bwt64<<<fmd_nblk(m, 256), 256, 0, st>>>(text, cur, m, bwt_direct + done);
         else {
-            k_emit_bwt64<<<nblk(m, 256), 256, 0, st>>>(text, cur, m, (uint8_t *)slice.p);
+            k_emit_bwt64<<<fmd_nblk(m, 256), 256, 0, st>>>(text, cur, m, (uint8_t *)slice.p);
             const int rc = sink((const uint8_t *)slice.p, done, m);
             if (rc) return rc;
         }
@@ -502,44 +490,42 @@ extern "C" int fmd_build_bwt_dev(int device, void *stream_, size_t n_reads, cons
     hipStream_t st = (hipStream_t)stream_;
     const uint64_t n = 2 * (total_bases + n_reads);
     const bool bucketed = n >= 0xffffffffull || getenv("FMD_BUILD_BUCKETED") != nullptr; // 32-bit suffix ids in the one-shot path
-    DevPtr text, keys_a, keys_b, ord_a, ord_b, send, tmp;
-    uint8_t *bwt = nullptr;
-    DALLOC(text, n + 64);
+    FmdDevBuf text, keys_a, keys_b, ord_a, ord_b, send, tmp, bwt;
+    FMD_TRY(text.alloc(n + 64));
     k_build_text<<<(unsigned)(n_reads < (1u << 24) ? n_reads : (1u << 24)), 64, 0, st>>>(n_reads, d_reads, d_off, (uint8_t *)text.p);
     RemRagged rr{nullptr, 2 * n_reads};
     if (!uniform_len) {
-        DALLOC(send, 2 * n_reads * 8);
-        k_seq_ends<<<nblk(n_reads, 256), 256, 0, st>>>(n_reads, d_off, (uint64_t *)send.p);
+        FMD_TRY(send.alloc(2 * n_reads * 8));
+        k_seq_ends<<<fmd_nblk(n_reads, 256), 256, 0, st>>>(n_reads, d_off, (uint64_t *)send.p);
         rr.send = (const uint64_t *)send.p;
     }
     if (bucketed) {
-        FMD_HIP_TRY(hipMalloc((void **)&bwt, n + 64));
-        int rc = build_bucketed(st, Text8{(const uint8_t *)text.p}, n, max_len, uniform_len, rr, bucket_depth(n, 2), bwt, NoSink());
-        if (rc) { hipFree(bwt); return rc; }
-        *d_bwt_out = bwt; *n_sym_out = n;
+        FMD_TRY(bwt.alloc(n + 64));
+        FMD_TRY(build_bucketed(st, Text8{(const uint8_t *)text.p}, n, max_len, uniform_len, rr, bucket_depth(n, 2), bwt.as<uint8_t>(), NoSink()));
+        *d_bwt_out = (uint8_t *)bwt.release(); *n_sym_out = n;
         return FMD_OK;
     }
-    DALLOC(keys_a, n * 8); DALLOC(keys_b, n * 8); DALLOC(ord_a, n * 4); DALLOC(ord_b, n * 4);
+    FMD_TRY(keys_a.alloc(n * 8)); FMD_TRY(keys_b.alloc(n * 8)); FMD_TRY(ord_a.alloc(n * 4)); FMD_TRY(ord_b.alloc(n * 4));
     size_t tmp_bytes = 0;
     FMD_HIP_TRY(fmd_sort_pairs(nullptr, tmp_bytes, (uint64_t *)keys_a.p, (uint64_t *)keys_b.p,
                                                   (uint32_t *)ord_a.p, (uint32_t *)ord_b.p, (size_t)n, 0, 63, st));
-    DALLOC(tmp, tmp_bytes);
+    FMD_TRY(tmp.alloc(tmp_bytes));
     const int n_chunks = (int)((max_len + 1 + 20) / 21);
     uint32_t *cur = (uint32_t *)ord_a.p, *nxt = (uint32_t *)ord_b.p;
-    k_iota32<<<nblk(n, 256), 256, 0, st>>>(cur, n); // text order = sequence-id order: the tie-break
+    k_iota32<<<fmd_nblk(n, 256), 256, 0, st>>>(cur, n); // text order = sequence-id order: the tie-break
     const uint64_t n_wide = getenv("FMD_BUILD_KEY_BYTES") && atoi(getenv("FMD_BUILD_KEY_BYTES")) ? 0 : n;   // A/B switch: 0 = every key byte by byte (round 3)
     for (int c = n_chunks - 1; c >= 0; --c) {
-        if (uniform_len) k_chunk_keys<<<nblk(n, 256), 256, 0, st>>>((const uint8_t *)text.p, n, n_wide, cur, c, RemUniform{max_len + 1}, (uint64_t *)keys_a.p);
-        else k_chunk_keys<<<nblk(n, 256), 256, 0, st>>>((const uint8_t *)text.p, n, n_wide, cur, c, rr, (uint64_t *)keys_a.p);
+        if (uniform_len) k_chunk_keys<<<fmd_nblk(n, 256), 256, 0, st>>>((const uint8_t *)text.p, n, n_wide, cur, c, RemUniform{max_len + 1}, (uint64_t *)keys_a.p);
+        else k_chunk_keys<<<fmd_nblk(n, 256), 256, 0, st>>>((const uint8_t *)text.p, n, n_wide, cur, c, rr, (uint64_t *)keys_a.p);
         FMD_HIP_TRY(fmd_sort_pairs(tmp.p, tmp_bytes, (uint64_t *)keys_a.p, (uint64_t *)keys_b.p, cur, nxt,
                                                       (size_t)n, 0, 63, st));
         uint32_t *t = cur; cur = nxt; nxt = t;
     }
-    FMD_HIP_TRY(hipMalloc((void **)&bwt, n + 64));
-    k_emit_bwt<<<nblk(n, 256), 256, 0, st>>>((const uint8_t *)text.p, cur, n, bwt);
+    FMD_TRY(bwt.alloc(n + 64));
+    k_emit_bwt<<<fmd_nblk(n, 256), 256, 0, st>>>((const uint8_t *)text.p, cur, n, bwt.as<uint8_t>());
     hipError_t e = hipStreamSynchronize(st);
-    if (e != hipSuccess) { hipFree(bwt); fmd_set_hip_error(e, "build"); return FMD_E_HIP; }
-    *d_bwt_out = bwt; *n_sym_out = n;
+    if (e != hipSuccess) { fmd_set_hip_error(e, "build"); return FMD_E_HIP; }
+    *d_bwt_out = (uint8_t *)bwt.release(); *n_sym_out = n;
     return FMD_OK;
 }
 
@@ -597,7 +583,7 @@ extern "C" int fmd_builder_add_dev(fmd_builder_t *b, void *stream, uint64_t n, c
     if (!b || (n && !d_reads) || b->added + n > b->n_reads) return FMD_E_ARG;
     if (n == 0) return FMD_OK;
     FMD_HIP_TRY(hipSetDevice(b->device));
-    k_text4_add<<<nblk(n * ((uint64_t)b->len + 1), 256), 256, 0, (hipStream_t)stream>>>(n, b->len, b->added, d_reads, b->text4);
+    k_text4_add<<<fmd_nblk(n * ((uint64_t)b->len + 1), 256), 256, 0, (hipStream_t)stream>>>(n, b->len, b->added, d_reads, b->text4);
     b->added += n;
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { fmd_set_hip_error(e, "k_text4_add"); return FMD_E_HIP; }
@@ -637,15 +623,15 @@ extern "C" int fmd_build_bwt(int device, size_t n_reads, const uint8_t *reads, c
         if (l > max_len) max_len = (uint32_t)l;
         if (l != off[1] - off[0]) uniform = 0;
     }
-    DevPtr dr, doff;
-    DALLOC(dr, off[n_reads] + 64); DALLOC(doff, (n_reads + 1) * 8);
+    FmdDevBuf dr, doff;
+    FMD_TRY(dr.alloc(off[n_reads] + 64)); FMD_TRY(doff.alloc((n_reads + 1) * 8));
     FMD_HIP_TRY(hipMemcpy(dr.p, reads, off[n_reads], hipMemcpyHostToDevice));
     FMD_HIP_TRY(hipMemcpy(doff.p, off, (n_reads + 1) * 8, hipMemcpyHostToDevice));
     uint8_t *d_bwt = nullptr;
     int rc = fmd_build_bwt_dev(device, nullptr, n_reads, (uint8_t *)dr.p, (uint64_t *)doff.p, off[n_reads], max_len, uniform, &d_bwt, n_sym);
     if (rc) return rc;
     hipError_t e = hipMemcpy(bwt, d_bwt, *n_sym, hipMemcpyDeviceToHost);
-    hipFree(d_bwt);
+    fmd_dev_free(d_bwt);
     FMD_HIP_TRY(e);
     return FMD_OK;
 }
@@ -681,12 +667,12 @@ extern "C" int fmd_bwt_to_rle6(int device, const uint8_t *d_bwt, uint64_t n, uin
     const uint64_t mx = n < CH ? n : CH;
     struct HostBuf { uint8_t *p = nullptr; ~HostBuf() { free(p); } } hold;   // released to the caller on success only (FMD_HIP_TRY returns early)
     uint8_t *&h = hold.p; uint64_t h_n = 0, h_cap = 0;
-    DevPtr sym, len, nruns, tmp, nb, start, out, t2;
-    DALLOC(sym, mx); DALLOC(len, mx * 4); DALLOC(nruns, 8); DALLOC(nb, mx * 8); DALLOC(start, mx * 8); DALLOC(out, mx);
+    FmdDevBuf sym, len, nruns, tmp, nb, start, out, t2;
+    FMD_TRY(sym.alloc(mx)); FMD_TRY(len.alloc(mx * 4)); FMD_TRY(nruns.alloc(8)); FMD_TRY(nb.alloc(mx * 8)); FMD_TRY(start.alloc(mx * 8)); FMD_TRY(out.alloc(mx));
     size_t tb = 0, b2 = 0;
     FMD_HIP_TRY(fmd_run_length_encode(nullptr, tb, d_bwt, (unsigned)mx, (uint8_t *)sym.p, (uint32_t *)len.p, (uint64_t *)nruns.p));
     FMD_HIP_TRY(fmd_exclusive_sum(nullptr, b2, (uint64_t *)nb.p, (uint64_t *)start.p, (size_t)mx));
-    DALLOC(tmp, tb); DALLOC(t2, b2);
+    FMD_TRY(tmp.alloc(tb)); FMD_TRY(t2.alloc(b2));
     for (uint64_t o = 0; o < n; o += CH) {
         const uint64_t m = n - o < CH ? n - o : CH;
         size_t tb1 = tb, b21 = b2;
@@ -694,14 +680,14 @@ extern "C" int fmd_bwt_to_rle6(int device, const uint8_t *d_bwt, uint64_t n, uin
         uint64_t n_runs = 0;
         FMD_HIP_TRY(hipMemcpy(&n_runs, nruns.p, 8, hipMemcpyDeviceToHost));
         if (n_runs == 0 || n_runs > m) return FMD_E_HIP;
-        k_run_bytes<<<nblk(n_runs, 256), 256>>>((uint32_t *)len.p, n_runs, (uint64_t *)nb.p);
+        k_run_bytes<<<fmd_nblk(n_runs, 256), 256>>>((uint32_t *)len.p, n_runs, (uint64_t *)nb.p);
         FMD_HIP_TRY(fmd_exclusive_sum(t2.p, b21, (uint64_t *)nb.p, (uint64_t *)start.p, (size_t)n_runs));
         uint64_t a = 0, b = 0;
         FMD_HIP_TRY(hipMemcpy(&a, (uint64_t *)start.p + n_runs - 1, 8, hipMemcpyDeviceToHost));
         FMD_HIP_TRY(hipMemcpy(&b, (uint64_t *)nb.p + n_runs - 1, 8, hipMemcpyDeviceToHost));
         const uint64_t total = a + b;
         if (total > m) return FMD_E_HIP;                 // cannot happen: a run of l symbols is ceil(l / 31) <= l bytes
-        k_run_emit<<<nblk(n_runs, 256), 256>>>((uint8_t *)sym.p, (uint32_t *)len.p, n_runs, (uint64_t *)start.p, (uint8_t *)out.p);
+        k_run_emit<<<fmd_nblk(n_runs, 256), 256>>>((uint8_t *)sym.p, (uint32_t *)len.p, n_runs, (uint64_t *)start.p, (uint8_t *)out.p);
         if (h_n + total > h_cap) {   // the first chunk's ratio for the whole stream + a fifth, then doubling
             const uint64_t est = o == 0 ? (uint64_t)((double)total * ((double)n / (double)m) * 1.2) + 64 : (h_n + total) * 2 + 64;
             h_cap = est > h_n + total ? est : h_n + total + 64;

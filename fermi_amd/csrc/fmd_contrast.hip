@@ -17,8 +17,8 @@
 // per-4096-row popcounts, a scan, and a kernel that finds the superblock its slice begins in from the scan.
 #include <stdlib.h>
 #include <string.h>
-#include "fmd_prim.h"
 #include "fmd_kernel_common.h"
+#include "fmd_bits.h"
 
 #define CT_SUF_LEN 4            // cmp.c:8: the walk starts from all strings of this length, pushed without the min_occ test
 #define CT_TIP_LEVELS 64        // levels of a tip's trie expanded as a frontier; the rest is walked row by row
@@ -34,7 +34,6 @@
 #define CT_TIP1 7
 #define CT_DEMAND 8             // the largest list any level asked for
 #define CT_WORDS 16
-#define SUB_SB_WORDS 64         // bit words per prefix-count superblock (4096 rows)
 
 // ------------------------------------------------------------------------------------------------ chunked appends
 // Output slots of a list are handed out `ch` entries at a time per wave, one device-wide atomic per chunk; a wave zero-fills what it
@@ -345,24 +344,13 @@ __global__ __launch_bounds__(64) void k_sub_mark(FmdIndexView ix, const unsigned
     }
 }
 
-// set bits of each 4096-row superblock: one wave per superblock, a lane per word
-__global__ __launch_bounds__(64) void k_sub_sb_count(const unsigned long long *__restrict__ bits, uint64_t n_words, uint64_t n_sb, uint64_t *__restrict__ cnt)
-{
-    for (uint64_t sb = blockIdx.x; sb < n_sb; sb += gridDim.x) {
-        const uint64_t wd = sb * SUB_SB_WORDS + threadIdx.x;
-        int c = wd < n_words ? __popcll(bits[wd]) : 0;
-        for (int s = 32; s > 0; s >>= 1) c += __shfl_xor(c, s);
-        if (threadIdx.x == 0) cnt[sb] = (uint64_t)c;
-    }
-}
-
 // gen_idx (sub.c:30-55) without the encoder: kept rows (bit == !is_comp) number [first, first + n) as nt6 bytes.  pre[sb] = set bits
 // before superblock sb (pre[n_sb] = all).  One wave per superblock from the one the slice begins in, a lane per word = 64 rows.
 __global__ __launch_bounds__(64) void k_sub_select(FmdIndexView ix, const unsigned long long *__restrict__ bits, const uint64_t *__restrict__ pre, uint64_t n_sb,
                                                    int is_comp, uint64_t first, uint64_t n, uint8_t *__restrict__ out)
 {
     const int q = fmd_lane();
-    const uint64_t n_sym = ix.n_sym, rows_sb = 64ull * SUB_SB_WORDS;
+    const uint64_t n_sym = ix.n_sym, rows_sb = 64ull * FMD_BITS_SB_WORDS;
 #define SUB_KEPT_BEFORE(sb) (is_comp ? ((sb) * rows_sb < n_sym ? (sb) * rows_sb : n_sym) - pre[sb] : pre[sb])
     uint64_t lo = 0, hi = n_sb;                        // the first superblock with kept rows beyond `first`
     while (lo < hi) {
@@ -372,7 +360,7 @@ __global__ __launch_bounds__(64) void k_sub_select(FmdIndexView ix, const unsign
     for (uint64_t sb = lo + blockIdx.x; sb < n_sb; sb += gridDim.x) {
         const uint64_t kb = SUB_KEPT_BEFORE(sb);
         if (kb >= first + n) break;
-        const uint64_t wd = sb * SUB_SB_WORDS + q, p0 = wd * 64;
+        const uint64_t wd = sb * FMD_BITS_SB_WORDS + q, p0 = wd * 64;
         uint64_t m = 0;
         if (p0 < n_sym) {
             m = bits[wd];
@@ -397,8 +385,6 @@ __global__ __launch_bounds__(64) void k_sub_select(FmdIndexView ix, const unsign
 }
 
 // -------------------------------------------------------------------------------------------------- host side
-static inline hipStream_t S(void *s) { return (hipStream_t)s; }
-
 extern "C" size_t fmd_contrast_work_bytes(uint64_t cap)
 {
     return (size_t)(CT_WORDS * 8 + 256 + cap * (2 * 32 + 2 * 16));   // counters, two pair frontiers, two tip lists
@@ -482,16 +468,15 @@ static int contrast_part_host(fmd_dev_t *h0, fmd_dev_t *h1, int k, int min_occ, 
             cap = by_demand > 2 * cap ? by_demand : 2 * cap;
         }
         if (cap >= 0xffffff00ull) return FMD_E_OVERFLOW;
-        void *work = nullptr, *ds = nullptr;
+        FmdDevBuf work, ds;
         const size_t wb = fmd_contrast_work_bytes(cap);
-        int rc = FMD_OK;
-        if (hipMalloc(&work, wb) != hipSuccess || hipMalloc(&ds, 32) != hipSuccess) { (void)hipGetLastError(); rc = FMD_E_NOMEM; }
+        int rc;
+        if ((rc = work.alloc(wb)) || (rc = ds.alloc(32))) return rc;
         uint64_t status[4] = {0, 0, 0, 0};
         unsigned long long ctr[CT_WORDS];
-        if (rc == FMD_OK) rc = fmd_contrast_dev(h0, h1, nullptr, k, min_occ, seed_mask, d_sub0, d_sub1, work, wb, cap, (uint64_t *)ds);
-        if (rc == FMD_OK && hipMemcpy(status, ds, 32, hipMemcpyDeviceToHost) != hipSuccess) rc = FMD_E_HIP;
-        if (rc == FMD_OK && status[1] != 0 && hipMemcpy(ctr, work, sizeof(ctr), hipMemcpyDeviceToHost) == hipSuccess) demand = ctr[CT_DEMAND];
-        hipFree(work); hipFree(ds);
+        rc = fmd_contrast_dev(h0, h1, nullptr, k, min_occ, seed_mask, d_sub0, d_sub1, work.p, wb, cap, ds.as<uint64_t>());
+        if (rc == FMD_OK && hipMemcpy(status, ds.p, 32, hipMemcpyDeviceToHost) != hipSuccess) rc = FMD_E_HIP;
+        if (rc == FMD_OK && status[1] != 0 && hipMemcpy(ctr, work.p, sizeof(ctr), hipMemcpyDeviceToHost) == hipSuccess) demand = ctr[CT_DEMAND];
         if (rc != FMD_OK) return rc;
         if (status[1] == 0) return FMD_OK;
     }
@@ -508,7 +493,8 @@ extern "C" int fmd_contrast(fmd_dev_t *h0, fmd_dev_t *h1, int k, int min_occ, ui
     if (!sub0 || !sub1) return FMD_E_ARG;
     FMD_HIP_TRY(hipSetDevice(h0->device));
     const uint64_t nw[2] = {(h0->mcnt[1] + 63) / 64, (h1->mcnt[1] + 63) / 64};
-    uint64_t *d[2] = {nullptr, nullptr}, *out[2] = {nullptr, nullptr};
+    FmdDevBuf d[2];
+    uint64_t *out[2] = {nullptr, nullptr};
     // the widest level holds about one node per distinct k-mer of the two samples: symbols / 24 at 30-fold coverage with a few errors per
     // thousand bases; never more than half of the free memory (96 bytes per entry), and the walk runs again when it was too little
     uint64_t cap0 = (h0->mcnt[0] + h1->mcnt[0]) / 24;
@@ -522,56 +508,40 @@ extern "C" int fmd_contrast(fmd_dev_t *h0, fmd_dev_t *h1, int k, int min_occ, ui
     { const char *e = getenv("FMD_CONTRAST_CAP"); if (e && atoll(e) >= (long long)CT_MIN_CAP) cap0 = (uint64_t)atoll(e); }
     { const char *e = getenv("FMD_CONTRAST_PARTS"); if (e && (atoi(e) == 1 || atoi(e) == 4)) parts = atoi(e); }
     for (int i = 0; i < 2 && rc == FMD_OK; ++i) {
-        if (hipMalloc((void **)&d[i], (nw[i] + 1) * 8) != hipSuccess) { (void)hipGetLastError(); rc = FMD_E_NOMEM; }
-        else if (hipMemset(d[i], 0, (nw[i] + 1) * 8) != hipSuccess) rc = FMD_E_HIP;
+        if ((rc = d[i].alloc((nw[i] + 1) * 8))) break;
+        if (hipMemset(d[i].p, 0, (nw[i] + 1) * 8) != hipSuccess) rc = FMD_E_HIP;
     }
     while (rc == FMD_OK) {
-        for (int p = 0; p < parts && rc == FMD_OK; ++p) rc = contrast_part_host(h0, h1, k, min_occ, parts == 1 ? 0xf : 1 << p, cap0, d[0], d[1]);
+        for (int p = 0; p < parts && rc == FMD_OK; ++p) rc = contrast_part_host(h0, h1, k, min_occ, parts == 1 ? 0xf : 1 << p, cap0, d[0].as<uint64_t>(), d[1].as<uint64_t>());
         if (rc != FMD_E_NOMEM || parts != 1) break;
         parts = 4; rc = FMD_OK;      // the frontiers of the whole trie did not fit: a quarter at a time
     }
     for (int i = 0; i < 2 && rc == FMD_OK; ++i) {
         out[i] = (uint64_t *)calloc(nw[i] + 1, 8);
         if (!out[i]) rc = FMD_E_NOMEM;
-        else if (nw[i] && hipMemcpy(out[i], d[i], nw[i] * 8, hipMemcpyDeviceToHost) != hipSuccess) rc = FMD_E_HIP;
+        else if (nw[i] && hipMemcpy(out[i], d[i].p, nw[i] * 8, hipMemcpyDeviceToHost) != hipSuccess) rc = FMD_E_HIP;
     }
-    hipFree(d[0]); hipFree(d[1]);
     if (rc) { free(out[0]); free(out[1]); return rc; }
     *sub0 = out[0]; *sub1 = out[1];
     return FMD_OK;
 }
 
 // ---- sub-index
-static inline unsigned sub_grid(uint64_t n_waves) { return (unsigned)(n_waves < (1u << 24) ? (n_waves ? n_waves : 1) : (1u << 24)); }
-static inline uint64_t sub_n_sb(uint64_t n_sym) { return ((n_sym + 63) / 64 + SUB_SB_WORDS - 1) / SUB_SB_WORDS; }
-
-// work area: prefix counts (n_sb + 1), superblock counts (n_sb + 1), the scan's temporary storage
-extern "C" size_t fmd_sub_work_bytes(uint64_t n_sym)
-{
-    const uint64_t n_sb = sub_n_sb(n_sym);
-    size_t b = 0;
-    if (fmd_exclusive_sum(nullptr, b, (const uint64_t *)nullptr, (uint64_t *)nullptr, (size_t)n_sb + 1, 0) != hipSuccess) b = 0;
-    return (size_t)(2 * (n_sb + 1) * 8 + 256 + b);
-}
+extern "C" size_t fmd_sub_work_bytes(uint64_t n_sym) { return fmd_bits_work_bytes(n_sym); }
 
 extern "C" int fmd_sub_mark_dev(fmd_dev_t *h, void *stream, const uint64_t *d_sub, uint64_t *d_bits, void *d_work, size_t work_bytes, uint64_t *d_n_kept)
 {
     if (!h || !d_sub || !d_bits || !d_work) return FMD_E_ARG;
     if (h->mcnt[1] >= 0xffffff00ull) return FMD_E_ARG;               // 32-bit ticket queue
-    const uint64_t n_sym = h->mcnt[0], n_words = (n_sym + 63) / 64, n_sb = sub_n_sb(n_sym);
+    const uint64_t n_sym = h->mcnt[0], n_sb = fmd_bits_n_sb(n_sym);
     if (work_bytes < fmd_sub_work_bytes(n_sym)) return FMD_E_ARG;
     FMD_HIP_TRY(hipSetDevice(h->device));
     uint32_t *queue = fmd_next_queue(h, S(stream));
     k_sub_mark<<<fmd_grid_for(h, h->mcnt[1]), 64, 0, S(stream)>>>(fmd_view(h), (const unsigned long long *)d_sub, (unsigned long long *)d_bits, queue);
     FMD_HIP_TRY(hipGetLastError());
-    uint64_t *pre = (uint64_t *)d_work, *cnt = pre + n_sb + 1;
-    void *tmp = (void *)(((uintptr_t)(cnt + n_sb + 1) + 255) & ~(uintptr_t)255);
-    size_t tmp_bytes = work_bytes - (size_t)((uint8_t *)tmp - (uint8_t *)d_work);
-    FMD_HIP_TRY(hipMemsetAsync(cnt + n_sb, 0, 8, S(stream)));
-    k_sub_sb_count<<<sub_grid(n_sb), 64, 0, S(stream)>>>((const unsigned long long *)d_bits, n_words, n_sb, cnt);
-    FMD_HIP_TRY(hipGetLastError());
-    FMD_HIP_TRY(fmd_exclusive_sum(tmp, tmp_bytes, (const uint64_t *)cnt, pre, (size_t)n_sb + 1, S(stream)));
-    if (d_n_kept) FMD_HIP_TRY(hipMemcpyAsync(d_n_kept, pre + n_sb, 8, hipMemcpyDeviceToDevice, S(stream)));
+    const int rc = fmd_bits_rank_dev(S(stream), d_bits, n_sym, d_work, work_bytes);
+    if (rc) return rc;
+    if (d_n_kept) FMD_HIP_TRY(hipMemcpyAsync(d_n_kept, (const uint64_t *)d_work + n_sb, 8, hipMemcpyDeviceToDevice, S(stream)));
     return FMD_OK;
 }
 
@@ -583,8 +553,8 @@ extern "C" int fmd_sub_select_dev(fmd_dev_t *h, void *stream, const uint64_t *d_
     FMD_HIP_TRY(hipSetDevice(h->device));
     // a slice of n kept rows spans at least n / 4096 superblocks and any number more: the waves stride from the first one until they
     // are past the slice
-    k_sub_select<<<sub_grid(n / (64 * SUB_SB_WORDS) + 64), 64, 0, S(stream)>>>(fmd_view(h), (const unsigned long long *)d_bits, (const uint64_t *)d_work,
-                                                                             sub_n_sb(h->mcnt[0]), is_comp != 0, first, n, d_out);
+    k_sub_select<<<fmd_wave_grid(n / (64 * FMD_BITS_SB_WORDS) + 64), 64, 0, S(stream)>>>(fmd_view(h), (const unsigned long long *)d_bits, (const uint64_t *)d_work,
+                                                                             fmd_bits_n_sb(h->mcnt[0]), is_comp != 0, first, n, d_out);
     FMD_HIP_TRY(hipGetLastError());
     return FMD_OK;
 }
@@ -597,44 +567,35 @@ extern "C" int fmd_dev_sub(fmd_dev_t *h0, const uint64_t *sub, int is_comp, unsi
     FMD_HIP_TRY(hipSetDevice(h0->device));
     const uint64_t n_sym = h0->mcnt[0], n_words = (n_sym + 63) / 64, sub_words = (h0->mcnt[1] + 63) / 64;
     const size_t wb = fmd_sub_work_bytes(n_sym);
-    uint64_t *bits = nullptr, *d_sub = nullptr; void *work = nullptr; uint8_t *buf = nullptr;
+    FmdDevBuf bits, work, d_sub, buf;
     fmd_dev *h = nullptr;
     hipStream_t st = nullptr;
-    uint64_t n_set = 0, n_out = 0, slice = 0;
-    int rc = FMD_OK;
-    if (hipMalloc((void **)&bits, n_words * 8 + 8) != hipSuccess || hipMalloc(&work, wb) != hipSuccess || hipMalloc((void **)&d_sub, sub_words * 8 + 8) != hipSuccess) {
-        (void)hipGetLastError(); rc = FMD_E_NOMEM; goto done;
-    }
-    if (hipMemsetAsync(bits, 0, n_words * 8 + 8, st) != hipSuccess || hipMemcpy(d_sub, sub, sub_words * 8, hipMemcpyHostToDevice) != hipSuccess) { rc = FMD_E_HIP; goto done; }
-    rc = fmd_sub_mark_dev(h0, st, d_sub, bits, work, wb, bits + n_words);
-    if (rc) goto done;
-    if (hipMemcpy(&n_set, bits + n_words, 8, hipMemcpyDeviceToHost) != hipSuccess) { rc = FMD_E_HIP; goto done; }
-    n_out = is_comp ? n_sym - n_set : n_set;
-    if (n_out == 0) { rc = FMD_E_ARG; goto done; }                   // nothing selected: there is no resident form of an empty index
-    slice = n_out < SUB_SLICE ? n_out : SUB_SLICE;
-    if (hipMalloc((void **)&buf, slice) != hipSuccess) { (void)hipGetLastError(); rc = FMD_E_NOMEM; goto done; }
+    uint64_t n_set = 0;
+    int rc;
+    if ((rc = bits.alloc(n_words * 8 + 8)) || (rc = work.alloc(wb)) || (rc = d_sub.alloc(sub_words * 8 + 8))) return rc;
+    uint64_t *d_n_set = bits.as<uint64_t>() + n_words;                // the count lands behind the bit array
+    if (hipMemsetAsync(bits.p, 0, n_words * 8 + 8, st) != hipSuccess || hipMemcpy(d_sub.p, sub, sub_words * 8, hipMemcpyHostToDevice) != hipSuccess) return FMD_E_HIP;
+    rc = fmd_sub_mark_dev(h0, st, d_sub.as<uint64_t>(), bits.as<uint64_t>(), work.p, wb, d_n_set);
+    if (rc) return rc;
+    if (hipMemcpy(&n_set, d_n_set, 8, hipMemcpyDeviceToHost) != hipSuccess) return FMD_E_HIP;
+    const uint64_t n_out = is_comp ? n_sym - n_set : n_set;
+    if (n_out == 0) return FMD_E_ARG;                                // nothing selected: there is no resident form of an empty index
+    const uint64_t slice = n_out < SUB_SLICE ? n_out : SUB_SLICE;
+    if ((rc = buf.alloc(slice))) return rc;
     rc = fmd_index_alloc(h0->device, n_out, &h);
-    if (rc) { h = nullptr; goto done; }
+    if (rc) return rc;
     for (uint64_t at = 0; at < n_out && rc == FMD_OK; at += slice) {
         const uint64_t m = n_out - at < slice ? n_out - at : slice;
-        rc = fmd_sub_select_dev(h0, st, bits, work, is_comp, at, m, buf);
-        if (rc == FMD_OK) rc = fmd_index_put_slice(h, st, buf, at, m);
+        rc = fmd_sub_select_dev(h0, st, bits.as<uint64_t>(), work.p, is_comp, at, m, buf.as<uint8_t>());
+        if (rc == FMD_OK) rc = fmd_index_put_slice(h, st, buf.as<uint8_t>(), at, m);
     }
     if (rc == FMD_OK) {
         hipError_t e = hipStreamSynchronize(st);
         if (e != hipSuccess) { fmd_set_hip_error(e, "sub"); rc = FMD_E_HIP; }
     }
-    hipFree(buf); buf = nullptr;
-    hipFree(work); work = nullptr;
-    hipFree(bits); bits = nullptr;
-    hipFree(d_sub); d_sub = nullptr;
+    buf.reset(); work.reset(); bits.reset(); d_sub.reset();   // the selection's own arrays go before the counts' scratch comes
     if (rc == FMD_OK) rc = fmd_index_finish(h, !(flags & FMD_OPEN_NO_TABLES));
-done:
-    if (buf) hipFree(buf);
-    if (work) hipFree(work);
-    if (bits) hipFree(bits);
-    if (d_sub) hipFree(d_sub);
-    if (rc) { if (h) fmd_dev_close(h); return rc; }
+    if (rc) { fmd_dev_close(h); return rc; }
     *out = h;
     return FMD_OK;
 }

@@ -780,15 +780,13 @@ extern "C" int fmd_ectab_build(int device, int w, int suf_len, uint64_t n, const
     if (n && (!bucket || !key || !val)) return FMD_E_ARG;
     if (fmd_device_count() <= 0) return FMD_E_NODEV;
     FMD_HIP_TRY(hipSetDevice(device));
-    void *db = nullptr, *dk = nullptr, *dv = nullptr;
-    int rc = FMD_OK;
-    if (hipMalloc(&db, n * 4 + 16) != hipSuccess || hipMalloc(&dk, n * 4 + 16) != hipSuccess || hipMalloc(&dv, n + 16) != hipSuccess) rc = FMD_E_NOMEM;
-    if (rc == FMD_OK && n && (hipMemcpy(db, bucket, n * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dk, key, n * 4, hipMemcpyHostToDevice) != hipSuccess ||
-                              hipMemcpy(dv, val, n, hipMemcpyHostToDevice) != hipSuccess)) rc = FMD_E_HIP;
-    if (rc == FMD_OK) rc = fmd_ectab_build_dev(device, nullptr, w, suf_len, n, (uint32_t *)db, (uint32_t *)dk, (uint8_t *)dv, out);
-    if (rc == FMD_OK && hipDeviceSynchronize() != hipSuccess) { rc = FMD_E_HIP; fmd_ectab_free(*out); *out = nullptr; }
-    hipFree(db); hipFree(dk); hipFree(dv);
-    return rc;
+    FmdDevBuf db, dk, dv;
+    FMD_TRY(db.alloc(n * 4 + 16)); FMD_TRY(dk.alloc(n * 4 + 16)); FMD_TRY(dv.alloc(n + 16));
+    if (n && (hipMemcpy(db.p, bucket, n * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dk.p, key, n * 4, hipMemcpyHostToDevice) != hipSuccess ||
+              hipMemcpy(dv.p, val, n, hipMemcpyHostToDevice) != hipSuccess)) return FMD_E_HIP;
+    FMD_TRY(fmd_ectab_build_dev(device, nullptr, w, suf_len, n, db.as<uint32_t>(), dk.as<uint32_t>(), dv.as<uint8_t>(), out));
+    if (hipDeviceSynchronize() != hipSuccess) { fmd_ectab_free(*out); *out = nullptr; return FMD_E_HIP; }
+    return FMD_OK;
 }
 
 static int ec_grid(int device, size_t n)   // the resident set: a workgroup (one wave) holds EC_LDS_BYTES of the CU's 160 KiB
@@ -830,32 +828,26 @@ extern "C" int fmd_ecfix_dev(fmd_ectab_t *t, void *stream_, size_t n, uint8_t *d
 // Device buffers of the host form, kept in the table handle between calls (`correct` calls it once per 10^6 reads: the work
 // area alone is 256 CUs x 16 waves x 64 lanes x ~12 KB).  One caller at a time owns them; a concurrent call allocates its own.
 struct EcBuf {
-    fmd_ectab *t; bool cached; void *p[5]; size_t bytes[5];
+    fmd_ectab *t; bool cached; FmdDevBuf b[5];
     explicit EcBuf(fmd_ectab *t_) : t(t_), cached(false)
     {
-        for (int i = 0; i < 5; ++i) { p[i] = nullptr; bytes[i] = 0; }
         int expect = 0;
         if (__atomic_compare_exchange_n(&t->buf_busy, &expect, 1, false, __ATOMIC_ACQUIRE, __ATOMIC_RELAXED)) {
             cached = true;
-            for (int i = 0; i < 5; ++i) { p[i] = t->buf[i]; bytes[i] = t->buf_bytes[i]; }
+            for (int i = 0; i < 5; ++i) { b[i].p = t->buf[i]; b[i].bytes = t->buf_bytes[i]; }
         }
     }
     void *get(int i, size_t need)   // at least `need` bytes in buffer i (contents are not kept), nullptr when the device is out of memory
     {
-        if (bytes[i] >= need && p[i]) return p[i];
-        if (p[i]) hipFree(p[i]);
-        p[i] = nullptr; bytes[i] = 0;
-        const size_t want = need + need / 8 + 256;
-        if (hipMalloc(&p[i], want) != hipSuccess) { (void)hipGetLastError(); p[i] = nullptr; return nullptr; }
-        bytes[i] = want;
-        return p[i];
+        if (b[i].bytes >= need && b[i].p) return b[i].p;
+        b[i].alloc(need + need / 8 + 256);
+        return b[i].p;
     }
-    ~EcBuf()
+    ~EcBuf()   // back to the handle; a concurrent call's own buffers go with it
     {
-        if (cached) {
-            for (int i = 0; i < 5; ++i) { t->buf[i] = p[i]; t->buf_bytes[i] = bytes[i]; }
-            __atomic_store_n(&t->buf_busy, 0, __ATOMIC_RELEASE);
-        } else for (int i = 0; i < 5; ++i) if (p[i]) hipFree(p[i]);
+        if (!cached) return;
+        for (int i = 0; i < 5; ++i) { t->buf_bytes[i] = b[i].bytes; t->buf[i] = b[i].release(); }
+        __atomic_store_n(&t->buf_busy, 0, __ATOMIC_RELEASE);
     }
 };
 

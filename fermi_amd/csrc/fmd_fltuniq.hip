@@ -21,6 +21,7 @@
 // range with those, seq.c:168 -- undefined there, a non-base here) is not a base.
 #include <stdlib.h>
 #include <string.h>
+#include <new>
 #include "fmd_internal.h"
 
 #define FU_MIN_K 3     // k < 3: the reference's table is zero words long (seq.c:161)
@@ -148,13 +149,14 @@ extern "C" int fmd_fltuniq_test_dev(int device, void *stream, int k, const uint8
 struct fmd_fltuniq_run {
     int device, k, cur;
     uint64_t max_bytes, max_reads;
-    uint64_t *table;
+    FmdDevBuf table;
     size_t table_bytes;
     struct {
-        hipStream_t st;
-        uint8_t *h_seqs, *d_seqs, *h_pass, *d_pass, *dst;   // dst: where h_pass goes once the slot's work is done (n_dst bytes)
-        uint64_t *h_off, *d_off, n_dst;
-        hipEvent_t ev0, ev1, ev2;                           // kernel start, kernel end, everything of the slot done
+        FmdStream st;                                       // (a blocking stream)
+        FmdHostBuf h_seqs, h_off, h_pass;
+        FmdDevBuf d_seqs, d_off, d_pass;
+        uint8_t *dst; uint64_t n_dst;                       // dst: where h_pass goes once the slot's work is done (n_dst bytes)
+        FmdEvent ev0, ev1, ev2;                             // (with timing) kernel start, kernel end, everything of the slot done
         int busy, kind;                                     // kind: 0 = count, 1 = test (whose kernel time ev0 -> ev1 is)
     } slot[FU_SLOTS];
     double kernel_ms[2];
@@ -166,7 +168,7 @@ static int fu_wait(fmd_fltuniq_run *f, int i)
     float ms = 0;
     FMD_HIP_TRY(hipEventSynchronize(f->slot[i].ev2));
     if (hipEventElapsedTime(&ms, f->slot[i].ev0, f->slot[i].ev1) == hipSuccess) f->kernel_ms[f->slot[i].kind] += ms;
-    if (f->slot[i].dst && f->slot[i].n_dst) memcpy(f->slot[i].dst, f->slot[i].h_pass, f->slot[i].n_dst);
+    if (f->slot[i].dst && f->slot[i].n_dst) memcpy(f->slot[i].dst, f->slot[i].h_pass.p, f->slot[i].n_dst);
     f->slot[i].dst = nullptr; f->slot[i].busy = 0;
     return FMD_OK;
 }
@@ -175,18 +177,8 @@ extern "C" void fmd_fltuniq_close(fmd_fltuniq_t *f)
 {
     if (!f) return;
     hipSetDevice(f->device);
-    for (int i = 0; i < FU_SLOTS; ++i) {
-        if (f->slot[i].st) { hipStreamSynchronize(f->slot[i].st); hipStreamDestroy(f->slot[i].st); }
-        if (f->slot[i].h_seqs) hipHostFree(f->slot[i].h_seqs);
-        if (f->slot[i].h_off) hipHostFree(f->slot[i].h_off);
-        if (f->slot[i].h_pass) hipHostFree(f->slot[i].h_pass);
-        hipFree(f->slot[i].d_seqs); hipFree(f->slot[i].d_off); hipFree(f->slot[i].d_pass);
-        if (f->slot[i].ev0) hipEventDestroy(f->slot[i].ev0);
-        if (f->slot[i].ev1) hipEventDestroy(f->slot[i].ev1);
-        if (f->slot[i].ev2) hipEventDestroy(f->slot[i].ev2);
-    }
-    hipFree(f->table);
-    free(f);
+    for (int i = 0; i < FU_SLOTS; ++i) if (f->slot[i].st) hipStreamSynchronize(f->slot[i].st);
+    delete f;   // the members free themselves
 }
 
 extern "C" int fmd_fltuniq_open(int device, int k, uint64_t max_bytes, uint64_t max_reads, fmd_fltuniq_t **out)
@@ -195,19 +187,21 @@ extern "C" int fmd_fltuniq_open(int device, int k, uint64_t max_bytes, uint64_t 
     *out = nullptr;
     if (fmd_device_count() <= 0) return FMD_E_NODEV;
     FMD_HIP_TRY(hipSetDevice(device));
-    fmd_fltuniq_run *f = (fmd_fltuniq_run *)calloc(1, sizeof(fmd_fltuniq_run));
+    fmd_fltuniq_run *f = new (std::nothrow) fmd_fltuniq_run();
     if (!f) return FMD_E_NOMEM;
     f->device = device; f->k = k; f->max_bytes = max_bytes; f->max_reads = max_reads; f->cur = -1;
     f->table_bytes = fmd_fltuniq_table_bytes(k);
-    bool ok = hipMalloc((void **)&f->table, f->table_bytes) == hipSuccess;
-    for (int i = 0; ok && i < FU_SLOTS; ++i)
-        ok = hipHostMalloc((void **)&f->slot[i].h_seqs, max_bytes + 16) == hipSuccess && hipHostMalloc((void **)&f->slot[i].h_off, (max_reads + 1) * 8) == hipSuccess &&
-             hipHostMalloc((void **)&f->slot[i].h_pass, max_reads) == hipSuccess && hipMalloc((void **)&f->slot[i].d_seqs, max_bytes + 16) == hipSuccess &&
-             hipMalloc((void **)&f->slot[i].d_off, (max_reads + 1) * 8) == hipSuccess && hipMalloc((void **)&f->slot[i].d_pass, max_reads) == hipSuccess &&
-             hipEventCreate(&f->slot[i].ev0) == hipSuccess && hipEventCreate(&f->slot[i].ev1) == hipSuccess && hipEventCreate(&f->slot[i].ev2) == hipSuccess &&
-             hipStreamCreate(&f->slot[i].st) == hipSuccess;
-    if (!ok) { fmd_set_hip_error(hipGetLastError(), "hipMalloc(fltuniq table, staging)"); fmd_fltuniq_close(f); return FMD_E_NOMEM; }
-    if (hipMemsetAsync(f->table, 0, f->table_bytes, f->slot[0].st) != hipSuccess || hipStreamSynchronize(f->slot[0].st) != hipSuccess) {
+    int rc = f->table.alloc(f->table_bytes, "hipMalloc(fltuniq table)");
+    for (int i = 0; rc == FMD_OK && i < FU_SLOTS; ++i) {
+        auto &s = f->slot[i];
+        if ((rc = s.h_seqs.alloc(max_bytes + 16)) || (rc = s.h_off.alloc((max_reads + 1) * 8)) || (rc = s.h_pass.alloc(max_reads)) ||
+            (rc = s.d_seqs.alloc(max_bytes + 16)) || (rc = s.d_off.alloc((max_reads + 1) * 8)) || (rc = s.d_pass.alloc(max_reads))) break;
+        if (s.ev0.make(hipEventDefault) || s.ev1.make(hipEventDefault) || s.ev2.make(hipEventDefault) || s.st.make(hipStreamDefault)) {
+            fmd_set_hip_error(hipGetLastError(), "fltuniq events, stream"); rc = FMD_E_NOMEM;
+        }
+    }
+    if (rc) { fmd_fltuniq_close(f); return rc; }
+    if (hipMemsetAsync(f->table.p, 0, f->table_bytes, f->slot[0].st) != hipSuccess || hipStreamSynchronize(f->slot[0].st) != hipSuccess) {
         fmd_set_hip_error(hipGetLastError(), "hipMemsetAsync(fltuniq table)"); fmd_fltuniq_close(f); return FMD_E_HIP;
     }
     *out = f;
@@ -221,7 +215,7 @@ extern "C" int fmd_fltuniq_slot(fmd_fltuniq_t *f, uint8_t **seqs, uint64_t **off
     f->cur = (f->cur + 1) % FU_SLOTS;
     const int rc = fu_wait(f, f->cur);
     if (rc != FMD_OK) return rc;
-    *seqs = f->slot[f->cur].h_seqs; *off = f->slot[f->cur].h_off;
+    *seqs = f->slot[f->cur].h_seqs.as<uint8_t>(); *off = f->slot[f->cur].h_off.as<uint64_t>();
     return FMD_OK;
 }
 
@@ -230,19 +224,20 @@ static int fu_submit(fmd_fltuniq_run *f, uint64_t n_reads, uint8_t *pass)
     if (!f || f->cur < 0 || f->slot[f->cur].busy || n_reads > f->max_reads) return FMD_E_ARG;
     if (n_reads == 0) return FMD_OK;
     auto &s = f->slot[f->cur];
-    if (s.h_off[0] != 0 || s.h_off[n_reads] > f->max_bytes) return FMD_E_ARG;
+    const uint64_t *h_off = s.h_off.as<uint64_t>();
+    if (h_off[0] != 0 || h_off[n_reads] > f->max_bytes) return FMD_E_ARG;
     FMD_HIP_TRY(hipSetDevice(f->device));
     if (pass)                                              // the table must be complete: every count of the other slots has ended
         for (int i = 0; i < FU_SLOTS; ++i)
             if (f->slot[i].busy && f->slot[i].kind == 0) { const int rc = fu_wait(f, i); if (rc != FMD_OK) return rc; }
-    FMD_HIP_TRY(hipMemcpyAsync(s.d_seqs, s.h_seqs, s.h_off[n_reads], hipMemcpyHostToDevice, s.st));
-    FMD_HIP_TRY(hipMemcpyAsync(s.d_off, s.h_off, (n_reads + 1) * 8, hipMemcpyHostToDevice, s.st));
+    FMD_HIP_TRY(hipMemcpyAsync(s.d_seqs.p, s.h_seqs.p, h_off[n_reads], hipMemcpyHostToDevice, s.st));
+    FMD_HIP_TRY(hipMemcpyAsync(s.d_off.p, h_off, (n_reads + 1) * 8, hipMemcpyHostToDevice, s.st));
     FMD_HIP_TRY(hipEventRecord(s.ev0, s.st));
-    const int rc = pass ? fmd_fltuniq_test_dev(f->device, s.st, f->k, s.d_seqs, s.d_off, n_reads, f->table, s.d_pass)
-                        : fmd_fltuniq_count_dev(f->device, s.st, f->k, s.d_seqs, s.d_off, n_reads, f->table);
+    const int rc = pass ? fmd_fltuniq_test_dev(f->device, s.st, f->k, s.d_seqs.as<uint8_t>(), s.d_off.as<uint64_t>(), n_reads, f->table.as<uint64_t>(), s.d_pass.as<uint8_t>())
+                        : fmd_fltuniq_count_dev(f->device, s.st, f->k, s.d_seqs.as<uint8_t>(), s.d_off.as<uint64_t>(), n_reads, f->table.as<uint64_t>());
     if (rc != FMD_OK) return rc;
     FMD_HIP_TRY(hipEventRecord(s.ev1, s.st));
-    if (pass) FMD_HIP_TRY(hipMemcpyAsync(s.h_pass, s.d_pass, n_reads, hipMemcpyDeviceToHost, s.st));
+    if (pass) FMD_HIP_TRY(hipMemcpyAsync(s.h_pass.p, s.d_pass.p, n_reads, hipMemcpyDeviceToHost, s.st));
     FMD_HIP_TRY(hipEventRecord(s.ev2, s.st));
     s.busy = 1; s.kind = pass ? 1 : 0; s.dst = pass; s.n_dst = pass ? n_reads : 0;
     return FMD_OK;
@@ -264,7 +259,7 @@ extern "C" int fmd_fltuniq_export(fmd_fltuniq_t *f, uint64_t first_word, uint64_
     if (!f || (n_words && !table) || first_word > f->table_bytes / 8 || n_words > f->table_bytes / 8 - first_word) return FMD_E_ARG;
     const int rc = fmd_fltuniq_sync(f, nullptr);
     if (rc != FMD_OK) return rc;
-    if (n_words) FMD_HIP_TRY(hipMemcpy(table, f->table + first_word, n_words * 8, hipMemcpyDeviceToHost));
+    if (n_words) FMD_HIP_TRY(hipMemcpy(table, f->table.as<uint64_t>() + first_word, n_words * 8, hipMemcpyDeviceToHost));
     return FMD_OK;
 }
 

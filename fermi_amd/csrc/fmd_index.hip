@@ -239,30 +239,29 @@ static int build_ptab(fmd_dev *h)
     int d = 2;
     while (d < 14 && (1ull << (2 * (d + 1))) <= h->mcnt[0] / 8 && h->mcnt[0] < (1ull << (64 - 2 * (d + 1))) - 1) ++d;
     if (getenv("FMD_PTAB_DEPTH")) { d = atoi(getenv("FMD_PTAB_DEPTH")); if (d < 1) return FMD_OK; if (d > 15) d = 15; while (d > 2 && ((1ull << (2 * d)) > h->mcnt[0] || h->mcnt[0] >= (1ull << (64 - 2 * d)) - 1)) --d; }   // (15: 17 GB, by request only)
-    uint4 *a = nullptr, *b = nullptr;
+    FmdDevBuf a, b;
     const uint64_t n = 1ull << (2 * d);
-    if (hipMalloc((void **)&a, n * 16) != hipSuccess) { (void)hipGetLastError(); return FMD_E_NOMEM; }      // (the error is the caller's to report: none is left behind for the next HIP call of the process to trip over)
-    if (hipMalloc((void **)&b, (n / 4 ? n / 4 : 1) * 16) != hipSuccess) { (void)hipGetLastError(); hipFree(a); return FMD_E_NOMEM; }
+    FMD_TRY(a.alloc(n * 16, "hipMalloc(prefix table)"));
+    FMD_TRY(b.alloc((n / 4 ? n / 4 : 1) * 16, "hipMalloc(prefix table)"));
     // levels alternate between b (odd distance from the last) and a, so that level d lands in a
     FmdIndexView ix = fmd_view(h);
     uint4 *cur = nullptr;
     for (int lv = 1; lv <= d; ++lv) {
-        uint4 *dst = ((d - lv) & 1) ? b : a;
+        uint4 *dst = ((d - lv) & 1) ? b.as<uint4>() : a.as<uint4>();
         const uint64_t m = 1ull << (2 * lv);
         k_ptab_level<<<(unsigned)((m + 255) / 256), 256>>>(ix, lv, cur, dst);
         cur = dst;
     }
     hipError_t e = hipDeviceSynchronize();
-    hipFree(b);
-    if (e != hipSuccess) { hipFree(a); fmd_set_hip_error(e, "prefix table"); return FMD_E_HIP; }
-    h->ptab = a; h->ptab_d = d;
+    b.reset();
+    if (e != hipSuccess) { fmd_set_hip_error(e, "prefix table"); return FMD_E_HIP; }
+    h->ptab = (uint4 *)a.release(); h->ptab_d = d;
     h->bytes += n * 16;
     return FMD_OK;
 }
 
 // ------------------------------------------------------------------ tail table (FmdIndexView::tail)
 #define FMD_TAIL_NONE (~0ull)
-static unsigned nblk(uint64_t n, unsigned per);
 __global__ void k_tail_table(FmdIndexView ix, int d, unsigned long long *__restrict__ tail)
 {
     for (uint64_t id = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; id < ix.n_seq; id += (uint64_t)gridDim.x * blockDim.x) {
@@ -284,49 +283,26 @@ static int build_tail(fmd_dev *h)
 {
     const char *e = getenv("FMD_TAIL_TABLE");
     if ((e && atoi(e) == 0) || !h->ptab || h->ptab_d < 2 || h->ptab_d > 15 || h->mcnt[0] >= (1ull << (64 - 2 * h->ptab_d)) - 1 || h->mcnt[1] == 0) return FMD_OK;   // 2 d bits of bases beside a row of 64 - 2 d bits
-    unsigned long long *t = nullptr;
-    if (hipMalloc((void **)&t, h->mcnt[1] * 8) != hipSuccess) { (void)hipGetLastError(); return FMD_OK; }   // no room: the walk takes its steps itself
-    k_tail_table<<<nblk(h->mcnt[1], 256), 256>>>(fmd_view(h), h->ptab_d, t);
+    FmdDevBuf t;
+    if (t.alloc(h->mcnt[1] * 8, "hipMalloc(tail table)")) return FMD_OK;   // no room: the walk takes its steps itself
+    k_tail_table<<<fmd_nblk(h->mcnt[1], 256), 256>>>(fmd_view(h), h->ptab_d, t.as<unsigned long long>());
     hipError_t err = hipDeviceSynchronize();
-    if (err != hipSuccess) { hipFree(t); fmd_set_hip_error(err, "tail table"); return FMD_E_HIP; }
-    h->tail = t;
+    if (err != hipSuccess) { fmd_set_hip_error(err, "tail table"); return FMD_E_HIP; }
+    h->tail = (unsigned long long *)t.release();
     h->bytes += h->mcnt[1] * 8;
     return FMD_OK;
 }
 
 // --------------------------------------------------------------------------------- host side
-struct FmdWiden { __host__ __device__ uint64_t operator()(fmd_bc_t v) const { return (uint64_t)v; } };
 static int scan_counts(const fmd_bc_t *d_in, uint64_t *d_out, uint64_t n, hipStream_t st)
 {
     rocprim::transform_iterator<const fmd_bc_t *, FmdWiden, uint64_t> in(d_in, FmdWiden());
-    void *tmp = nullptr; size_t tmp_bytes = 0;
-    FMD_HIP_TRY(fmd_exclusive_sum(nullptr, tmp_bytes, in, d_out, (size_t)n, st));
-    FMD_HIP_TRY(hipMalloc(&tmp, tmp_bytes ? tmp_bytes : 16));
-    hipError_t e = fmd_exclusive_sum(tmp, tmp_bytes, in, d_out, (size_t)n, st);
-    hipError_t e2 = hipStreamSynchronize(st);
-    hipFree(tmp);
-    FMD_HIP_TRY(e); FMD_HIP_TRY(e2);
-    return FMD_OK;
+    return fmd_with_tmp(st, true, "scan", [&](void *tmp, size_t &bytes) { return fmd_exclusive_sum(tmp, bytes, in, d_out, (size_t)n, st); });
 }
 
 static int scan_u64(uint64_t *d_in, uint64_t *d_out, uint64_t n, hipStream_t st)
 {
-    void *tmp = nullptr; size_t tmp_bytes = 0;
-    FMD_HIP_TRY(fmd_exclusive_sum(nullptr, tmp_bytes, d_in, d_out, (size_t)n, st));
-    FMD_HIP_TRY(hipMalloc(&tmp, tmp_bytes ? tmp_bytes : 16));
-    hipError_t e = fmd_exclusive_sum(tmp, tmp_bytes, d_in, d_out, (size_t)n, st);
-    hipError_t e2 = hipStreamSynchronize(st);
-    hipFree(tmp);
-    FMD_HIP_TRY(e); FMD_HIP_TRY(e2);
-    return FMD_OK;
-}
-
-// blocks for n items, t threads each: at most 2^31 threads per launch (the dispatch packet counts work-items in 32
-// bits; the kernels above loop with a grid stride)
-static inline unsigned nblk(uint64_t n, unsigned t)
-{
-    const uint64_t b = (n + t - 1) / t, cap = (1ull << 31) / t;
-    return (unsigned)(b < cap ? (b ? b : 1) : cap);
+    return fmd_with_tmp(st, true, "scan", [&](void *tmp, size_t &bytes) { return fmd_exclusive_sum(tmp, bytes, d_in, d_out, (size_t)n, st); });
 }
 
 static int dev_alloc_index(int device, uint64_t n_sym, fmd_dev **out)
@@ -336,20 +312,20 @@ static int dev_alloc_index(int device, uint64_t n_sym, fmd_dev **out)
     if (n_sym == 0 || n_sym >= (1ull << 40)) return FMD_E_ARG; // 40-bit absolute counts
     if ((n_sym + FMD_BLK_STRIDE - 1) / FMD_BLK_STRIDE + 1 >= 0xffffffffull) return FMD_E_ARG; // 32-bit block numbers
     FMD_HIP_TRY(hipSetDevice(device));
-    fmd_dev *h = (fmd_dev *)calloc(1, sizeof(fmd_dev));
-    if (!h) return FMD_E_NOMEM;
     hipDeviceProp_t prop;
     FMD_HIP_TRY(hipGetDeviceProperties(&prop, device));
+    fmd_dev *h = (fmd_dev *)calloc(1, sizeof(fmd_dev));
+    if (!h) return FMD_E_NOMEM;
     h->device = device;
     h->n_cu = prop.multiProcessorCount;
     h->n_blocks = (n_sym + FMD_BLK_STRIDE - 1) / FMD_BLK_STRIDE + 1; // +1 pad block
     h->bytes = h->n_blocks * FMD_BLK_BYTES;
     hipError_t e = hipMalloc((void **)&h->blocks, h->bytes);
-    if (e != hipSuccess) { fmd_set_hip_error(e, "hipMalloc(index)"); free(h); return FMD_E_NOMEM; }
+    if (e != hipSuccess) { fmd_set_hip_error(e, "hipMalloc(index)"); fmd_dev_close(h); return FMD_E_NOMEM; }
     e = hipMalloc((void **)&h->queues, FMD_N_QUEUES * sizeof(uint32_t));
-    if (e != hipSuccess) { fmd_set_hip_error(e, "hipMalloc(queues)"); hipFree(h->blocks); free(h); return FMD_E_NOMEM; }
+    if (e != hipSuccess) { fmd_set_hip_error(e, "hipMalloc(queues)"); fmd_dev_close(h); return FMD_E_NOMEM; }
     e = hipMalloc((void **)&h->stat, FMD_STAT_SLOTS * FMD_STAT_STRIDE * 8);
-    if (e != hipSuccess) { fmd_set_hip_error(e, "hipMalloc(stat)"); hipFree(h->queues); hipFree(h->blocks); free(h); return FMD_E_NOMEM; }
+    if (e != hipSuccess) { fmd_set_hip_error(e, "hipMalloc(stat)"); fmd_dev_close(h); return FMD_E_NOMEM; }
     hipMemset(h->blocks, 0, h->bytes);
     hipMemset(h->queues, 0, FMD_N_QUEUES * sizeof(uint32_t));
     hipMemset(h->stat, 0, FMD_STAT_SLOTS * FMD_STAT_STRIDE * 8);
@@ -361,18 +337,18 @@ static int dev_alloc_index(int device, uint64_t n_sym, fmd_dev **out)
 static int finish_index(fmd_dev *h, int tables = 1)
 {
     const uint64_t nb = h->n_blocks;
-    fmd_bc_t *bc = nullptr; uint64_t *acc = nullptr;
-    FMD_HIP_TRY(hipMalloc((void **)&bc, 6 * nb * sizeof(fmd_bc_t)));
-    hipError_t e = hipMalloc((void **)&acc, nb * 8);
-    if (e != hipSuccess) { hipFree(bc); fmd_set_hip_error(e, "hipMalloc(scan)"); return FMD_E_NOMEM; }
-    k_fill_lookahead<<<nblk(nb, 256), 256>>>(h->blocks, nb);
-    k_block_counts<<<nblk(nb, 256), 256>>>(h->blocks, nb, bc);
+    FmdDevBuf d_bc, d_acc;
+    FMD_TRY(d_bc.alloc(6 * nb * sizeof(fmd_bc_t), "hipMalloc(scan)"));
+    FMD_TRY(d_acc.alloc(nb * 8, "hipMalloc(scan)"));
+    fmd_bc_t *bc = d_bc.as<fmd_bc_t>(); uint64_t *acc = d_acc.as<uint64_t>();
+    k_fill_lookahead<<<fmd_nblk(nb, 256), 256>>>(h->blocks, nb);
+    k_block_counts<<<fmd_nblk(nb, 256), 256>>>(h->blocks, nb, bc);
     int rc = FMD_OK;
     uint64_t last[6] = {0, 0, 0, 0, 0, 0};
     for (int s = 0; s < 6 && rc == FMD_OK; ++s) { // one symbol at a time through the same buffer
         rc = scan_counts(bc + (uint64_t)s * nb, acc, nb, 0);
         if (rc != FMD_OK) break;
-        k_write_meta_sym<<<nblk(nb, 256), 256>>>(h->blocks, nb, acc, s);
+        k_write_meta_sym<<<fmd_nblk(nb, 256), 256>>>(h->blocks, nb, acc, s);
         // marginal count = prefix at the pad block
         if (hipMemcpy(&last[s], acc + (nb - 1), 8, hipMemcpyDeviceToHost) != hipSuccess) rc = FMD_E_HIP;
     }
@@ -384,11 +360,11 @@ static int finish_index(fmd_dev *h, int tables = 1)
         for (int s = 1; s < 6; ++s) h->mcnt[s + 1] = last[s];
         h->cnt[0] = 0;
         for (int s = 1; s < 7; ++s) h->cnt[s] = h->cnt[s - 1] + h->mcnt[s];
-        e = hipDeviceSynchronize();
+        hipError_t e = hipDeviceSynchronize();
         if (e != hipSuccess) { fmd_set_hip_error(e, "transcode"); rc = FMD_E_HIP; }
         else if (h->cnt[6] != h->mcnt[0]) rc = FMD_E_FORMAT;
     }
-    hipFree(bc); hipFree(acc);
+    d_bc.reset(); d_acc.reset();   // the counts' scratch goes before the tables come
     if (rc == FMD_OK && tables) rc = build_ptab(h);
     if (rc == FMD_OK && tables) rc = build_tail(h);
     return rc;
@@ -426,7 +402,7 @@ int fmd_index_put_slice(fmd_dev *h, hipStream_t st, const uint8_t *d_slice, uint
     if (m == 0) return FMD_OK;
     if (first + m > h->mcnt[0]) return FMD_E_ARG;
     const uint64_t words = ((first + m - 1) >> 5) - (first >> 5) + 1;
-    k_slice_to_planes<<<nblk(words, 256), 256, 0, st>>>(d_slice, first, m, h->blocks);
+    k_slice_to_planes<<<fmd_nblk(words, 256), 256, 0, st>>>(d_slice, first, m, h->blocks);
     return hipGetLastError() == hipSuccess ? FMD_OK : FMD_E_HIP;
 }
 
@@ -438,7 +414,7 @@ static int open_bwt_dev(int device, const uint8_t *d_bwt, uint64_t n, int tables
     if (rc) return rc;
     h->mcnt[0] = n;
     const uint64_t n_chunks = (n + 31) / 32;
-    k_bwt_to_planes<<<nblk(n_chunks, 256), 256>>>(d_bwt, n, h->blocks, n_chunks);
+    k_bwt_to_planes<<<fmd_nblk(n_chunks, 256), 256>>>(d_bwt, n, h->blocks, n_chunks);
     rc = finish_index(h, tables);
     if (rc) { fmd_dev_close(h); return rc; }
     *out = h;
@@ -451,12 +427,10 @@ static int open_bwt(int device, const uint8_t *bwt, uint64_t n, int tables, fmd_
     if (!bwt || !out) return FMD_E_ARG;
     if (fmd_device_count() <= 0) return FMD_E_NODEV;
     FMD_HIP_TRY(hipSetDevice(device));
-    uint8_t *d = nullptr;
-    FMD_HIP_TRY(hipMalloc((void **)&d, n + 64));
-    hipError_t e = hipMemcpy(d, bwt, n, hipMemcpyHostToDevice);
-    int rc = e == hipSuccess ? open_bwt_dev(device, d, n, tables, out) : FMD_E_HIP;
-    hipFree(d);
-    return rc;
+    FmdDevBuf d;
+    FMD_TRY(d.alloc(n + 64));
+    hipError_t e = hipMemcpy(d.p, bwt, n, hipMemcpyHostToDevice);
+    return e == hipSuccess ? open_bwt_dev(device, d.as<uint8_t>(), n, tables, out) : FMD_E_HIP;
 }
 extern "C" int fmd_dev_open_bwt(int device, const uint8_t *bwt, uint64_t n, fmd_dev_t **out) { return open_bwt(device, bwt, n, 1, out); }
 
@@ -465,71 +439,56 @@ static int open_rle6(int device, const uint8_t *runs, uint64_t n_bytes, int tabl
     if (!runs || !out || n_bytes == 0) return FMD_E_ARG;
     if (fmd_device_count() <= 0) return FMD_E_NODEV;
     FMD_HIP_TRY(hipSetDevice(device));
-    uint8_t *d_runs = nullptr; uint64_t *d_len = nullptr, *d_start = nullptr, *d_tot = nullptr;
-    int rc = FMD_OK;
+    FmdDevBuf runs_b, len_b, start_b, tot_b;
+    FMD_TRY(runs_b.alloc(n_bytes)); FMD_TRY(len_b.alloc(n_bytes * 8)); FMD_TRY(start_b.alloc(n_bytes * 8)); FMD_TRY(tot_b.alloc(8));
+    uint8_t *d_runs = runs_b.as<uint8_t>(); uint64_t *d_len = len_b.as<uint64_t>(), *d_start = start_b.as<uint64_t>(), *d_tot = tot_b.as<uint64_t>();
     fmd_dev *h = nullptr;
     uint64_t n_sym = 0;
-    FMD_HIP_TRY(hipMalloc((void **)&d_runs, n_bytes));
-    if (hipMalloc((void **)&d_len, n_bytes * 8) != hipSuccess || hipMalloc((void **)&d_start, n_bytes * 8) != hipSuccess ||
-        hipMalloc((void **)&d_tot, 8) != hipSuccess) { rc = FMD_E_NOMEM; goto done; }
     hipMemcpy(d_runs, runs, n_bytes, hipMemcpyHostToDevice);
-    k_rle6_len<<<nblk(n_bytes, 256), 256>>>(d_runs, n_bytes, d_len);
-    rc = scan_u64(d_len, d_start, n_bytes, 0);
-    if (rc) goto done;
+    k_rle6_len<<<fmd_nblk(n_bytes, 256), 256>>>(d_runs, n_bytes, d_len);
+    FMD_TRY(scan_u64(d_len, d_start, n_bytes, 0));
     { // total = start[last] + len[last]
         uint64_t a, b;
         hipMemcpy(&a, d_start + n_bytes - 1, 8, hipMemcpyDeviceToHost);
         hipMemcpy(&b, d_len + n_bytes - 1, 8, hipMemcpyDeviceToHost);
         n_sym = a + b;
     }
-    rc = dev_alloc_index(device, n_sym, &h);
-    if (rc) goto done;
+    FMD_TRY(dev_alloc_index(device, n_sym, &h));
     h->mcnt[0] = n_sym;
-    k_rle6_scatter<<<nblk(n_bytes, 256), 256>>>(d_runs, n_bytes, d_start, (uint32_t *)h->blocks, d_tot);
+    k_rle6_scatter<<<fmd_nblk(n_bytes, 256), 256>>>(d_runs, n_bytes, d_start, (uint32_t *)h->blocks, d_tot);
     // the runs go before the counts' scratch comes (hipFree waits for the scatter): the load's peak is the larger of the two, not their sum
-    hipFree(d_runs); hipFree(d_len); hipFree(d_start); hipFree(d_tot);
-    d_runs = nullptr; d_len = d_start = d_tot = nullptr;
-    rc = finish_index(h, tables);
-done:
-    hipFree(d_runs); hipFree(d_len); hipFree(d_start); hipFree(d_tot);
-    if (rc) { if (h) fmd_dev_close(h); return rc; }
+    runs_b.reset(); len_b.reset(); start_b.reset(); tot_b.reset();
+    const int rc = finish_index(h, tables);
+    if (rc) { fmd_dev_close(h); return rc; }
     *out = h;
     return FMD_OK;
 }
 extern "C" int fmd_dev_open_rle6(int device, const uint8_t *runs, uint64_t n_bytes, fmd_dev_t **out) { return open_rle6(device, runs, n_bytes, 1, out); }
 
-// The payload words of an RLD\2 file, already in device memory ((n_words / 8 + 1) * 64 bytes, zero behind the payload): the index.  Frees d_w.
-static int open_rld_words_dev(int device, uint64_t *d_w, uint64_t n_words, const uint64_t mcnt[7], int tables, fmd_dev_t **out)
+// The payload words of an RLD\2 file, already in device memory ((n_words / 8 + 1) * 64 bytes, zero behind the payload): the index.  Takes w over.
+static int open_rld_words_dev(int device, FmdDevBuf w_b, uint64_t n_words, const uint64_t mcnt[7], int tables, fmd_dev_t **out)
 {
     // blocks 0 .. last/8-1 carry payload; the block at word `last` is header-only (rld.h:64)
     const uint64_t n_rld = n_words / 8;
-    uint64_t *d_size = nullptr, *d_start = nullptr, *d_tot = nullptr;
-    int rc = FMD_OK;
+    FmdDevBuf size_b, start_b, tot_b;
+    FMD_TRY(size_b.alloc(n_rld * 8)); FMD_TRY(start_b.alloc(n_rld * 8)); FMD_TRY(tot_b.alloc(16));
+    uint64_t *d_w = w_b.as<uint64_t>(), *d_size = size_b.as<uint64_t>(), *d_start = start_b.as<uint64_t>(), *d_tot = tot_b.as<uint64_t>();
     fmd_dev *h = nullptr;
-    if (hipMalloc((void **)&d_size, n_rld * 8) != hipSuccess || hipMalloc((void **)&d_start, n_rld * 8) != hipSuccess ||
-        hipMalloc((void **)&d_tot, 16) != hipSuccess) { rc = FMD_E_NOMEM; goto done; }
     hipMemset(d_tot, 0, 16);
-    k_rld_sizes<<<nblk(n_rld, 256), 256>>>(d_w, n_rld, d_size);
-    rc = scan_u64(d_size, d_start, n_rld, 0);
-    if (rc) goto done;
-    rc = dev_alloc_index(device, mcnt[0], &h);
-    if (rc) goto done;
+    k_rld_sizes<<<fmd_nblk(n_rld, 256), 256>>>(d_w, n_rld, d_size);
+    FMD_TRY(scan_u64(d_size, d_start, n_rld, 0));
+    FMD_TRY(dev_alloc_index(device, mcnt[0], &h));
     h->mcnt[0] = mcnt[0];
-    k_rld_scatter<<<nblk(n_rld, 64), 64>>>(d_w, n_rld, d_start, (uint32_t *)h->blocks, mcnt[0], d_tot);
-    {
-        uint64_t tot[2] = {0, 0};
-        hipMemcpy(tot, d_tot, 16, hipMemcpyDeviceToHost);
-        if (tot[1] || tot[0] != mcnt[0]) { rc = FMD_E_FORMAT; goto done; }
-    }
+    k_rld_scatter<<<fmd_nblk(n_rld, 64), 64>>>(d_w, n_rld, d_start, (uint32_t *)h->blocks, mcnt[0], d_tot);
+    uint64_t tot[2] = {0, 0};
+    hipMemcpy(tot, d_tot, 16, hipMemcpyDeviceToHost);
+    int rc = tot[1] || tot[0] != mcnt[0] ? FMD_E_FORMAT : FMD_OK;
     // the payload goes before the counts' scratch comes: the load's peak is the larger of the two, not their sum
-    hipFree(d_w); hipFree(d_size); hipFree(d_start); hipFree(d_tot);
-    d_w = d_size = d_start = d_tot = nullptr;
-    rc = finish_index(h, tables);
+    w_b.reset(); size_b.reset(); start_b.reset(); tot_b.reset();
+    if (rc == FMD_OK) rc = finish_index(h, tables);
     if (rc == FMD_OK)
         for (int s = 1; s < 7; ++s) if (h->mcnt[s] != mcnt[s]) rc = FMD_E_FORMAT; // header vs decoded stream
-done:
-    hipFree(d_w); hipFree(d_size); hipFree(d_start); hipFree(d_tot);
-    if (rc) { if (h) fmd_dev_close(h); return rc; }
+    if (rc) { fmd_dev_close(h); return rc; }
     *out = h;
     return FMD_OK;
 }
@@ -541,11 +500,11 @@ extern "C" int fmd_dev_open_rld(int device, const uint64_t *payload, uint64_t n_
     FMD_HIP_TRY(hipSetDevice(device));
     const uint64_t n_rld = n_words / 8;
     if (n_rld == 0) return FMD_E_FORMAT;
-    uint64_t *d_w = nullptr;
-    FMD_HIP_TRY(hipMalloc((void **)&d_w, (n_rld + 1) * 64));
-    hipMemset(d_w, 0, (n_rld + 1) * 64);
-    hipMemcpy(d_w, payload, n_words * 8, hipMemcpyHostToDevice);
-    return open_rld_words_dev(device, d_w, n_words, mcnt, 1, out);
+    FmdDevBuf w;
+    FMD_TRY(w.alloc((n_rld + 1) * 64));
+    hipMemset(w.p, 0, (n_rld + 1) * 64);
+    hipMemcpy(w.p, payload, n_words * 8, hipMemcpyHostToDevice);
+    return open_rld_words_dev(device, std::move(w), n_words, mcnt, 1, out);
 }
 
 // The payload of a large .fmd goes from the file to the device in pieces, several threads each reading a piece into its own pinned buffer and sending it
@@ -559,8 +518,9 @@ static int upload_payload(int device, int fd, off_t at, uint64_t bytes, uint8_t 
     std::atomic<int> failed{0};
     const uint64_t n_ch = (bytes + CH - 1) / CH;
     auto work = [&]() {
-        void *stage = nullptr; hipStream_t st = nullptr;
-        if (hipSetDevice(device) != hipSuccess || hipHostMalloc(&stage, CH, hipHostMallocDefault) != hipSuccess || hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) { failed = FMD_E_HIP; if (stage) hipHostFree(stage); return; }
+        FmdHostBuf stage_b; FmdStream st;
+        if (hipSetDevice(device) != hipSuccess || stage_b.alloc(CH) || st.make()) { failed = FMD_E_HIP; return; }
+        void *stage = stage_b.p;
         for (;;) {
             const uint64_t c = next.fetch_add(1);
             if (c >= n_ch || failed) break;
@@ -570,7 +530,6 @@ static int upload_payload(int device, int fd, off_t at, uint64_t bytes, uint8_t 
             if (failed) break;
             if (hipMemcpyAsync(d_dst + off, stage, len, hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { failed = FMD_E_HIP; break; }
         }
-        hipStreamDestroy(st); hipHostFree(stage);
     };
     std::vector<std::thread> th;
     for (int k = 1; k < T && (uint64_t)k < n_ch; ++k) th.emplace_back(work);
@@ -610,13 +569,13 @@ static int open_file(int device, const char *fn, int tables, fmd_dev_t **out)
         {
             const uint64_t n_rld = n_words / 8;
             const off_t at = (off_t)ftell(fp);
-            uint64_t *d_w = nullptr;
-            if (hipMalloc((void **)&d_w, (n_rld + 1) * 64) != hipSuccess) { fclose(fp); (void)hipGetLastError(); return FMD_E_NOMEM; }
-            hipMemset((uint8_t *)d_w + n_words * 8, 0, (n_rld + 1) * 64 - n_words * 8);   // behind the payload
-            rc = upload_payload(device, fileno(fp), at, n_words * 8, (uint8_t *)d_w);
+            FmdDevBuf w;
+            if (w.alloc((n_rld + 1) * 64)) { fclose(fp); return FMD_E_NOMEM; }
+            hipMemset(w.as<uint8_t>() + n_words * 8, 0, (n_rld + 1) * 64 - n_words * 8);   // behind the payload
+            rc = upload_payload(device, fileno(fp), at, n_words * 8, w.as<uint8_t>());
             fclose(fp); // the rank frames that follow are not needed: the device layout has none
-            if (rc) { hipFree(d_w); return rc; }
-            return open_rld_words_dev(device, d_w, n_words, mcnt, tables, out);
+            if (rc) return rc;
+            return open_rld_words_dev(device, std::move(w), n_words, mcnt, tables, out);
         }
     } else {
         fseek(fp, 0, SEEK_END);
@@ -664,12 +623,11 @@ extern "C" int fmd_dev_export_bwt(fmd_dev_t *h, uint64_t first, uint64_t n, uint
     if (!h || (n && !bwt) || first > h->mcnt[0] || n > h->mcnt[0] - first) return FMD_E_ARG;
     if (n == 0) return FMD_OK;
     FMD_HIP_TRY(hipSetDevice(h->device));
-    uint8_t *d = nullptr;
-    FMD_HIP_TRY(hipMalloc((void **)&d, n));
+    FmdDevBuf d;
+    FMD_TRY(d.alloc(n));
     const uint64_t n_chunks = (first + n + 31) / 32 - first / 32;
-    k_planes_to_bwt<<<nblk(n_chunks, 256), 256>>>(h->blocks, first, n, d);
-    hipError_t e = hipMemcpy(bwt, d, n, hipMemcpyDeviceToHost);
-    hipFree(d);
+    k_planes_to_bwt<<<fmd_nblk(n_chunks, 256), 256>>>(h->blocks, first, n, d.as<uint8_t>());
+    hipError_t e = hipMemcpy(bwt, d.p, n, hipMemcpyDeviceToHost);
     if (e != hipSuccess) { fmd_set_hip_error(e, "export"); return FMD_E_HIP; }
     return FMD_OK;
 }
@@ -696,13 +654,13 @@ extern "C" int fmd_dev_check_rank(fmd_dev_t *h, uint64_t *n_bad, uint64_t *first
 {
     if (!h || !n_bad || !first_bad) return FMD_E_ARG;
     FMD_HIP_TRY(hipSetDevice(h->device));
-    unsigned long long *d = nullptr, init[2] = {0, ~0ull}, res[2];
-    FMD_HIP_TRY(hipMalloc((void **)&d, 16));
-    FMD_HIP_TRY(hipMemcpy(d, init, 16, hipMemcpyHostToDevice));
+    unsigned long long init[2] = {0, ~0ull}, res[2];
+    FmdDevBuf d;
+    FMD_TRY(d.alloc(16));
+    FMD_HIP_TRY(hipMemcpy(d.p, init, 16, hipMemcpyHostToDevice));
     const uint64_t n = h->mcnt[0];
-    if (n) k_check_rank<<<nblk(n, 256), 256>>>(fmd_view(h), d);
-    hipError_t e = hipMemcpy(res, d, 16, hipMemcpyDeviceToHost);
-    hipFree(d);
+    if (n) k_check_rank<<<fmd_nblk(n, 256), 256>>>(fmd_view(h), d.as<unsigned long long>());
+    hipError_t e = hipMemcpy(res, d.p, 16, hipMemcpyDeviceToHost);
     if (e != hipSuccess) { fmd_set_hip_error(e, "check_rank"); return FMD_E_HIP; }
     *n_bad = res[0]; *first_bad = res[1];
     return FMD_OK;

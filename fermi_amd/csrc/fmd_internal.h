@@ -52,6 +52,8 @@ void fmd_set_hip_error(hipError_t e, const char *what);
         }                                                       \
     } while (0)
 
+#define FMD_TRY(expr) do { int rc__ = (expr); if (rc__) return rc__; } while (0)   // an FMD_* code
+
 static inline FmdIndexView fmd_view(const fmd_dev *h)
 {
     FmdIndexView v;
@@ -102,3 +104,6 @@ static inline int fmd_resident_per_cu(K kernel, size_t lds_bytes, int cap, const
     if (getenv("FMD_DEBUG_OCC")) fprintf(stderr, "[occupancy] %s: %d workgroups per CU\n", name, nb);
     return nb;
 }
+
+// the owning host-side resources (device / pinned buffers, streams, events, scratch leases): a .hip file uses these and defines none
+#include "fmd_hostres.h"

@@ -381,24 +381,15 @@ __global__ void k_km_unpack(uint64_t n, const uint64_t *__restrict__ k64, uint32
 static int km_sort_triples(uint64_t m, int suf_len, uint32_t *db, uint32_t *dk, uint8_t *dv)
 {
     if (m < 2 || m > 0x7fffffffull) return FMD_OK;
-    uint64_t *ka = nullptr, *kb = nullptr; uint8_t *vb = nullptr; void *tmp = nullptr;
-    size_t tmp_bytes = 0;
-    int rc = FMD_OK;
-    if (hipMalloc((void **)&ka, m * 8) != hipSuccess || hipMalloc((void **)&kb, m * 8) != hipSuccess || hipMalloc((void **)&vb, m) != hipSuccess) rc = FMD_E_NOMEM;
-    if (rc == FMD_OK) {
-        const unsigned nb = (unsigned)((m + 255) / 256);
-        k_km_pack<<<nb, 256>>>(m, db, dk, ka);
-        const int end_bit = 32 + 2 * suf_len;
-        if (fmd_sort_pairs(nullptr, tmp_bytes, ka, kb, dv, vb, (int)m, 0, end_bit) != hipSuccess ||
-            hipMalloc(&tmp, tmp_bytes ? tmp_bytes : 16) != hipSuccess) rc = FMD_E_NOMEM;
-        else if (fmd_sort_pairs(tmp, tmp_bytes, ka, kb, dv, vb, (int)m, 0, end_bit) != hipSuccess) rc = FMD_E_HIP;
-        else {
-            k_km_unpack<<<nb, 256>>>(m, kb, db, dk);
-            if (hipMemcpy(dv, vb, m, hipMemcpyDeviceToDevice) != hipSuccess) rc = FMD_E_HIP;
-        }
-    }
-    hipFree(ka); hipFree(kb); hipFree(vb); hipFree(tmp);
-    return rc;
+    FmdDevBuf ka_b, kb_b, vb_b;
+    FMD_TRY(ka_b.alloc(m * 8)); FMD_TRY(kb_b.alloc(m * 8)); FMD_TRY(vb_b.alloc(m));
+    uint64_t *ka = ka_b.as<uint64_t>(), *kb = kb_b.as<uint64_t>(); uint8_t *vb = vb_b.as<uint8_t>();
+    const unsigned nb = (unsigned)((m + 255) / 256);
+    k_km_pack<<<nb, 256>>>(m, db, dk, ka);
+    const int end_bit = 32 + 2 * suf_len;
+    FMD_TRY(fmd_with_tmp(0, false, "sort k-mers", [&](void *tmp, size_t &bytes) { return fmd_sort_pairs(tmp, bytes, ka, kb, dv, vb, (int)m, 0, end_bit); }));
+    k_km_unpack<<<nb, 256>>>(m, kb, db, dk);
+    return hipMemcpy(dv, vb, m, hipMemcpyDeviceToDevice) == hipSuccess ? FMD_OK : FMD_E_HIP;
 }
 
 // One part of the harvest (seed_mask) on the device with the capacity grown until nothing overflows; triples sorted by
@@ -412,21 +403,21 @@ static int km_collect_part_host(fmd_dev_t *h, int w, int min_occ, int suf_len, i
             const uint64_t by_demand = demand + demand / 5 + 1024;
             cap = by_demand > 2 * cap ? by_demand : 2 * cap;
         }
-        void *work = nullptr, *db = nullptr, *dk = nullptr, *dv = nullptr, *ds = nullptr;
+        FmdDevBuf work, db_b, dk_b, dv_b, ds;
         const size_t wb = fmd_kmer_work_bytes(cap);
-        int rc = FMD_OK;
-        if (hipMalloc(&work, wb) != hipSuccess || hipMalloc(&db, cap * 4) != hipSuccess || hipMalloc(&dk, cap * 4) != hipSuccess ||
-            hipMalloc(&dv, cap) != hipSuccess || hipMalloc(&ds, 32) != hipSuccess) { (void)hipGetLastError(); rc = FMD_E_NOMEM; }
+        int rc;
+        if ((rc = work.alloc(wb)) || (rc = db_b.alloc(cap * 4)) || (rc = dk_b.alloc(cap * 4)) || (rc = dv_b.alloc(cap)) || (rc = ds.alloc(32))) return rc;   // FMD_E_NOMEM: the caller cuts the harvest into more parts
+        uint32_t *db = db_b.as<uint32_t>(), *dk = dk_b.as<uint32_t>(); uint8_t *dv = dv_b.as<uint8_t>();
         uint64_t status[4] = {0, 0, 0, 0};
-        if (rc == FMD_OK) rc = fmd_kmer_collect_part_dev(h, nullptr, w, min_occ, suf_len, seed_mask, work, wb, cap, (uint32_t *)db, (uint32_t *)dk, (uint8_t *)dv, (uint64_t *)ds);
-        if (rc == FMD_OK && hipMemcpy(status, ds, 32, hipMemcpyDeviceToHost) != hipSuccess) rc = FMD_E_HIP;
+        rc = fmd_kmer_collect_part_dev(h, nullptr, w, min_occ, suf_len, seed_mask, work.p, wb, cap, db, dk, dv, ds.as<uint64_t>());
+        if (rc == FMD_OK && hipMemcpy(status, ds.p, 32, hipMemcpyDeviceToHost) != hipSuccess) rc = FMD_E_HIP;
         if (rc == FMD_OK && status[1] != 0) {   // overflowed: the level counters (exact up to the first level that did not fit) say how much is needed
             unsigned long long lv[KM_WORDS];
-            if (hipMemcpy(lv, work, sizeof(lv), hipMemcpyDeviceToHost) == hipSuccess) { demand = 0; for (int d = 1; d <= w && d < KM_WORDS; ++d) if (lv[d] > demand) demand = lv[d]; }
+            if (hipMemcpy(lv, work.p, sizeof(lv), hipMemcpyDeviceToHost) == hipSuccess) { demand = 0; for (int d = 1; d <= w && d < KM_WORDS; ++d) if (lv[d] > demand) demand = lv[d]; }
         }
         if (rc == FMD_OK && status[1] == 0) {
-            hipFree(work); work = nullptr;   // the frontier buffers are not needed any more; the sort wants the room
-            rc = km_sort_triples(status[0], suf_len, (uint32_t *)db, (uint32_t *)dk, (uint8_t *)dv);
+            work.reset();   // the frontier buffers are not needed any more; the sort wants the room
+            rc = km_sort_triples(status[0], suf_len, db, dk, dv);
         }
         if (rc == FMD_OK && status[1] == 0) {
             const uint64_t m = status[0];
@@ -443,8 +434,7 @@ static int km_collect_part_host(fmd_dev_t *h, int w, int min_occ, int suf_len, i
                                       hipMemcpy(*val + *n, dv, m, hipMemcpyDeviceToHost) != hipSuccess)) rc = FMD_E_HIP;
             if (rc == FMD_OK) { *n += m; cnt[0] += (int64_t)status[2]; cnt[1] += (int64_t)status[3]; }
         }
-        hipFree(work); hipFree(db); hipFree(dk); hipFree(dv); hipFree(ds);
-        if (rc != FMD_OK) return rc;   // FMD_E_NOMEM: the caller cuts the harvest into more parts
+        if (rc != FMD_OK) return rc;   // (FMD_E_NOMEM from the sort too)
         if (status[1] == 0) return FMD_OK;
     }
     return FMD_E_OVERFLOW;

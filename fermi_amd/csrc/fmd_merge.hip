@@ -13,10 +13,8 @@
 // the other index at p - rank1(p) when it is not; rank1 comes from per-4096-bit prefix counts the walk leaves in d_work.
 #include <stdlib.h>
 #include <string.h>
-#include "fmd_prim.h"
 #include "fmd_kernel_common.h"
-
-#define MERGE_SB_WORDS 64                    // bit words per prefix-count superblock (4096 rows)
+#include "fmd_bits.h"
 
 // ------------------------------------------------------------------------------------------------ gap walk
 // One lane per walked sequence (persistent waves, tickets); ~0 in `i` is row -1 of the other index.
@@ -68,18 +66,6 @@ __global__ __launch_bounds__(64) void k_merge_walk(FmdIndexView w, FmdIndexView 
     }
 }
 
-// set bits of each 4096-row superblock: one wave per superblock, a lane per word
-__global__ __launch_bounds__(64) void k_merge_sb_count(const unsigned long long *__restrict__ bits, uint64_t n_words, uint64_t n_sb,
-                                                       uint64_t *__restrict__ cnt)
-{
-    for (uint64_t sb = blockIdx.x; sb < n_sb; sb += gridDim.x) {
-        const uint64_t wd = sb * MERGE_SB_WORDS + threadIdx.x;
-        int c = wd < n_words ? __popcll(bits[wd]) : 0;
-        for (int s = 32; s > 0; s >>= 1) c += __shfl_xor(c, s);
-        if (threadIdx.x == 0) cnt[sb] = (uint64_t)c;
-    }
-}
-
 // ------------------------------------------------------------------------------------------------ interleave
 // Symbol q of an index, read one 32-position plane word at a time (the caller walks q upwards).
 struct MergeCursor {
@@ -102,9 +88,9 @@ __global__ __launch_bounds__(64) void k_merge_interleave(FmdIndexView w, FmdInde
                                                          uint8_t *__restrict__ out)
 {
     const int q = fmd_lane();
-    const uint64_t sb0 = first / (64 * MERGE_SB_WORDS), sb1 = (first + n - 1) / (64 * MERGE_SB_WORDS);
+    const uint64_t sb0 = first / (64 * FMD_BITS_SB_WORDS), sb1 = (first + n - 1) / (64 * FMD_BITS_SB_WORDS);
     for (uint64_t sb = sb0 + blockIdx.x; sb <= sb1; sb += gridDim.x) {
-        const uint64_t wd = sb * MERGE_SB_WORDS + q, p0 = wd * 64;
+        const uint64_t wd = sb * FMD_BITS_SB_WORDS + q, p0 = wd * 64;
         const bool any = p0 < first + n && p0 + 64 > first;
         const uint64_t m = p0 < n_tot ? bits[wd] : 0;   // (the words before the slice count too: they are in the prefix of those in it)
         // exclusive prefix of the popcounts over the wave
@@ -124,24 +110,10 @@ __global__ __launch_bounds__(64) void k_merge_interleave(FmdIndexView w, FmdInde
 }
 
 // -------------------------------------------------------------------------------------------------- host side
-static inline hipStream_t S(void *s) { return (hipStream_t)s; }
-static inline unsigned merge_grid(uint64_t n_waves) { return (unsigned)(n_waves < (1u << 24) ? (n_waves ? n_waves : 1) : (1u << 24)); }
-
 // the walked index: the smaller one (e1 on a tie, as the reference)
 static inline int merge_walked(const fmd_dev *h0, const fmd_dev *h1) { return h1->mcnt[0] <= h0->mcnt[0] ? 1 : 0; }
 
-static size_t merge_scan_tmp_bytes(uint64_t n_sb)
-{
-    size_t b = 0;
-    if (fmd_exclusive_sum(nullptr, b, (const uint64_t *)nullptr, (uint64_t *)nullptr, (size_t)n_sb + 1, 0) != hipSuccess) return 0;
-    return b;
-}
-// work area: prefix counts (n_sb + 1), superblock counts (n_sb + 1), the scan's temporary storage
-extern "C" size_t fmd_merge_work_bytes(uint64_t n_tot)
-{
-    const uint64_t n_sb = (n_tot + 64 * MERGE_SB_WORDS - 1) / (64 * MERGE_SB_WORDS);
-    return (size_t)(2 * (n_sb + 1) * 8 + 256 + merge_scan_tmp_bytes(n_sb));
-}
+extern "C" size_t fmd_merge_work_bytes(uint64_t n_tot) { return fmd_bits_work_bytes(n_tot); }
 
 static int merge_args(const fmd_dev *h0, const fmd_dev *h1)
 {
@@ -156,8 +128,7 @@ extern "C" int fmd_merge_walk_dev(fmd_dev_t *h0, fmd_dev_t *h1, void *stream, ui
 {
     int rc = merge_args(h0, h1);
     if (rc) return rc;
-    const uint64_t n_tot = h0->mcnt[0] + h1->mcnt[0], n_words = (n_tot + 63) / 64;
-    const uint64_t n_sb = (n_words + MERGE_SB_WORDS - 1) / MERGE_SB_WORDS;
+    const uint64_t n_tot = h0->mcnt[0] + h1->mcnt[0];
     if (!d_bits || !d_work || work_bytes < fmd_merge_work_bytes(n_tot)) return FMD_E_ARG;
     FMD_HIP_TRY(hipSetDevice(h0->device));
     const int wk = merge_walked(h0, h1);
@@ -167,13 +138,8 @@ extern "C" int fmd_merge_walk_dev(fmd_dev_t *h0, fmd_dev_t *h1, void *stream, ui
     const int mark = !(on && atoi(on) == 1 && e && atoi(e) == 0);
     k_merge_walk<<<fmd_grid_for(hw, hw->mcnt[1]), 64, 0, S(stream)>>>(fmd_view(hw), fmd_view(ho), wk, n_tot, (unsigned long long *)d_bits, queue, mark);
     FMD_HIP_TRY(hipGetLastError());
-    uint64_t *pre = (uint64_t *)d_work, *cnt = pre + n_sb + 1;
-    void *tmp = (void *)(((uintptr_t)(cnt + n_sb + 1) + 255) & ~(uintptr_t)255);
-    size_t tmp_bytes = work_bytes - (size_t)((uint8_t *)tmp - (uint8_t *)d_work);
-    FMD_HIP_TRY(hipMemsetAsync(cnt + n_sb, 0, 8, S(stream)));
-    k_merge_sb_count<<<merge_grid(n_sb), 64, 0, S(stream)>>>((const unsigned long long *)d_bits, n_words, n_sb, cnt);
-    FMD_HIP_TRY(hipGetLastError());
-    FMD_HIP_TRY(fmd_exclusive_sum(tmp, tmp_bytes, (const uint64_t *)cnt, pre, (size_t)n_sb + 1, S(stream)));
+    rc = fmd_bits_rank_dev(S(stream), d_bits, n_tot, d_work, work_bytes);
+    if (rc) return rc;
     if (walked) *walked = wk;
     return FMD_OK;
 }
@@ -189,8 +155,8 @@ extern "C" int fmd_merge_interleave_dev(fmd_dev_t *h0, fmd_dev_t *h1, void *stre
     FMD_HIP_TRY(hipSetDevice(h0->device));
     const int wk = merge_walked(h0, h1);
     const fmd_dev *hw = wk ? h1 : h0, *ho = wk ? h0 : h1;
-    const uint64_t sb0 = first / (64 * MERGE_SB_WORDS), sb1 = (first + n - 1) / (64 * MERGE_SB_WORDS);
-    k_merge_interleave<<<merge_grid(sb1 - sb0 + 1), 64, 0, S(stream)>>>(fmd_view(hw), fmd_view(ho), (const unsigned long long *)d_bits,
+    const uint64_t sb0 = first / (64 * FMD_BITS_SB_WORDS), sb1 = (first + n - 1) / (64 * FMD_BITS_SB_WORDS);
+    k_merge_interleave<<<fmd_wave_grid(sb1 - sb0 + 1), 64, 0, S(stream)>>>(fmd_view(hw), fmd_view(ho), (const unsigned long long *)d_bits,
                                                                       (const uint64_t *)d_work, n_tot, first, n, d_out);
     FMD_HIP_TRY(hipGetLastError());
     return FMD_OK;
@@ -207,35 +173,27 @@ extern "C" int fmd_dev_merge_ex(fmd_dev_t *h0, fmd_dev_t *h1, unsigned flags, fm
     const uint64_t n_tot = h0->mcnt[0] + h1->mcnt[0], n_words = (n_tot + 63) / 64;
     const size_t wb = fmd_merge_work_bytes(n_tot);
     const uint64_t slice = n_tot < MERGE_SLICE ? n_tot : MERGE_SLICE;
-    uint64_t *bits = nullptr; void *work = nullptr; uint8_t *buf = nullptr;
+    FmdDevBuf bits, work, buf;
     fmd_dev *h = nullptr;
     hipStream_t st = nullptr;
-    if (hipMalloc((void **)&bits, n_words * 8) != hipSuccess || hipMalloc(&work, wb) != hipSuccess || hipMalloc((void **)&buf, slice) != hipSuccess) {
-        (void)hipGetLastError(); rc = FMD_E_NOMEM; goto done;
-    }
-    if (hipMemsetAsync(bits, 0, n_words * 8, st) != hipSuccess) { rc = FMD_E_HIP; goto done; }
-    rc = fmd_merge_walk_dev(h0, h1, st, bits, work, wb, nullptr);
-    if (rc) goto done;
+    if ((rc = bits.alloc(n_words * 8)) || (rc = work.alloc(wb)) || (rc = buf.alloc(slice))) return rc;
+    if (hipMemsetAsync(bits.p, 0, n_words * 8, st) != hipSuccess) return FMD_E_HIP;
+    rc = fmd_merge_walk_dev(h0, h1, st, bits.as<uint64_t>(), work.p, wb, nullptr);
+    if (rc) return rc;
     rc = fmd_index_alloc(h0->device, n_tot, &h);
-    if (rc) { h = nullptr; goto done; }
+    if (rc) return rc;
     for (uint64_t at = 0; at < n_tot && rc == FMD_OK; at += slice) {
         const uint64_t m = n_tot - at < slice ? n_tot - at : slice;
-        rc = fmd_merge_interleave_dev(h0, h1, st, bits, work, at, m, buf);
-        if (rc == FMD_OK) rc = fmd_index_put_slice(h, st, buf, at, m);
+        rc = fmd_merge_interleave_dev(h0, h1, st, bits.as<uint64_t>(), work.p, at, m, buf.as<uint8_t>());
+        if (rc == FMD_OK) rc = fmd_index_put_slice(h, st, buf.as<uint8_t>(), at, m);
     }
     if (rc == FMD_OK) {
         hipError_t e = hipStreamSynchronize(st);
         if (e != hipSuccess) { fmd_set_hip_error(e, "merge"); rc = FMD_E_HIP; }
     }
-    hipFree(buf); buf = nullptr;
-    hipFree(work); work = nullptr;
-    hipFree(bits); bits = nullptr;
+    buf.reset(); work.reset(); bits.reset();   // the merge's own arrays go before the counts' scratch comes
     if (rc == FMD_OK) rc = fmd_index_finish(h, !(flags & FMD_OPEN_NO_TABLES));
-done:
-    if (buf) hipFree(buf);
-    if (work) hipFree(work);
-    if (bits) hipFree(bits);
-    if (rc) { if (h) fmd_dev_close(h); return rc; }
+    if (rc) { fmd_dev_close(h); return rc; }
     *out = h;
     return FMD_OK;
 }

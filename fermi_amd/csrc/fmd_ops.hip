@@ -436,8 +436,6 @@ __global__ __launch_bounds__(64) void k_retrieve(FmdIndexView ix, size_t n, cons
 }
 
 // ------------------------------------------------------------------------------- host entry
-static inline hipStream_t S(void *s) { return (hipStream_t)s; }
-
 #define FMD_CHECK_LAUNCH()                                              \
     do {                                                                \
         hipError_t e__ = hipGetLastError();                             \
@@ -532,22 +530,16 @@ extern "C" int fmd_retrieve_dev(fmd_dev_t *h, void *stream, size_t n, const uint
 }
 
 // ---- host-pointer convenience forms: copy in, run, copy out, synchronise --------------------
-struct DevBuf {
-    void *p = nullptr;
-    int alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16) == hipSuccess ? FMD_OK : FMD_E_NOMEM; }
-    ~DevBuf() { if (p) hipFree(p); }
-};
-#define TRY_RC(x) do { int rc__ = (x); if (rc__) return rc__; } while (0)
 
 extern "C" int fmd_rank1a_batch(fmd_dev_t *h, size_t n, const uint64_t *k, uint64_t *ok, int8_t *sym)
 {
     if (!h || (n && (!k || !ok))) return FMD_E_ARG;
     if (n == 0) return FMD_OK;
     FMD_HIP_TRY(hipSetDevice(h->device));
-    DevBuf dk, dok, ds;
-    TRY_RC(dk.alloc(n * 8)); TRY_RC(dok.alloc(n * 48)); TRY_RC(ds.alloc(n));
+    FmdDevBuf dk, dok, ds;
+    FMD_TRY(dk.alloc(n * 8)); FMD_TRY(dok.alloc(n * 48)); FMD_TRY(ds.alloc(n));
     FMD_HIP_TRY(hipMemcpy(dk.p, k, n * 8, hipMemcpyHostToDevice));
-    TRY_RC(fmd_rank1a_dev(h, nullptr, n, (uint64_t *)dk.p, (uint64_t *)dok.p, (int8_t *)ds.p));
+    FMD_TRY(fmd_rank1a_dev(h, nullptr, n, (uint64_t *)dk.p, (uint64_t *)dok.p, (int8_t *)ds.p));
     FMD_HIP_TRY(hipMemcpy(ok, dok.p, n * 48, hipMemcpyDeviceToHost));
     if (sym) FMD_HIP_TRY(hipMemcpy(sym, ds.p, n, hipMemcpyDeviceToHost));
     return FMD_OK;
@@ -558,11 +550,11 @@ extern "C" int fmd_rank2a_batch(fmd_dev_t *h, size_t n, const uint64_t *k, const
     if (!h || (n && (!k || !l || !ok || !ol))) return FMD_E_ARG;
     if (n == 0) return FMD_OK;
     FMD_HIP_TRY(hipSetDevice(h->device));
-    DevBuf dk, dl, dok, dol;
-    TRY_RC(dk.alloc(n * 8)); TRY_RC(dl.alloc(n * 8)); TRY_RC(dok.alloc(n * 48)); TRY_RC(dol.alloc(n * 48));
+    FmdDevBuf dk, dl, dok, dol;
+    FMD_TRY(dk.alloc(n * 8)); FMD_TRY(dl.alloc(n * 8)); FMD_TRY(dok.alloc(n * 48)); FMD_TRY(dol.alloc(n * 48));
     FMD_HIP_TRY(hipMemcpy(dk.p, k, n * 8, hipMemcpyHostToDevice));
     FMD_HIP_TRY(hipMemcpy(dl.p, l, n * 8, hipMemcpyHostToDevice));
-    TRY_RC(fmd_rank2a_dev(h, nullptr, n, (uint64_t *)dk.p, (uint64_t *)dl.p, (uint64_t *)dok.p, (uint64_t *)dol.p));
+    FMD_TRY(fmd_rank2a_dev(h, nullptr, n, (uint64_t *)dk.p, (uint64_t *)dl.p, (uint64_t *)dok.p, (uint64_t *)dol.p));
     FMD_HIP_TRY(hipMemcpy(ok, dok.p, n * 48, hipMemcpyDeviceToHost));
     FMD_HIP_TRY(hipMemcpy(ol, dol.p, n * 48, hipMemcpyDeviceToHost));
     return FMD_OK;
@@ -573,11 +565,11 @@ extern "C" int fmd_extend_batch(fmd_dev_t *h, size_t n, const fmd_intv_t *ik, co
     if (!h || (n && (!ik || !is_back || !ok))) return FMD_E_ARG;
     if (n == 0) return FMD_OK;
     FMD_HIP_TRY(hipSetDevice(h->device));
-    DevBuf di, db, dok;
-    TRY_RC(di.alloc(n * 32)); TRY_RC(db.alloc(n)); TRY_RC(dok.alloc(n * 192));
+    FmdDevBuf di, db, dok;
+    FMD_TRY(di.alloc(n * 32)); FMD_TRY(db.alloc(n)); FMD_TRY(dok.alloc(n * 192));
     FMD_HIP_TRY(hipMemcpy(di.p, ik, n * 32, hipMemcpyHostToDevice));
     FMD_HIP_TRY(hipMemcpy(db.p, is_back, n, hipMemcpyHostToDevice));
-    TRY_RC(fmd_extend_dev(h, nullptr, n, (fmd_intv_t *)di.p, (uint8_t *)db.p, (fmd_intv_t *)dok.p));
+    FMD_TRY(fmd_extend_dev(h, nullptr, n, (fmd_intv_t *)di.p, (uint8_t *)db.p, (fmd_intv_t *)dok.p));
     FMD_HIP_TRY(hipMemcpy(ok, dok.p, n * 192, hipMemcpyDeviceToHost));
     return FMD_OK;
 }
@@ -589,11 +581,11 @@ extern "C" int fmd_bsearch_batch(fmd_dev_t *h, size_t n, const uint8_t *seqs, co
     if (n == 0) return FMD_OK;
     FMD_HIP_TRY(hipSetDevice(h->device));
     const size_t total = off[n];
-    DevBuf ds, doff, dc, dbg, den;
-    TRY_RC(ds.alloc(total + 8)); TRY_RC(doff.alloc((n + 1) * 8)); TRY_RC(dc.alloc(n * 8)); TRY_RC(dbg.alloc(n * 8)); TRY_RC(den.alloc(n * 8));
+    FmdDevBuf ds, doff, dc, dbg, den;
+    FMD_TRY(ds.alloc(total + 8)); FMD_TRY(doff.alloc((n + 1) * 8)); FMD_TRY(dc.alloc(n * 8)); FMD_TRY(dbg.alloc(n * 8)); FMD_TRY(den.alloc(n * 8));
     FMD_HIP_TRY(hipMemcpy(ds.p, seqs, total, hipMemcpyHostToDevice));
     FMD_HIP_TRY(hipMemcpy(doff.p, off, (n + 1) * 8, hipMemcpyHostToDevice));
-    TRY_RC(fmd_bsearch_dev(h, nullptr, n, (uint8_t *)ds.p, (uint64_t *)doff.p, (uint64_t *)dc.p, (uint64_t *)dbg.p, (uint64_t *)den.p));
+    FMD_TRY(fmd_bsearch_dev(h, nullptr, n, (uint8_t *)ds.p, (uint64_t *)doff.p, (uint64_t *)dc.p, (uint64_t *)dbg.p, (uint64_t *)den.p));
     FMD_HIP_TRY(hipMemcpy(cnt, dc.p, n * 8, hipMemcpyDeviceToHost));
     FMD_HIP_TRY(hipMemcpy(beg, dbg.p, n * 8, hipMemcpyDeviceToHost));
     FMD_HIP_TRY(hipMemcpy(end, den.p, n * 8, hipMemcpyDeviceToHost));
@@ -605,11 +597,11 @@ extern "C" int fmd_reach_batch(fmd_dev_t *h, size_t n_bytes, const uint8_t *seqs
     if (!h || (n_bytes && (!seqs || !len))) return FMD_E_ARG;
     if (n_bytes == 0) return FMD_OK;
     FMD_HIP_TRY(hipSetDevice(h->device));
-    DevBuf ds, dl;
-    TRY_RC(ds.alloc(n_bytes + 8)); TRY_RC(dl.alloc(n_bytes * 4));
+    FmdDevBuf ds, dl;
+    FMD_TRY(ds.alloc(n_bytes + 8)); FMD_TRY(dl.alloc(n_bytes * 4));
     FMD_HIP_TRY(hipMemset((uint8_t *)ds.p + (n_bytes & ~(size_t)3), 0, 8 + (n_bytes & 3))); // zero terminator after the last sequence
     FMD_HIP_TRY(hipMemcpy(ds.p, seqs, n_bytes, hipMemcpyHostToDevice));
-    TRY_RC(fmd_reach_dev(h, nullptr, n_bytes, (uint8_t *)ds.p, (uint32_t *)dl.p));
+    FMD_TRY(fmd_reach_dev(h, nullptr, n_bytes, (uint8_t *)ds.p, (uint32_t *)dl.p));
     FMD_HIP_TRY(hipMemcpy(len, dl.p, n_bytes * 4, hipMemcpyDeviceToHost));
     return FMD_OK;
 }
@@ -620,11 +612,11 @@ extern "C" int fmd_retrieve_batch(fmd_dev_t *h, size_t n, const uint64_t *x, uin
     if (!h || (n && (!x || !seqs || !len || !rank || !stride))) return FMD_E_ARG;
     if (n == 0) return FMD_OK;
     FMD_HIP_TRY(hipSetDevice(h->device));
-    DevBuf dx, ds, dl, dr;
-    TRY_RC(dx.alloc(n * 8)); TRY_RC(ds.alloc(n * (size_t)stride)); TRY_RC(dl.alloc(n * 4)); TRY_RC(dr.alloc(n * 8));
+    FmdDevBuf dx, ds, dl, dr;
+    FMD_TRY(dx.alloc(n * 8)); FMD_TRY(ds.alloc(n * (size_t)stride)); FMD_TRY(dl.alloc(n * 4)); FMD_TRY(dr.alloc(n * 8));
     FMD_HIP_TRY(hipMemcpy(dx.p, x, n * 8, hipMemcpyHostToDevice));
     FMD_HIP_TRY(hipMemset(ds.p, 0, n * (size_t)stride));
-    TRY_RC(fmd_retrieve_dev(h, nullptr, n, (uint64_t *)dx.p, (uint8_t *)ds.p, stride, (uint32_t *)dl.p, (uint64_t *)dr.p));
+    FMD_TRY(fmd_retrieve_dev(h, nullptr, n, (uint64_t *)dx.p, (uint8_t *)ds.p, stride, (uint32_t *)dl.p, (uint64_t *)dr.p));
     FMD_HIP_TRY(hipMemcpy(seqs, ds.p, n * (size_t)stride, hipMemcpyDeviceToHost));
     FMD_HIP_TRY(hipMemcpy(len, dl.p, n * 4, hipMemcpyDeviceToHost));
     FMD_HIP_TRY(hipMemcpy(rank, dr.p, n * 8, hipMemcpyDeviceToHost));

@@ -1162,7 +1162,6 @@ __global__ __launch_bounds__(64) void k_ovl_cls(FmdIndexView ix, size_t n, int m
 }
 
 // ------------------------------------------------------------------------------- host entry
-static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 // tickets per atomic of a walk launch (FmdTickets::chunk): `dflt` for large launches, never more than a 64th of a wave's share
 // (the last chunks of a launch are worked off by fewer and fewer waves); the environment variable is the A/B knob
 static int walk_gate(const char *env, int dflt) { const char *e = getenv(env); int g = e ? atoi(e) : dflt; return g < 0 ? 0 : g > 64 ? 64 : g; }   // lanes that must be idle before any takes a new strand (k_ovl_walk)
@@ -1592,8 +1591,10 @@ static int ovl_head(fmd_dev *h, hipStream_t st, size_t n, const uint64_t *d_ids,
         { const char *e = getenv("FMD_HEAD_WAVES"); if (e && atoi(e) > 0 && grid > h->n_cu * atoi(e)) grid = h->n_cu * atoi(e); }
         bool pairs = ix.pair != nullptr && ix.pair_tab != nullptr && n >= 4096 && n < 0xffffff00ull;
         { const char *e = getenv("FMD_PAIR_USE"); if (e && atoi(e) == 0) pairs = false; }   // A/B switch on a handle that has the blocks
-        uint32_t *strag = pairs ? (uint32_t *)fmd_scratch_acquire(h, (n + 1) * 4) : nullptr;
-        if (pairs && strag) {
+        FmdScratch strag_l, adm2_l;
+        if (pairs) strag_l.alloc(h, (n + 1) * 4);
+        uint32_t *strag = strag_l.as<uint32_t>();
+        if (strag) {
             // single steps up to `from` (by then a strand's interval is narrow), two bases per request from there to FMD_WALK_SPLIT (k_ovl_pair), and
             // the strands that kernel could not take all the way once more from their admission records, single steps all the way
             int from = 16;
@@ -1610,23 +1611,22 @@ static int ovl_head(fmd_dev *h, hipStream_t st, size_t n, const uint64_t *d_ids,
             uint32_t n_strag = 0;
             hipError_t e1 = hipMemcpyAsync(&n_strag, strag, 4, hipMemcpyDeviceToHost, st);
             if (e1 == hipSuccess) e1 = hipStreamSynchronize(st);
-            if (e1 != hipSuccess) { fmd_set_hip_error(e1, "two-base pass"); fmd_scratch_release(h, strag); return FMD_E_HIP; }
+            if (e1 != hipSuccess) { fmd_set_hip_error(e1, "two-base pass"); return FMD_E_HIP; }
             if (n_strag) {
-                uint4 *adm2 = (uint4 *)fmd_scratch_acquire(h, (size_t)n_strag * 32);
-                if (!adm2) { fmd_scratch_release(h, strag); return FMD_E_NOMEM; }
+                if (adm2_l.alloc(h, (size_t)n_strag * 32)) return FMD_E_NOMEM;
+                uint4 *adm2 = adm2_l.as<uint4>();
                 k_ovl_strag_adm<<<(n_strag + 255) / 256 < 65536 ? (n_strag + 255) / 256 : 65536, 256, 0, st>>>(strag, adm, adm2);
                 uint32_t *q3 = fmd_next_queue(h, st);
                 int grid3 = fmd_grid_for_lds(h, n_strag, FMD_COMPACT_LDS_U4 * 16);
                 k_ovl_walk<WALK_HEAD><<<grid3, 64, 0, st>>>(ix, n_strag, d_ids, min_match, nullptr, (uint32_t)sizeof(FmdWalkPark), 0, nullptr, d_rec,
                                                          nullptr, seq_stride, q3, 0, park, nullptr, adm2, walk_ticket_chunk("FMD_HEAD_TICKETS", 256, n_strag, grid3), nullptr, nullptr, 0);
                 e1 = hipStreamSynchronize(st);      // (adm2 goes back to the handle's cache)
-                fmd_scratch_release(h, adm2);
-                if (e1 != hipSuccess) { fmd_set_hip_error(e1, "two-base pass"); fmd_scratch_release(h, strag); return FMD_E_HIP; }
+                adm2_l.reset();
+                if (e1 != hipSuccess) { fmd_set_hip_error(e1, "two-base pass"); return FMD_E_HIP; }
             }
-            fmd_scratch_release(h, strag);
+            strag_l.reset();
             if (getenv("FMD_DEBUG_PAIR")) fprintf(stderr, "[M::ovl_head] two-base pass from depth %d: %u of %zu strands walked again one base at a time\n", from, n_strag, n);
         } else {
-        if (strag) fmd_scratch_release(h, strag);
         k_ovl_walk<WALK_HEAD><<<grid, 64, 0, st>>>(ix, n, d_ids, min_match, nullptr, (uint32_t)sizeof(FmdWalkPark), 0, nullptr, d_rec,
                                                 nullptr, seq_stride, q, 0, park, nullptr, adm, walk_ticket_chunk("FMD_HEAD_TICKETS", 256, n, grid), nullptr, nullptr, walk_gate("FMD_HEAD_GATE", 0) << 16);
         }
@@ -1839,25 +1839,6 @@ extern "C" int fmd_seqinfo_dev(fmd_dev_t *h, void *stream_, size_t n, const uint
     return FMD_OK;
 }
 
-struct DevBuf2 {
-    void *p = nullptr;
-    int alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16) == hipSuccess ? FMD_OK : FMD_E_NOMEM; }
-    ~DevBuf2() { if (p) hipFree(p); }
-};
-
-// hipHostRegister for the lifetime of a scope; only for large arrays, silently skipped when it fails
-struct HostPin {
-    void *p;
-    HostPin(void *ptr, size_t bytes) : p(nullptr)
-    {
-        if (bytes >= ((size_t)64 << 20) && !getenv("FMD_NO_PIN") && hipHostRegister(ptr, bytes, hipHostRegisterDefault) == hipSuccess) p = ptr;
-        else (void)hipGetLastError();
-    }
-    ~HostPin() { if (p) hipHostUnregister(p); }
-    HostPin(const HostPin &) = delete;
-    HostPin &operator=(const HostPin &) = delete;
-};
-
 extern "C" int fmd_ovlp_batch(fmd_dev_t *h, size_t n, const uint64_t *ids, int min_match, uint32_t max_len, uint32_t max_nei,
                               fmd_ovlp_rec_t *rec, fmd_intv_t *nei, uint8_t *seq, uint32_t seq_stride, int with_check_left)
 {
@@ -1872,12 +1853,13 @@ extern "C" int fmd_ovlp_batch(fmd_dev_t *h, size_t n, const uint64_t *ids, int m
     if (chunk < (1u << 16)) chunk = 1u << 16;
     const size_t m = n < chunk ? n : chunk;
     const size_t wb = fmd_ovlp_work_bytes(m, max_len, min_match);
-    DevBuf2 di, dr, dn, ds, dw;
+    FmdDevBuf di, dr, dn, ds, dw;
     if (di.alloc(m * 8) || dr.alloc(m * sizeof(fmd_ovlp_rec_t)) || dn.alloc(m * max_nei * sizeof(fmd_intv_t)) ||
         ds.alloc(m * (size_t)seq_stride) || dw.alloc(wb)) return FMD_E_NOMEM;
     // Gigabytes come back per call: pin the caller's arrays for its duration so the copies run at link speed
     // instead of through the runtime's staging buffers (best effort; pageable copies otherwise).
-    HostPin pin_rec(rec, n * sizeof(fmd_ovlp_rec_t)), pin_nei(nei, n * max_nei * sizeof(fmd_intv_t)), pin_seq(seq, n * (size_t)seq_stride);
+    const size_t pin_min = (size_t)64 << 20;
+    FmdHostPin pin_rec(rec, n * sizeof(fmd_ovlp_rec_t), pin_min), pin_nei(nei, n * max_nei * sizeof(fmd_intv_t), pin_min), pin_seq(seq, n * (size_t)seq_stride, pin_min);
     for (size_t o = 0; o < n; o += m) {
         const size_t c = n - o < m ? n - o : m;
         FMD_HIP_TRY(hipMemcpy(di.p, ids + o, c * 8, hipMemcpyHostToDevice));
@@ -1906,7 +1888,7 @@ extern "C" int fmd_seqinfo_batch(fmd_dev_t *h, size_t n, const uint64_t *ids, ui
     const size_t m = n < chunk ? n : chunk;
     const uint32_t stride = (uint32_t)align_up(max_len, 4);
     const size_t wb = fmd_ovlp_work_bytes(m, max_len, (int)max_len - 1);
-    DevBuf2 di, dr, ds, dw;
+    FmdDevBuf di, dr, ds, dw;
     if (di.alloc(m * 8) || dr.alloc(m * sizeof(fmd_ovlp_rec_t)) || ds.alloc(m * (size_t)stride) || dw.alloc(wb)) return FMD_E_NOMEM;
     for (size_t o = 0; o < n; o += m) {
         const size_t c = n - o < m ? n - o : m;

@@ -245,38 +245,34 @@ static inline unsigned nblk(size_t n, unsigned per) { size_t b = (n + per - 1) /
 
 // ------------------------------------------------------------------------------------------------ the job object
 namespace {
-struct DBuf {   // device memory owned by the job
-    void *p = nullptr; size_t bytes = 0;
-    int need(size_t b) { if (b <= bytes) return FMD_OK; if (p) { hipFree(p); p = nullptr; bytes = 0; } if (hipMalloc(&p, b ? b : 16) != hipSuccess) { (void)hipGetLastError(); return FMD_E_NOMEM; } bytes = b; return FMD_OK; }
-    void drop() { if (p) hipFree(p); p = nullptr; bytes = 0; }
-};
 // FMD_DIST_DRY=1: fmd_ovlp_dist_new says what it allocates (every buffer of a step, the root's table and -- what a step would only allocate as rows arrive -- the
 // arena of the variable parts at its usual size), so that the sizes of a configuration can be proven on ONE rank with a stand-in communicator of the
 // intended world size before N ranks try (tools/scale_check.py `dry`)
 static bool dist_dry() { static const bool v = getenv("FMD_DIST_DRY") && atoi(getenv("FMD_DIST_DRY")) != 0; return v; }
-struct HBuf {   // pinned host memory owned by the job
-    void *p = nullptr; size_t bytes = 0;
-    int need(size_t b) { if (b <= bytes) return FMD_OK; if (p) { hipHostFree(p); p = nullptr; bytes = 0; } if (hipHostMalloc(&p, b ? b : 16, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return FMD_E_NOMEM; } bytes = b; return FMD_OK; }
-    void drop() { if (p) hipHostFree(p); p = nullptr; bytes = 0; }
-};
-struct Arena {  // variable parts at the root: large chunks, allocated when first needed, kept between steps
+struct Arena {  // variable parts at the root: large chunks (pinned host or device memory), allocated when first needed, kept between steps
     bool host = false;
     size_t chunk_bytes = 0;
-    std::vector<void *> chunks;
+    std::vector<FmdDevBuf> dev;
+    std::vector<FmdHostBuf> pin;
     size_t cur = 0, used = 0;   // chunk in use, bytes used in it
     void reset() { cur = 0; used = 0; }
+    size_t n_chunks() const { return host ? pin.size() : dev.size(); }
+    bool grow()
+    {
+        if (host) { pin.emplace_back(); if (pin.back().alloc(chunk_bytes) == FMD_OK) return true; pin.pop_back(); }
+        else { dev.emplace_back(); if (dev.back().alloc(chunk_bytes) == FMD_OK) return true; dev.pop_back(); }
+        return false;
+    }
     void *take(size_t bytes)
     {
         bytes = (bytes + 255) & ~(size_t)255;
         if (bytes > chunk_bytes) return nullptr;
-        if (cur < chunks.size() && used + bytes > chunk_bytes) { ++cur; used = 0; }
-        if (cur >= chunks.size()) {
-            void *p = nullptr;
-            if ((host ? hipHostMalloc(&p, chunk_bytes, hipHostMallocDefault) : hipMalloc(&p, chunk_bytes)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-            chunks.push_back(p);
-            cur = chunks.size() - 1; used = 0;
+        if (cur < n_chunks() && used + bytes > chunk_bytes) { ++cur; used = 0; }
+        if (cur >= n_chunks()) {
+            if (!grow()) return nullptr;
+            cur = n_chunks() - 1; used = 0;
         }
-        void *r = (uint8_t *)chunks[cur] + used;
+        void *r = (uint8_t *)(host ? pin[cur].p : dev[cur].p) + used;
         used += bytes;
         return r;
     }
@@ -289,21 +285,16 @@ struct Arena {  // variable parts at the root: large chunks, allocated when firs
         if (each == 0 || n_takes == 0) return true;
         if (each > chunk_bytes) return false;
         const size_t per_chunk = chunk_bytes / each;
-        const size_t in_cur = cur < chunks.size() ? (chunk_bytes - used) / each : 0;
+        const size_t in_cur = cur < n_chunks() ? (chunk_bytes - used) / each : 0;
         const size_t more = n_takes > in_cur ? (n_takes - in_cur + per_chunk - 1) / per_chunk : 0;
-        const size_t want = (cur < chunks.size() ? cur + 1 : chunks.size()) + more;
-        while (chunks.size() < want) {
-            void *p = nullptr;
-            if ((host ? hipHostMalloc(&p, chunk_bytes, hipHostMallocDefault) : hipMalloc(&p, chunk_bytes)) != hipSuccess) { (void)hipGetLastError(); return false; }
-            chunks.push_back(p);
-        }
+        const size_t want = (cur < n_chunks() ? cur + 1 : n_chunks()) + more;
+        while (n_chunks() < want) if (!grow()) return false;
         return true;
     }
     void shrink_last(size_t taken, size_t kept) { taken = (taken + 255) & ~(size_t)255; kept = (kept + 255) & ~(size_t)255; if (kept < taken && used >= taken - kept) used -= taken - kept; }
-    void drop() { for (void *p : chunks) { if (host) hipHostFree(p); else hipFree(p); } chunks.clear(); reset(); }
 };
-struct Stage { DBuf pid, prec, off, var, vaddr; };   // one piece of one peer on its way through HBM (host table), or this rank's piece on its way out
-struct HStage { HBuf pid, prec, off, var; uint64_t rows = 0; };   // root with a row sink: where such a piece lands in pinned host memory, until the sink has had it
+struct Stage { FmdDevBuf pid, prec, off, var, vaddr; };   // one piece of one peer on its way through HBM (host table), or this rank's piece on its way out
+struct HStage { FmdHostBuf pid, prec, off, var; uint64_t rows = 0; };   // root with a row sink: where such a piece lands in pinned host memory, until the sink has had it
 }   // namespace
 
 struct fmd_ovlp_dist {
@@ -312,20 +303,20 @@ struct fmd_ovlp_dist {
     uint32_t stride;
     uint64_t n_home, cap_rows, n_rows;          // strands of pass 1; capacity / number of the rows this rank computes
     size_t piece_max, var_cap_piece;
-    DBuf ids_home, ids_loc, park_home, park_send, park_loc, keys, order, iota, rec, nei, seq, work, pack_work, cnt_dev, sizes_dev, split_dev;
-    HBuf cnt_host, sizes_host, split_host;
+    FmdDevBuf ids_home, ids_loc, park_home, park_send, park_loc, keys, order, iota, rec, nei, seq, work, pack_work, cnt_dev, sizes_dev, split_dev;
+    FmdHostBuf cnt_host, sizes_host, split_host;
     Stage out[2];                               // this rank's piece on its way out (non-root: set 0; root with a host table: set p & 1)
     std::vector<Stage> in[2];                   // root, host mode: staging per peer, two sets
     int sink = 0;                               // root, cfg.host_table == 2: no table -- every piece goes to cfg.row_sink from ...
     std::vector<HStage> hin[2];                 // ... these, set p & 1 (rows != 0: the sink has not had them yet)
     // the table at the root
-    DBuf t_prec, t_ids, t_vaddr, t_row_of, t_off;   // (t_off: per peer (piece_max + 1) offsets of the piece being placed)
-    HBuf th_prec, th_ids, th_vaddr, th_row_of;
+    FmdDevBuf t_prec, t_ids, t_vaddr, t_row_of, t_off;   // (t_off: per peer (piece_max + 1) offsets of the piece being placed)
+    FmdHostBuf th_prec, th_ids, th_vaddr, th_row_of;
     Arena var;
-    hipStream_t sm = nullptr, s3 = nullptr;
-    std::vector<hipEvent_t> done;               // piece p computed (compute stream)
-    hipEvent_t ev[8] = {};                      // timing + joins
-    hipEvent_t staged[2] = {}, drained[2] = {};
+    FmdStream sm, s3;
+    std::vector<FmdEvent> done;                 // piece p computed (compute stream)
+    FmdEvent ev[8];                             // timing + joins
+    FmdEvent staged[2], drained[2];
     fmd_ovlp_dist_stats_t last;
     const uint64_t *loc_ids;                    // ids of the rows this rank computed in the last step
 };
@@ -344,21 +335,8 @@ extern "C" void fmd_ovlp_dist_free(fmd_ovlp_dist_t *d)
     if (!d) return;
     hipSetDevice(d->h->device);
     hipDeviceSynchronize();
-    DBuf *bs[] = {&d->ids_home, &d->ids_loc, &d->park_home, &d->park_send, &d->park_loc, &d->keys, &d->order, &d->iota, &d->rec, &d->nei, &d->seq, &d->work, &d->pack_work, &d->cnt_dev, &d->split_dev,
-                  &d->sizes_dev, &d->t_prec, &d->t_ids, &d->t_vaddr, &d->t_row_of, &d->t_off, &d->out[0].pid, &d->out[0].prec, &d->out[0].off, &d->out[0].var, &d->out[0].vaddr, &d->out[1].pid, &d->out[1].prec, &d->out[1].off, &d->out[1].var, &d->out[1].vaddr};
-    for (DBuf *b : bs) b->drop();
-    for (int k = 0; k < 2; ++k) for (Stage &s : d->in[k]) { s.pid.drop(); s.prec.drop(); s.off.drop(); s.var.drop(); s.vaddr.drop(); }
-    for (int k = 0; k < 2; ++k) for (HStage &s : d->hin[k]) { s.pid.drop(); s.prec.drop(); s.off.drop(); s.var.drop(); }
-    HBuf *hs[] = {&d->cnt_host, &d->sizes_host, &d->split_host, &d->th_prec, &d->th_ids, &d->th_vaddr, &d->th_row_of};
-    for (HBuf *b : hs) b->drop();
-    d->var.drop();
-    for (hipEvent_t e : d->done) if (e) hipEventDestroy(e);
-    for (hipEvent_t e : d->ev) if (e) hipEventDestroy(e);
-    for (int k = 0; k < 2; ++k) { if (d->staged[k]) hipEventDestroy(d->staged[k]); if (d->drained[k]) hipEventDestroy(d->drained[k]); }
-    if (d->sm) hipStreamDestroy(d->sm);
-    if (d->s3) hipStreamDestroy(d->s3);
+    delete d;   // the members free themselves
     (void)hipGetLastError();
-    delete d;
 }
 
 extern "C" int fmd_ovlp_dist_new(fmd_dev_t *h, fmd_comm_t *comm, const fmd_ovlp_dist_cfg_t *cfg, fmd_ovlp_dist_t **out)
@@ -463,14 +441,14 @@ extern "C" int fmd_ovlp_dist_new(fmd_dev_t *h, fmd_comm_t *comm, const fmd_ovlp_
             const size_t want = (size_t)n * (size_t)(cfg->max_nei * 8 + 72);
             size_t got = 0;
             while (got < want) {
-                d->var.cur = d->var.chunks.size(); d->var.used = 0;
+                d->var.cur = d->var.n_chunks(); d->var.used = 0;
                 if (!d->var.take(d->var.chunk_bytes)) { rc = FMD_E_NOMEM; break; }
                 got += d->var.chunk_bytes;
             }
             d->var.reset();
             (d->on_host ? dry_host : dry_dev) += got;
             fprintf(stderr, "[M::fmd_ovlp_dist_new] rank %d/%d: %-24s %8.2f GB of %s in %zu chunks%s\n", d->rank, d->world, "variable parts (arena)", got / 1e9,
-                    d->on_host ? "pinned host memory" : "HBM", d->var.chunks.size(), rc == FMD_OK ? "" : "  <- FAILED");
+                    d->on_host ? "pinned host memory" : "HBM", d->var.n_chunks(), rc == FMD_OK ? "" : "  <- FAILED");
         }
     }
     for (int k = 0; k < (root && d->on_host ? 2 : (root ? 0 : 1)); ++k) { NEED(d->out[k].pid, d->piece_max * 4); NEED(d->out[k].prec, d->piece_max * sizeof(fmd_ovlp_rec_t)); NEED(d->out[k].off, (d->piece_max + 1) * 8); NEED(d->out[k].var, d->var_cap_piece); }
@@ -483,13 +461,13 @@ extern "C" int fmd_ovlp_dist_new(fmd_dev_t *h, fmd_comm_t *comm, const fmd_ovlp_
         int lo = 0, hi = 0;
         // the second stream at the compute stream's priority: measured on one GPU (tools/dist_one_rank.py), 10^8 strands, pass 2 takes 242 ms beside
         // the pack at equal priority (243 without any pack) and 265 ms when the pack's stream is the device's highest; FMD_DIST_HIGH_PRIORITY is the A/B knob
-        bool ok = getenv("FMD_DIST_HIGH_PRIORITY") && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && hipStreamCreateWithPriority(&d->sm, hipStreamNonBlocking, hi) == hipSuccess;
-        if (!ok) { (void)hipGetLastError(); ok = hipStreamCreateWithFlags(&d->sm, hipStreamNonBlocking) == hipSuccess; }
-        ok = ok && hipStreamCreateWithFlags(&d->s3, hipStreamNonBlocking) == hipSuccess;
-        d->done.resize((size_t)d->pieces, nullptr);
-        for (int p = 0; p < d->pieces && ok; ++p) ok = hipEventCreateWithFlags(&d->done[(size_t)p], hipEventDisableTiming) == hipSuccess;
-        for (int k = 0; k < 8 && ok; ++k) ok = hipEventCreate(&d->ev[k]) == hipSuccess;
-        for (int k = 0; k < 2 && ok; ++k) ok = hipEventCreateWithFlags(&d->staged[k], hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&d->drained[k], hipEventDisableTiming) == hipSuccess;
+        bool ok = getenv("FMD_DIST_HIGH_PRIORITY") && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && hipStreamCreateWithPriority(&d->sm.s, hipStreamNonBlocking, hi) == hipSuccess;
+        if (!ok) { (void)hipGetLastError(); ok = d->sm.make() == FMD_OK; }
+        ok = ok && d->s3.make() == FMD_OK;
+        d->done.resize((size_t)d->pieces);
+        for (int p = 0; p < d->pieces && ok; ++p) ok = d->done[(size_t)p].make() == FMD_OK;
+        for (int k = 0; k < 8 && ok; ++k) ok = d->ev[k].make(hipEventDefault) == FMD_OK;   // (with timing)
+        for (int k = 0; k < 2 && ok; ++k) ok = d->staged[k].make() == FMD_OK && d->drained[k].make() == FMD_OK;
         if (!ok) { fmd_set_hip_error(hipGetLastError(), "overlap job on N GPUs: streams and events"); rc = FMD_E_HIP; }
     }
     if (rc != FMD_OK) { fmd_ovlp_dist_free(d); return rc; }

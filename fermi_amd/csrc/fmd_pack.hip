@@ -327,7 +327,9 @@ extern "C" int fmd_ovlp_link_dev(fmd_dev_t *h, void *stream_, size_t n, fmd_ovlp
     size_t blocks = (n + 255) / 256;
     if (blocks > (1u << 20)) blocks = 1u << 20;
     const int force_exact = getenv("FMD_CHECK_LEFT_EXACT") != nullptr;
-    unsigned long long *map = getenv("FMD_LINK_MAP32") ? nullptr : (unsigned long long *)fmd_scratch_acquire(h, n * 8);   // (kept by the handle between calls; FMD_LINK_MAP32: the A/B switch)
+    FmdScratch map_l;   // (kept by the handle between calls; FMD_LINK_MAP32: the A/B switch)
+    if (!getenv("FMD_LINK_MAP32")) map_l.alloc(h, n * 8);
+    unsigned long long *map = map_l.as<unsigned long long>();
     if (!map) {   // no room for 8 bytes per position (or asked not to): the 4-byte map in the caller's array, three look-ups per edge
         (void)hipGetLastError();
         FMD_HIP_TRY(hipMemsetAsync(d_row_of, 0xff, n * 4, st));
@@ -337,14 +339,13 @@ extern "C" int fmd_ovlp_link_dev(fmd_dev_t *h, void *stream_, size_t n, fmd_ovlp
         if (e32 != hipSuccess) { fmd_set_hip_error(e32, "link kernels"); return FMD_E_HIP; }
         return FMD_OK;
     }
-    if (hipMemsetAsync(map, 0xff, n * 8, st) != hipSuccess) { fmd_set_hip_error(hipGetLastError(), "link kernels"); fmd_scratch_release(h, map); return FMD_E_HIP; }
+    if (hipMemsetAsync(map, 0xff, n * 8, st) != hipSuccess) { fmd_set_hip_error(hipGetLastError(), "link kernels"); return FMD_E_HIP; }
     k_link_rows<<<(unsigned)blocks, 256, 0, st>>>(n, d_rec, map);
     k_link_edges<<<(unsigned)blocks, 256, 0, st>>>(n, d_rec, d_nei_x01, nei_stride_u64, map, d_link, d_undecided, (unsigned long long *)d_n_undecided, force_exact);
     k_link_row_of<<<(unsigned)blocks, 256, 0, st>>>(n, map, d_row_of);
     hipError_t e = hipGetLastError();
     // the map goes back to the handle's cache when the stream has passed the kernels that read it
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    fmd_scratch_release(h, map);
     if (e != hipSuccess) { fmd_set_hip_error(e, "link kernels"); return FMD_E_HIP; }
     return FMD_OK;
 }
@@ -360,30 +361,6 @@ __global__ void k_fill_ids(size_t n, uint64_t first, uint64_t step, uint64_t *id
 {
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) ids[i] = first + step * i;
-}
-
-namespace {
-struct DevMem { // from the handle's buffer cache: the same sizes come back call after call
-    fmd_dev *h = nullptr;
-    void *p = nullptr;
-    int alloc(fmd_dev *h_, size_t bytes) { h = h_; p = fmd_scratch_acquire(h, bytes); return p ? FMD_OK : FMD_E_NOMEM; }
-    ~DevMem() { if (p) fmd_scratch_release(h, p); }
-};
-struct Stream {
-    hipStream_t s = nullptr;
-    int make() { return hipStreamCreateWithFlags(&s, hipStreamNonBlocking) == hipSuccess ? FMD_OK : FMD_E_HIP; }
-    ~Stream() { if (s) hipStreamDestroy(s); }
-};
-struct Event {
-    hipEvent_t e = nullptr;
-    int make() { return hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess ? FMD_OK : FMD_E_HIP; }
-    ~Event() { if (e) hipEventDestroy(e); }
-};
-struct Pinned { // hipHostRegister for a scope (best effort: pageable copies otherwise)
-    void *p = nullptr;
-    void pin(void *ptr, size_t bytes) { if (bytes >= ((size_t)8 << 20) && !getenv("FMD_NO_PIN") && !getenv("FMD_TABLE_DIR") && hipHostRegister(ptr, bytes, hipHostRegisterDefault) == hipSuccess) p = ptr; else (void)hipGetLastError(); }   // (FMD_TABLE_DIR: the table is not to be held in RAM)
-    ~Pinned() { if (p) hipHostUnregister(p); }
-};
 }
 
 // ---- host memory of the tables (include/fmd_hip.h: fmd_table_alloc) --------------------------------------------------------
@@ -463,11 +440,6 @@ __global__ void k_take_reserved(size_t n, const fmd_ovlp_rec_t *__restrict__ rec
 
 // where the packed chunks go when the caller does not want them kept: a callback over two pinned staging sets (the streamed forms below)
 struct RowSink { fmd_ovlp_rows_fn fn; void *ctx; };
-struct PinnedBuf { // hipHostMalloc for a scope
-    void *p = nullptr;
-    int alloc(size_t bytes) { return hipHostMalloc(&p, bytes ? bytes : 8, hipHostMallocDefault) == hipSuccess ? FMD_OK : FMD_E_NOMEM; }
-    ~PinnedBuf() { if (p) hipHostFree(p); }
-};
 
 static int packed_batch_core(fmd_dev_t *h, const uint64_t *ids, uint64_t first, uint64_t step, size_t n, int min_match, uint32_t max_len,
                              uint32_t max_nei, int with_check_left, fmd_ovlp_rec_t *rec, uint64_t *off, uint32_t chunk_shift, uint8_t **chunks,
@@ -487,9 +459,9 @@ static int packed_batch_core(fmd_dev_t *h, const uint64_t *ids, uint64_t first, 
     const size_t wb0 = fmd_ovlp_work_bytes(m, max_len, min_match), wb1 = fmd_ovlp_pack_work_bytes(m), wb = wb0 > wb1 ? wb0 : wb1;
     const size_t cap = fmd_ovlp_pack_max_bytes(m, max_nei, stride);
     if (!sink) for (size_t c = 0; c < n_chunks; ++c) chunks[c] = nullptr;
-    DevMem d_ids, d_rec, d_nei, d_seq, d_work, d_prec[2], d_off[2], d_var[2];
-    Stream s_cmp, s_cpy;
-    Event done[2], copied[2];
+    FmdScratch d_ids, d_rec, d_nei, d_seq, d_work, d_prec[2], d_off[2], d_var[2];
+    FmdStream s_cmp, s_cpy;
+    FmdEvent done[2], copied[2];
     // Large tables: ALL rows from one sorted job (fmd_ovlp_sorted_dev: the order that keeps neighbours on the genome in flight together)
     // into fixed-stride arrays for the whole table, which the chunks are then packed from in id order.  Taken when those arrays + the
     // job's work area fit beside what is in HBM already; otherwise chunk by chunk in id order, as before.
@@ -513,14 +485,17 @@ static int packed_batch_core(fmd_dev_t *h, const uint64_t *ids, uint64_t first, 
     for (int k = 0; k < 2; ++k)
         if (d_prec[k].alloc(h, m * sizeof(fmd_ovlp_rec_t)) || d_off[k].alloc(h, (m + 1) * 8) || d_var[k].alloc(h, cap) || done[k].make() || copied[k].make()) return FMD_E_NOMEM;
     if (s_cmp.make() || s_cpy.make()) return FMD_E_HIP;
-    Pinned pin_rec, pin_off;
-    PinnedBuf st_rec[2], st_adj[2], st_var[2], st_off;        // the sink's staging sets (pieces of SUB rows), and the offsets of a whole chunk
+    // the caller's arrays and chunks are registered for the copies (best effort: pageable copies otherwise) -- but not under FMD_TABLE_DIR: registering every
+    // chunk until the end of the pass would hold the whole table in RAM, which is what it is there to avoid
+    const size_t pin_min = getenv("FMD_TABLE_DIR") ? ~(size_t)0 : (size_t)8 << 20;
+    FmdHostPin pin_rec, pin_off;
+    FmdHostBuf st_rec[2], st_adj[2], st_var[2], st_off;        // the sink's staging sets (pieces of SUB rows), and the offsets of a whole chunk
     size_t st_var_cap[2] = {0, 0};
-    Event sub_done[2];
+    FmdEvent sub_done[2];
     const size_t sub_m = m < SUB ? m : SUB;
     if (!sink) {
-        pin_rec.pin(rec, n * sizeof(fmd_ovlp_rec_t));
-        pin_off.pin(off, n * 8);
+        pin_rec.pin(rec, n * sizeof(fmd_ovlp_rec_t), pin_min);
+        pin_off.pin(off, n * 8, pin_min);
     } else {
         if (st_off.alloc((m + 1) * 8)) return FMD_E_NOMEM;
         for (int k = 0; k < 2; ++k) {
@@ -528,11 +503,12 @@ static int packed_batch_core(fmd_dev_t *h, const uint64_t *ids, uint64_t first, 
             if (st_rec[k].alloc(sub_m * sizeof(fmd_ovlp_rec_t)) || st_adj[k].alloc((sub_m + 1) * 8) || st_var[k].alloc(st_var_cap[k]) || sub_done[k].make()) return FMD_E_NOMEM;
         }
     }
-    uint64_t *tot = nullptr;            // pinned landing place of the two chunk totals
-    FMD_HIP_TRY(hipHostMalloc((void **)&tot, 2 * sizeof(uint64_t), hipHostMallocDefault));
+    FmdHostBuf tot_b;                   // pinned landing place of the two chunk totals
+    FMD_TRY(tot_b.alloc(2 * sizeof(uint64_t)));
+    uint64_t *tot = tot_b.as<uint64_t>();
     t_alloc = now() - t_begin;
     int rc = FMD_OK;
-    std::vector<void *> registered;
+    std::vector<FmdHostPin> registered;
     auto fail = [&](int code) { rc = code; };
     double t_job = 0;
     if (sorted_batch) {   // every row of the table, once
@@ -591,7 +567,6 @@ static int packed_batch_core(fmd_dev_t *h, const uint64_t *ids, uint64_t first, 
                     const uint64_t b0 = offs[r0], bytes = offs[r0 + nr] - b0;
                     t0 = now();
                     if (bytes > st_var_cap[ks]) {   // (the caller finished with this set two pieces ago)
-                        hipHostFree(st_var[ks].p); st_var[ks].p = nullptr;
                         st_var_cap[ks] = bytes + bytes / 4;
                         if (st_var[ks].alloc(st_var_cap[ks])) { fail(FMD_E_NOMEM); break; }
                     }
@@ -627,9 +602,7 @@ static int packed_batch_core(fmd_dev_t *h, const uint64_t *ids, uint64_t first, 
             void *buf = fmd_table_alloc(bytes ? bytes : 64);
             if (!buf) { fail(FMD_E_NOMEM); break; }
             chunks[p] = (uint8_t *)buf;
-            // (file pages are not pinned: registering every chunk until the end of the pass would hold the whole table in RAM, which is what FMD_TABLE_DIR is there to avoid)
-            if (bytes >= ((size_t)8 << 20) && !getenv("FMD_NO_PIN") && !getenv("FMD_TABLE_DIR") && hipHostRegister(buf, bytes, hipHostRegisterDefault) == hipSuccess) registered.push_back(buf);
-            else (void)hipGetLastError();
+            registered.emplace_back(buf, bytes, pin_min);
             if (hipMemcpyAsync(rec + b, d_prec[k].p, np * sizeof(fmd_ovlp_rec_t), hipMemcpyDeviceToHost, s_cpy.s) != hipSuccess ||
                 hipMemcpyAsync(off + b, d_off[k].p, np * 8, hipMemcpyDeviceToHost, s_cpy.s) != hipSuccess ||
                 (bytes && hipMemcpyAsync(buf, d_var[k].p, bytes, hipMemcpyDeviceToHost, s_cpy.s) != hipSuccess) ||
@@ -642,8 +615,7 @@ static int packed_batch_core(fmd_dev_t *h, const uint64_t *ids, uint64_t first, 
     hipStreamSynchronize(s_cpy.s);
     if (timing) fprintf(stderr, "[M::%s] %zu rows in %zu chunks%s: device buffers + pinning %.3f s, sorted job %.3f s, waiting for kernels / copies %.3f s, host allocation + copy issue %.3f s, the caller's sink %.3f s, last copy %.3f s, total %.3f s\n",
                         __func__, n, n_chunks, sorted_batch ? " (all rows from one sorted job)" : " (chunk by chunk in id order)", t_alloc, t_job, t_wait, t_host, t_sink, now() - t_tail0, now() - t_begin);
-    for (void *q : registered) hipHostUnregister(q);
-    hipHostFree(tot);
+    registered.clear();
     if (rc == FMD_OK) {
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) { fmd_set_hip_error(e, "packed overlap batch"); rc = FMD_E_HIP; }
@@ -669,7 +641,7 @@ extern "C" int fmd_ovlp_packed_table(fmd_dev_t *h, size_t n, int min_match, uint
     if (n == 0) return FMD_OK;
     if (n >= 0xffffffffull) return FMD_E_ARG;
     FMD_HIP_TRY(hipSetDevice(h->device));
-    DevMem d_rec_all, d_nei01, d_row_of, d_link, d_und, d_nund, d_res;
+    FmdScratch d_rec_all, d_nei01, d_row_of, d_link, d_und, d_nund, d_res;
     if (d_rec_all.alloc(h, n * sizeof(fmd_ovlp_rec_t)) || d_nei01.alloc(h, n * 16) || d_row_of.alloc(h, n * 4) || d_link.alloc(h, n * sizeof(fmd_ovlp_link_t)) ||
         d_und.alloc(h, n * 8) || d_nund.alloc(h, 8) || d_res.alloc(h, n)) return FMD_E_NOMEM;
     KeepRows keep{(fmd_ovlp_rec_t *)d_rec_all.p, (uint64_t *)d_nei01.p};
@@ -716,7 +688,7 @@ extern "C" int fmd_ovlp_packed_stream(fmd_dev_t *h, const uint64_t *ids, uint64_
 struct fmd_ovlp_tabjob {
     fmd_dev *h = nullptr;
     size_t n = 0;
-    DevMem rec_all, nei01;
+    FmdScratch rec_all, nei01;
 };
 extern "C" void fmd_ovlp_tabjob_free(fmd_ovlp_tabjob_t *j) { delete j; }
 extern "C" int fmd_ovlp_tabjob_rows(fmd_dev_t *h, size_t n, int min_match, uint32_t max_len, uint32_t max_nei, uint32_t chunk_shift,
@@ -753,7 +725,7 @@ extern "C" int fmd_ovlp_tabjob_patch(fmd_ovlp_tabjob_t *j, size_t m, const uint6
     if (!j || (m && (!ids || !rec || !nei01))) return FMD_E_ARG;
     if (m == 0) return FMD_OK;
     FMD_HIP_TRY(hipSetDevice(j->h->device));
-    DevMem d_ids, d_rec, d_n01;
+    FmdScratch d_ids, d_rec, d_n01;
     if (d_ids.alloc(j->h, m * 8) || d_rec.alloc(j->h, m * sizeof(fmd_ovlp_rec_t)) || d_n01.alloc(j->h, m * 16)) return FMD_E_NOMEM;
     FMD_HIP_TRY(hipMemcpy(d_ids.p, ids, m * 8, hipMemcpyHostToDevice));
     FMD_HIP_TRY(hipMemcpy(d_rec.p, rec, m * sizeof(fmd_ovlp_rec_t), hipMemcpyHostToDevice));
@@ -772,7 +744,7 @@ extern "C" int fmd_ovlp_tabjob_link(fmd_ovlp_tabjob_t *j, fmd_ovlp_links_fn fn, 
     if (n == 0) return FMD_OK;
     fmd_dev *h = j->h;
     FMD_HIP_TRY(hipSetDevice(h->device));
-    DevMem d_row_of, d_link, d_und, d_nund, d_res;
+    FmdScratch d_row_of, d_link, d_und, d_nund, d_res;
     if (d_row_of.alloc(h, n * 4) || d_link.alloc(h, n * sizeof(fmd_ovlp_link_t)) || d_und.alloc(h, n * 8) || d_nund.alloc(h, 8) || d_res.alloc(h, n)) return FMD_E_NOMEM;
     int rc = fmd_ovlp_link_dev(h, nullptr, n, (fmd_ovlp_rec_t *)j->rec_all.p, (const uint64_t *)j->nei01.p, 2, (uint32_t *)d_row_of.p, (fmd_ovlp_link_t *)d_link.p,
                                (uint64_t *)d_und.p, (uint64_t *)d_nund.p);
@@ -781,7 +753,7 @@ extern "C" int fmd_ovlp_tabjob_link(fmd_ovlp_tabjob_t *j, fmd_ovlp_links_fn fn, 
     if (blocks > (1u << 20)) blocks = 1u << 20;
     k_take_reserved<<<(unsigned)blocks, 256>>>(n, (const fmd_ovlp_rec_t *)j->rec_all.p, (uint8_t *)d_res.p);
     const size_t piece = (size_t)1 << 22;
-    PinnedBuf st_link, st_res;
+    FmdHostBuf st_link, st_res;
     if (st_link.alloc(piece * sizeof(fmd_ovlp_link_t)) || st_res.alloc(piece)) return FMD_E_NOMEM;
     for (size_t b = 0; b < n && rc == FMD_OK; b += piece) {
         const size_t m = n - b < piece ? n - b : piece;

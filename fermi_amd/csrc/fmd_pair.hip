@@ -9,12 +9,6 @@
 #include "fmd_prim.h"
 #include <stdlib.h>
 
-static inline unsigned pnblk(uint64_t n, unsigned t)
-{
-    const uint64_t b = (n + t - 1) / t, cap = (1ull << 31) / t;
-    return (unsigned)(b < cap ? (b ? b : 1) : cap);
-}
-
 // symbol at position q, straight from the rank blocks in HBM
 __device__ __forceinline__ int pair_sym_at(const uint4 *__restrict__ blocks, uint64_t q)
 {
@@ -124,8 +118,6 @@ __global__ void k_pair_k2(FmdIndexView ix, unsigned long long *__restrict__ k2)
     k2[i] = ix.cnt[c2] + r;
 }
 
-struct PairWiden { __host__ __device__ uint64_t operator()(uint8_t v) const { return (uint64_t)v; } };
-
 // Build the two-base blocks of `h` (idempotent): 32 bits per symbol beside the index's 8, ~1 s per 10^10 symbols.  They pay where an index serves many
 // passes (pass 1 of the sorted overlap job 47.8 -> 36.3 ms per 10^8 strands, profiles/r6_pair) and never within ONE pass, so nothing builds them unasked:
 // force = fmd_dev_build_pairs (a caller that keeps the index), FMD_PAIR=1 the same from the first sorted job of any caller (A/B, tests), FMD_PAIR=0 never.
@@ -146,32 +138,32 @@ int fmd_pairs_ensure(fmd_dev *h, int force)
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return FMD_OK; }
     // by default only where the job that follows still finds its room: the blocks, their construction, and as much again as the index itself
     if (want < 2 && need + temp + h->bytes + ((size_t)8 << 30) > free_b) return FMD_OK;
-    uint4 *pair = nullptr; uint8_t *pc = nullptr; uint64_t *acc = nullptr; unsigned long long *tab = nullptr, *k2d = nullptr;
+    FmdDevBuf pair_b, pc_b, acc_b, tab_b, k2d_b, tmp;
     const uint64_t n_sb = ((nb - 1) >> FMD_PAIR_SB_SHIFT) + 1;
-    bool ok = hipMalloc((void **)&pair, need) == hipSuccess && hipMalloc((void **)&pc, (size_t)nb * 16) == hipSuccess && hipMalloc((void **)&acc, (size_t)nb * 8) == hipSuccess &&
-              hipMalloc((void **)&tab, n_sb * 16 * 8) == hipSuccess && hipMalloc((void **)&k2d, 16 * 8) == hipSuccess;
+    bool ok = !pair_b.alloc(need) && !pc_b.alloc((size_t)nb * 16) && !acc_b.alloc((size_t)nb * 8) && !tab_b.alloc(n_sb * 16 * 8) && !k2d_b.alloc(16 * 8);
     unsigned long long k2[16];
-    void *tmp = nullptr; size_t tmp_bytes = 0;
+    size_t tmp_bytes = 0;
     if (ok) {
+        uint4 *pair = pair_b.as<uint4>(); uint8_t *pc = pc_b.as<uint8_t>(); uint64_t *acc = acc_b.as<uint64_t>();
+        unsigned long long *tab = tab_b.as<unsigned long long>(), *k2d = k2d_b.as<unsigned long long>();
         const FmdIndexView ix = fmd_view(h);
         ok = hipMemsetAsync(pair, 0, need, 0) == hipSuccess;
         k_pair_k2<<<1, 64>>>(ix, k2d);
-        k_pair_planes<<<pnblk(nrb, 4), 256>>>(ix, nrb, nb, pair, pc);
-        k_pair_lookahead<<<pnblk(nb, 256), 256>>>(pair, nb);
+        k_pair_planes<<<fmd_nblk(nrb, 4), 256>>>(ix, nrb, nb, pair, pc);
+        k_pair_lookahead<<<fmd_nblk(nb, 256), 256>>>(pair, nb);
         ok = ok && hipMemcpy(k2, k2d, sizeof(k2), hipMemcpyDeviceToHost) == hipSuccess;
-        rocprim::transform_iterator<const uint8_t *, PairWiden, uint64_t> in0(pc, PairWiden());
-        ok = ok && fmd_exclusive_sum(nullptr, tmp_bytes, in0, acc, (size_t)nb, 0) == hipSuccess && hipMalloc(&tmp, tmp_bytes ? tmp_bytes : 16) == hipSuccess;
+        rocprim::transform_iterator<const uint8_t *, FmdWiden, uint64_t> in0(pc, FmdWiden());
+        ok = ok && fmd_exclusive_sum(nullptr, tmp_bytes, in0, acc, (size_t)nb, 0) == hipSuccess && !tmp.alloc(tmp_bytes);
         for (int pr = 0; pr < 16 && ok; ++pr) {
-            rocprim::transform_iterator<const uint8_t *, PairWiden, uint64_t> in(pc + (size_t)pr * nb, PairWiden());
-            ok = fmd_exclusive_sum(tmp, tmp_bytes, in, acc, (size_t)nb, 0) == hipSuccess;
-            k_pair_counts<<<pnblk(nb, 256), 256>>>(pair, nb, acc, pr, k2[pr], tab);
+            rocprim::transform_iterator<const uint8_t *, FmdWiden, uint64_t> in(pc + (size_t)pr * nb, FmdWiden());
+            ok = fmd_exclusive_sum(tmp.p, tmp_bytes, in, acc, (size_t)nb, 0) == hipSuccess;
+            k_pair_counts<<<fmd_nblk(nb, 256), 256>>>(pair, nb, acc, pr, k2[pr], tab);
         }
         ok = ok && hipDeviceSynchronize() == hipSuccess;
     }
     (void)hipGetLastError();
-    hipFree(tmp); hipFree(pc); hipFree(acc); hipFree(k2d);
-    if (!ok) { hipFree(pair); hipFree(tab); (void)hipGetLastError(); return FMD_OK; }
-    h->pair = pair; h->pair_tab = tab;
+    if (!ok) return FMD_OK;
+    h->pair = (uint4 *)pair_b.release(); h->pair_tab = (unsigned long long *)tab_b.release();
     h->pair_bytes = need + n_sb * 128;
     h->bytes += h->pair_bytes;
     if (getenv("FMD_DEBUG_PAIR")) fprintf(stderr, "[M::fmd_pairs_ensure] two-base blocks: %.2f GB, %llu superblocks\n", need / 1e9, (unsigned long long)n_sb);
@@ -241,13 +233,13 @@ extern "C" int fmd_dev_check_pairs(fmd_dev_t *h, uint64_t *n_bad, uint64_t *firs
     if (!h || !n_bad) return FMD_E_ARG;
     if (!h->pair) return FMD_E_ARG;
     FMD_HIP_TRY(hipSetDevice(h->device));
-    unsigned long long *bad = nullptr, host[2] = {0, 0};
-    FMD_HIP_TRY(hipMalloc((void **)&bad, 16));
-    FMD_HIP_TRY(hipMemset(bad, 0, 16));
-    k_pair_check<<<h->n_cu * 16, 256>>>(fmd_view(h), bad);
+    unsigned long long host[2] = {0, 0};
+    FmdDevBuf bad;
+    FMD_TRY(bad.alloc(16));
+    FMD_HIP_TRY(hipMemset(bad.p, 0, 16));
+    k_pair_check<<<h->n_cu * 16, 256>>>(fmd_view(h), bad.as<unsigned long long>());
     FMD_HIP_TRY(hipDeviceSynchronize());
-    FMD_HIP_TRY(hipMemcpy(host, bad, 16, hipMemcpyDeviceToHost));
-    hipFree(bad);
+    FMD_HIP_TRY(hipMemcpy(host, bad.p, 16, hipMemcpyDeviceToHost));
     *n_bad = host[0];
     if (first_bad) *first_bad = host[1];
     return FMD_OK;

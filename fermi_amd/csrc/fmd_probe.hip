@@ -42,17 +42,17 @@ extern "C" int fmd_probe_gather(int device, uint64_t ws_bytes, uint32_t line_byt
     FMD_HIP_TRY(hipSetDevice(device));
     hipDeviceProp_t prop;
     FMD_HIP_TRY(hipGetDeviceProperties(&prop, device));
-    uint4 *ws = nullptr; uint32_t *sink = nullptr;
-    FMD_HIP_TRY(hipMalloc((void **)&ws, ws_bytes));
-    FMD_HIP_TRY(hipMalloc((void **)&sink, 64));
+    FmdDevBuf ws_b, sink_b;
+    FMD_TRY(ws_b.alloc(ws_bytes)); FMD_TRY(sink_b.alloc(64));
+    uint4 *ws = ws_b.as<uint4>(); uint32_t *sink = sink_b.as<uint32_t>();
     FMD_HIP_TRY(hipMemset(ws, 1, ws_bytes));
     const uint64_t n_lines = ws_bytes / line_bytes;
     const int lanes = (int)line_bytes / 16, lines_per_iter = 16 * (64 / lanes);
     const int grid = prop.multiProcessorCount * 10;
     uint64_t ipw = n_access / ((uint64_t)grid * lines_per_iter);
     if (ipw == 0) ipw = 1;
-    hipEvent_t e0, e1;
-    FMD_HIP_TRY(hipEventCreate(&e0)); FMD_HIP_TRY(hipEventCreate(&e1));
+    FmdEvent e0, e1;   // with timing
+    FMD_TRY(e0.make(hipEventDefault)); FMD_TRY(e1.make(hipEventDefault));
     float best = 1e30f;
     for (int i = 0; i < iters + 1; ++i) {
         FMD_HIP_TRY(hipEventRecord(e0, 0));
@@ -67,7 +67,5 @@ extern "C" int fmd_probe_gather(int device, uint64_t ws_bytes, uint32_t line_byt
     }
     // report time normalised to exactly n_access lines
     *ms = best * (float)((double)n_access / (double)(ipw * (uint64_t)grid * lines_per_iter));
-    hipEventDestroy(e0); hipEventDestroy(e1);
-    hipFree(ws); hipFree(sink);
     return FMD_OK;
 }

@@ -390,15 +390,13 @@ extern "C" int fmd_smem_win_dev(fmd_dev_t *h, void *stream_, size_t n, const uin
     return FMD_OK;
 }
 
-struct SBuf { void *p = nullptr; int alloc(size_t b) { return hipMalloc(&p, b ? b : 16) == hipSuccess ? FMD_OK : FMD_E_NOMEM; } ~SBuf() { if (p) hipFree(p); } };
-
 extern "C" int fmd_smem_batch(fmd_dev_t *h, size_t n, const uint8_t *seqs, const uint64_t *off, int self_match, uint32_t max_len,
                               uint32_t max_mem, fmd_intv_t *mem, uint32_t *n_mem)
 {
     if (!h || (n && (!seqs || !off || !mem || !n_mem))) return FMD_E_ARG;
     if (n == 0) return FMD_OK;
     FMD_HIP_TRY(hipSetDevice(h->device));
-    SBuf ds, doff, dm, dn, dw;
+    FmdDevBuf ds, doff, dm, dn, dw;
     const size_t wb = fmd_smem_work_bytes(n, max_len);
     if (ds.alloc(off[n] + 8) || doff.alloc((n + 1) * 8) || dm.alloc(n * (size_t)max_mem * sizeof(fmd_intv_t)) || dn.alloc(n * 4) || dw.alloc(wb))
         return FMD_E_NOMEM;
@@ -418,7 +416,7 @@ extern "C" int fmd_smem_win_batch(fmd_dev_t *h, size_t n, const uint8_t *seqs, u
     if (!h || (n && (!seqs || !wins || !mem || !n_mem))) return FMD_E_ARG;
     if (n == 0) return FMD_OK;
     FMD_HIP_TRY(hipSetDevice(h->device));
-    SBuf ds, dwin, dm, dn, dw;
+    FmdDevBuf ds, dwin, dm, dn, dw;
     const size_t wb = fmd_smem_work_bytes(n, max_len);
     if (ds.alloc(seq_bytes + 8) || dwin.alloc(n * sizeof(fmd_smem_win_t)) || dm.alloc(n * (size_t)max_mem * sizeof(fmd_intv_t)) || dn.alloc(n * 4) || dw.alloc(wb))
         return FMD_E_NOMEM;

@@ -199,6 +199,39 @@ def test_api_sub_equals_the_build_of_the_selected_reads(gpu):
         d.close()
 
 
+@pytest.mark.parametrize("rows", [4096, 4098])
+def test_sub_of_a_parent_at_a_superblock_border(gpu, rows):
+    """a parent index of exactly one 4096-row superblock of the row bit array, and of one with two rows in the next (an index of reads
+    has 2 * sum(len + 1) rows, never 4097: 4098 takes the same 65 bit words in two superblocks); the first read only, the last read
+    only and all but one: DevIndex.sub is the BWT `build` makes of the selected reads alone"""
+    from fermi_amd import synth
+    gen = synth.genome(synth.DEFAULT_SEED + 6, 20000, 100, 10)
+    reads, left = [], rows // 2
+    for r in synth.ragged_reads(synth.DEFAULT_SEED + 90 + rows % 7, 400, gen, min_len=5, max_len=60, err=0.02):
+        if left == 0:
+            break
+        r = r[: min(len(r), left - 1)].copy()
+        if left - (len(r) + 1) == 1:                                              # one row cannot hold a read: leave room for two
+            r = r[:-1]
+        r[3:: 11] = 5                                                             # Ns
+        reads.append(r)
+        left -= len(r) + 1
+    d = gpu.DevIndex.from_bwt(gpu.build_bwt(reads))
+    assert left == 0 and d.n == rows and int(d.mcnt[1]) == 2 * len(reads)
+    for name, keep in (("first", [0]), ("last", [len(reads) - 1]), ("all but one", [i for i in range(len(reads)) if i != len(reads) // 2])):
+        pick = np.zeros(len(reads), bool)
+        pick[keep] = True
+        on = np.zeros((2 * len(reads) + 63) // 64 * 64, np.uint8)
+        on[: 2 * len(reads)] = np.repeat(pick, 2)                                # bit 2r, 2r + 1 <-> read r
+        bits = np.packbits(on, bitorder="little").view(np.uint64)
+        want = gpu.build_bwt([reads[i] for i in keep])
+        s = d.sub(bits)
+        assert s.n == len(want) and np.array_equal(_bwt_of(gpu, s), want), name
+        assert _rank_ok(gpu, s), name
+        s.close()
+    d.close()
+
+
 def test_contrast_overflow_is_reported_and_the_host_form_runs_again(gpu, monkeypatch):
     """fmd_contrast_dev with lists of 1024 entries: the overflow flag, no write outside the work area or the bit arrays, every bit it did
     set a right one; the host form started at that capacity, and in four parts, still returns the reference's bits"""

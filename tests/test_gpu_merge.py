@@ -138,6 +138,45 @@ def test_api_merge_of_parts_equals_the_build_of_the_whole(gpu):
             d.close()
 
 
+def _reads_with_rows(rows):
+    """ragged reads with Ns whose index has exactly `rows` rows: 2 * sum(len + 1), so an even number"""
+    from fermi_amd import synth
+    seed = synth.DEFAULT_SEED + 200 + rows % 97
+    assert rows % 2 == 0
+    gen = synth.genome(synth.DEFAULT_SEED + 5, 20000, 100, 10)
+    out, left = [], rows // 2
+    for r in synth.ragged_reads(seed, 400, gen, min_len=5, max_len=60, err=0.02):
+        if left == 0:
+            break
+        r = r[: min(len(r), left - 1)].copy()
+        if left - (len(r) + 1) == 1:                                              # one row cannot hold a read: leave room for two
+            r = r[:-1]
+        r[3:: 11] = 5                                                             # Ns
+        out.append(r)
+        left -= len(r) + 1
+    assert left == 0
+    return out
+
+
+@pytest.mark.parametrize("rows", [4094, 4096, 4098, 2 * 4096 + 2])
+def test_merge_at_a_superblock_border_equals_the_build_of_the_whole(gpu, rows):
+    """two parts whose merged row count sits at the border of the 4096-row superblocks of the bit array's prefix counts (one superblock
+    not full, exactly full, one and two full ones with two rows in the next): DevIndex.merge is the one-shot build of all reads, every
+    rank consistent.  An index of reads holds both strands, 2 * sum(len + 1) rows -- never an odd number -- so the sizes are the even
+    ones on either side of the border: 4094 / 4095 rows take 64 bit words in one superblock, 4097 / 4098 take 65 in two, 8193 / 8194 take
+    129 in three, and the ranking sees a row count only through these two numbers."""
+    reads = _reads_with_rows(rows)
+    cut = len(reads) // 3
+    a, b = (gpu.DevIndex.from_bwt(gpu.build_bwt(part)) for part in (reads[:cut], reads[cut:]))
+    assert a.n + b.n == rows and a.n > 0 and b.n > 0
+    whole = gpu.build_bwt(reads)
+    m = a.merge(b)
+    assert m.n == rows == len(whole) and np.array_equal(_bwt_of(gpu, m), whole)
+    assert _rank_ok(gpu, m)
+    for d in (a, b, m):
+        d.close()
+
+
 def test_merge_arguments(gpu):
     L = gpu.lib()
     a = gpu.DevIndex.open_bare(os.path.join(GOLD, "tiny.fmd"))
