@@ -42,6 +42,7 @@ ABI_SYMBOLS = [
     "fmd_contrast_work_bytes", "fmd_contrast_dev", "fmd_contrast", "fmd_sub_work_bytes", "fmd_sub_mark_dev", "fmd_sub_select_dev", "fmd_dev_sub",
     "fmd_fltuniq_table_bytes", "fmd_fltuniq_count_dev", "fmd_fltuniq_test_dev", "fmd_fltuniq", "fmd_fltuniq_table",
     "fmd_fltuniq_open", "fmd_fltuniq_slot", "fmd_fltuniq_count", "fmd_fltuniq_test", "fmd_fltuniq_sync", "fmd_fltuniq_export", "fmd_fltuniq_close",
+    "fmd_fltuniq_batch_limits",
 ]
 
 
@@ -101,6 +102,7 @@ def _configure(L):
     L.fmd_fltuniq_sync.argtypes = [vp, vp]
     L.fmd_fltuniq_export.argtypes = [vp, C.c_uint64, C.c_uint64, u64p]
     L.fmd_fltuniq_close.restype = None; L.fmd_fltuniq_close.argtypes = [vp]
+    L.fmd_fltuniq_batch_limits.restype = None; L.fmd_fltuniq_batch_limits.argtypes = [u64p, u64p]
     L.fmd_dev_close.restype = None; L.fmd_dev_close.argtypes = [vp]
     L.fmd_dev_trim.restype = C.c_uint64; L.fmd_dev_trim.argtypes = [vp]
     L.fmd_dev_info.argtypes = [vp, C.POINTER(Info)]

@@ -263,9 +263,26 @@ extern "C" int fmd_fltuniq_export(fmd_fltuniq_t *f, uint64_t first_word, uint64_
     return FMD_OK;
 }
 
-// host form: both passes over reads in host memory, in batches of FU_BATCH_BYTES / FU_BATCH_READS
-#define FU_BATCH_BYTES (64ull << 20)
-#define FU_BATCH_READS (1ull << 20)
+// The batch limits of the host form and of the command: 64 MiB of bases / 2^20 reads.  A test aid behind FMD_FLTUNIQ_TEST_HOOKS=1:
+// FMD_FLTUNIQ_TEST_BATCH_BYTES / FMD_FLTUNIQ_TEST_BATCH_READS (each >= 1) replace them, so that a small input runs in many batches.
+// Where the batches are cut changes no table word, no verdict and no output byte (the header of this file); without the gate the two
+// variables are not read (as FMD_MERGE_TEST_HOOKS, fmd_merge.hip).  The environment is read on every call.
+extern "C" void fmd_fltuniq_batch_limits(uint64_t *max_bytes, uint64_t *max_reads)
+{
+    uint64_t lim[2] = {64ull << 20, 1ull << 20};
+    const char *on = getenv("FMD_FLTUNIQ_TEST_HOOKS");
+    if (on && atoi(on) == 1) {
+        const char *e[2] = {getenv("FMD_FLTUNIQ_TEST_BATCH_BYTES"), getenv("FMD_FLTUNIQ_TEST_BATCH_READS")};
+        for (int i = 0; i < 2; ++i) {
+            const long long v = e[i] ? atoll(e[i]) : 0;
+            if (v >= 1) lim[i] = (uint64_t)v;
+        }
+    }
+    if (max_bytes) *max_bytes = lim[0];
+    if (max_reads) *max_reads = lim[1];
+}
+
+// host form: both passes over reads in host memory, in batches of fmd_fltuniq_batch_limits()
 static int fu_run(fmd_fltuniq_run *f, const uint8_t *seqs, const uint64_t *off, uint64_t n_reads, uint8_t *pass)
 {
     for (uint64_t i = 0; i < n_reads;) {
@@ -290,7 +307,10 @@ static int fu_host(int device, int k, const uint8_t *seqs, const uint64_t *off, 
         if (off[i + 1] < off[i] || off[i + 1] - off[i] > 0xfffffff0ull) return FMD_E_ARG;
         if (off[i + 1] - off[i] > longest) longest = off[i + 1] - off[i];
     }
-    uint64_t mb = total < FU_BATCH_BYTES ? total : FU_BATCH_BYTES, mr = n_reads < FU_BATCH_READS ? n_reads : FU_BATCH_READS;
+    uint64_t mb, mr;
+    fmd_fltuniq_batch_limits(&mb, &mr);
+    if (mb > total) mb = total;
+    if (mr > n_reads) mr = n_reads;
     if (mb < longest) mb = longest;
     if (mr < 1) mr = 1;
     fmd_fltuniq_run *f = nullptr;

@@ -1,7 +1,7 @@
 /* readprep_cmd.c -- the read-preparation commands of fermi's driver script: `fermi fltuniq` (seq.c:122-210), `trimseq` (seq.c:289-373),
  * `pe2cofq` (seq.c:257-287), `splitfa` (seq.c:79-120) and `cnt2qual` (cmd.c:13-45), same argv, messages and output bytes.
- * fltuniq: the k-mer table lives on the GPU (fmd_fltuniq_*: include/fmd_hip.h); the file is read twice in batches of FU_BATCH_BYTES
- * bases -- pass 1 counts, pass 2 tests -- and a batch is parsed while the one before it is copied and worked on.  What the host keeps
+ * fltuniq: the k-mer table lives on the GPU (fmd_fltuniq_*: include/fmd_hip.h); the file is read twice in batches of at most
+ * fmd_fltuniq_batch_limits() bases and reads -- pass 1 counts, pass 2 tests -- and a batch is parsed while the one before it is copied and worked on.  What the host keeps
  * is two batches of bases and, in pass 2, the text of their records until their verdicts are back; the pairing machine of
  * seq.c:185-204 then runs over (name, verdict) in file order exactly as the reference runs it over the records.
  * Bytes >= 128 in a sequence: the reference indexes seq_nt6_table out of range with them (undefined); here they are non-bases.
@@ -15,9 +15,6 @@
 #include <unistd.h>
 #include <zlib.h>
 #include "fmd_host.h"
-
-#define FU_BATCH_BYTES (64ull << 20)
-#define FU_BATCH_READS (1ull << 20)
 
 static double now_s(void) { struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return (double)t.tv_sec + 1e-9 * (double)t.tv_nsec; }
 
@@ -79,7 +76,8 @@ static void fu_emit(fu_emit_t *e, const fu_text_t *b)
     }
 }
 
-static int fu_pass(const char *fn, fmd_fltuniq_t *f, int testing, fu_emit_t *e, uint64_t *n_rec, uint64_t *n_bases)
+static int fu_pass(const char *fn, fmd_fltuniq_t *f, uint64_t max_bytes, uint64_t max_reads, int testing, fu_emit_t *e, uint64_t *n_rec, uint64_t *n_bases,
+                   uint64_t *n_batches)
 {
     fmdh_seqio_t *io = fmdh_seq_open(fn);
     fu_text_t text[2];
@@ -88,18 +86,18 @@ static int fu_pass(const char *fn, fmd_fltuniq_t *f, int testing, fu_emit_t *e, 
     int len, rc = 0, cur = 1;
     memset(text, 0, sizeof(text));
     if (!io) return 1;
-    if (testing) { text[0].pass = (uint8_t *)malloc(FU_BATCH_READS); text[1].pass = (uint8_t *)malloc(FU_BATCH_READS); }
+    if (testing) { text[0].pass = (uint8_t *)malloc(max_reads); text[1].pass = (uint8_t *)malloc(max_reads); }
     for (;;) {
         len = fmdh_seq_read(io);
-        if (len < 0 || hs == 0 || n == FU_BATCH_READS || fill + (uint64_t)len > FU_BATCH_BYTES) {   /* the batch is complete (or there is none yet) */
+        if (len < 0 || hs == 0 || n == max_reads || fill + (uint64_t)len > max_bytes) {   /* the batch is complete (or there is none yet) */
             if (hs && n) {
                 ho[n] = fill;
                 rc = testing ? fmd_fltuniq_test(f, n, text[cur].pass) : fmd_fltuniq_count(f, n);
                 if (rc) break;
-                text[cur].n = n;
+                text[cur].n = n; ++*n_batches;
             }
             if (len < 0) break;
-            if ((uint64_t)len > FU_BATCH_BYTES) { fprintf(stderr, "[E::main_fltuniq] a sequence of %d bases: longer than a batch\n", len); rc = 1; break; }
+            if ((uint64_t)len > max_bytes) { fprintf(stderr, "[E::main_fltuniq] a sequence of %d bases: longer than a batch\n", len); rc = 1; break; }
             cur ^= 1;
             if ((rc = fmd_fltuniq_slot(f, &hs, &ho)) != 0) break;      /* the slot's earlier batch is done: its verdicts are in text[cur].pass */
             if (testing) { fu_emit(e, &text[cur]); text[cur].n = 0; text[cur].txt.l = 0; }
@@ -140,7 +138,7 @@ int fmdh_main_fltuniq(int argc, char *argv[])
     const int timing = getenv("FMD_TIMING") != 0;
     fmd_fltuniq_t *f = 0;
     fu_emit_t e;
-    uint64_t n_rec[2] = {0, 0}, n_bases[2] = {0, 0};
+    uint64_t n_rec[2] = {0, 0}, n_bases[2] = {0, 0}, n_batches[2] = {0, 0}, max_bytes, max_reads;
     double t0 = now_s(), t1, t2, ms[2] = {0, 0};
     while ((c = getopt(argc, argv, "k:g:")) >= 0) {
         switch (c) {
@@ -179,7 +177,8 @@ int fmdh_main_fltuniq(int argc, char *argv[])
     }
     if (fmd_device_count() <= 0) { fprintf(stderr, "[E::main] %s\n", fmd_strerror(FMD_E_NODEV)); return 1; }
     if (device < 0 || device >= fmd_device_count()) { fprintf(stderr, "[E::main_fltuniq] GPU %d: this node has %d\n", device, fmd_device_count()); return 1; }
-    rc = fmd_fltuniq_open(device, k, FU_BATCH_BYTES, FU_BATCH_READS, &f);
+    fmd_fltuniq_batch_limits(&max_bytes, &max_reads);
+    rc = fmd_fltuniq_open(device, k, max_bytes, max_reads, &f);
     if (rc) {
         fprintf(stderr, "[E::main_fltuniq] a table of %.1f GB for k = %d: %s\n", (double)fmd_fltuniq_table_bytes(k) / 1e9, k, fmd_strerror(rc));
         return 1;
@@ -187,11 +186,11 @@ int fmdh_main_fltuniq(int argc, char *argv[])
     memset(&e, 0, sizeof(e));
     e.fp = stdout;
     fprintf(stderr, "[M::main_fltuniq] building the hash table...\n");
-    rc = fu_pass(argv[optind], f, 0, &e, &n_rec[0], &n_bases[0]);
+    rc = fu_pass(argv[optind], f, max_bytes, max_reads, 0, &e, &n_rec[0], &n_bases[0], &n_batches[0]);
     t1 = now_s();
     if (rc == 0) {
         fprintf(stderr, "[M::main_fltuniq] filtering the reads...\n");
-        rc = fu_pass(argv[optind], f, 1, &e, &n_rec[1], &n_bases[1]);
+        rc = fu_pass(argv[optind], f, max_bytes, max_reads, 1, &e, &n_rec[1], &n_bases[1], &n_batches[1]);
     }
     t2 = now_s();
     if (rc == 0) fmd_fltuniq_sync(f, ms);
@@ -201,6 +200,7 @@ int fmdh_main_fltuniq(int argc, char *argv[])
         fprintf(stderr, "[M::main_fltuniq] k = %d, table %.3f GB; %llu records, %llu bases; kept %llu records\n", k, (double)fmd_fltuniq_table_bytes(k) / 1e9,
                 (unsigned long long)n_rec[0], (unsigned long long)n_bases[0], (unsigned long long)e.n_out);
         fprintf(stderr, "[M::main_fltuniq] pass 1: %.3f s (count kernels %.3f s); pass 2: %.3f s (test kernels %.3f s)\n", t1 - t0, ms[0] * 1e-3, t2 - t1, ms[1] * 1e-3);
+        fprintf(stderr, "[M::main_fltuniq] batches: %llu in pass 1, %llu in pass 2\n", (unsigned long long)n_batches[0], (unsigned long long)n_batches[1]);
     }
     return rc;
 }

@@ -586,7 +586,10 @@ int fmd_dev_sub(fmd_dev_t *h, const uint64_t *sub, int is_comp, unsigned flags, 
  *   two staging slots of max_bytes bases and max_reads reads in pinned host memory; slot hands out the next one (off[0] must be 0;
  *   waits until its previous work is done); count / test upload the slot last handed out and enqueue its kernel -- the caller fills the
  *   next slot meanwhile; the first test waits for every count.  pass[] of a test is filled when its slot comes round again or at
- *   sync; sync also reports the milliseconds the count and the test kernels took so far.  export copies table words out. */
+ *   sync; sync also reports the milliseconds the count and the test kernels took so far.  export copies table words out.
+ * fmd_fltuniq_batch_limits: the most bases and reads the host forms and the command put into one batch (64 MiB, 2^20).  A test aid that
+ *   changes no result: with FMD_FLTUNIQ_TEST_HOOKS=1 in the environment, FMD_FLTUNIQ_TEST_BATCH_BYTES / FMD_FLTUNIQ_TEST_BATCH_READS
+ *   (each >= 1) replace them, so that a small input runs in many batches; without the gate both are ignored.  Read on every call. */
 typedef struct fmd_fltuniq_run fmd_fltuniq_t;
 size_t fmd_fltuniq_table_bytes(int k);
 int fmd_fltuniq_count_dev(int device, void *stream, int k, const uint8_t *d_seqs, const uint64_t *d_off, uint64_t n_reads, uint64_t *d_table);
@@ -601,6 +604,7 @@ int fmd_fltuniq_test(fmd_fltuniq_t *f, uint64_t n_reads, uint8_t *pass);
 int fmd_fltuniq_sync(fmd_fltuniq_t *f, double kernel_ms[2]);
 int fmd_fltuniq_export(fmd_fltuniq_t *f, uint64_t first_word, uint64_t n_words, uint64_t *table);
 void fmd_fltuniq_close(fmd_fltuniq_t *f);
+void fmd_fltuniq_batch_limits(uint64_t *max_bytes, uint64_t *max_reads);
 
 /* device memory for C hosts (the reference has no device; these are what a cgo/C caller uses to
  * stage batches): plain hipMalloc / hipMemcpyAsync behind the ABI. */
