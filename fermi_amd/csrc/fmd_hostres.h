@@ -110,6 +110,43 @@ struct FmdEvent {
     operator hipEvent_t() const { return e; }
 };
 
+// ---- a second stream with its events, kept in a long-lived handle (fmd_dev): zero bytes are its empty state, it is made on the first
+// acquire and goes with destroy().  One caller at a time: acquire is false while another call holds it (that call takes its serial
+// path) and when the stream or one of its n_events (<= FMD_OVLP_MAX_PARTS + 1) events cannot be made -- what was made is freed, the
+// runtime's last error cleared, and the next acquire tries again.
+struct FmdSideStream {
+    hipStream_t stream;   // non-blocking: must not synchronise with the null stream
+    hipEvent_t ev[FMD_OVLP_MAX_PARTS + 1];
+    int ready, busy;      // (busy: atomic)
+    bool acquire(int n_events)
+    {
+        int expect = 0;
+        if (!__atomic_compare_exchange_n(&busy, &expect, 1, false, __ATOMIC_ACQUIRE, __ATOMIC_RELAXED)) return false;
+        if (!ready) {
+            bool ok = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) == hipSuccess;
+            int made = 0;
+            for (; ok && made < n_events; ++made) ok = hipEventCreateWithFlags(&ev[made], hipEventDisableTiming) == hipSuccess;
+            if (!ok) {
+                for (int i = 0; i < made - 1; ++i) hipEventDestroy(ev[i]);
+                if (stream) { hipStreamDestroy(stream); stream = nullptr; }   // or every retry would leak a stream
+                (void)hipGetLastError();
+                release();
+                return false;
+            }
+            ready = n_events;
+        }
+        return true;
+    }
+    void release() { __atomic_store_n(&busy, 0, __ATOMIC_RELEASE); }
+    void destroy()
+    {
+        if (!ready) return;
+        hipStreamDestroy(stream);
+        for (int i = 0; i < ready; ++i) hipEventDestroy(ev[i]);
+        stream = nullptr; ready = 0;
+    }
+};
+
 // ---- a buffer of the handle's scratch cache (fmd_scratch_acquire) for a scope: the same sizes come back call after call
 struct FmdScratch {
     fmd_dev *h = nullptr;

@@ -7,6 +7,17 @@
 #include "fmd_wave.h"
 
 #define FMD_OVLP_MAX_PARTS 8
+
+void fmd_set_hip_error(hipError_t e, const char *what);
+// A device buffer of at least `bytes` from the handle's cache (hipMalloc when none fits); give it back with
+// fmd_scratch_release.  Thread-safe; nullptr when the device is out of memory.
+void *fmd_scratch_acquire(fmd_dev *h, size_t bytes);
+void fmd_scratch_release(fmd_dev *h, void *p);
+
+// the owning host-side resources (device / pinned buffers, streams, events, scratch leases): a .hip file uses these and defines none
+#include <stdlib.h>
+#include "fmd_hostres.h"
+
 struct fmd_dev {
     int device;
     int n_cu;                 // compute units on this GPU
@@ -24,24 +35,16 @@ struct fmd_dev {
     uint32_t *queues;         // device ring of work-queue heads for the persistent kernels
     uint32_t queue_next;      // host-side ring cursor (atomic)
     unsigned long long *stat; // device: FMD_STAT_SLOTS x FMD_STAT_STRIDE line counters (written by the instrumented build only)
-    // second stream + events of the pipelined overlap batch (fmd_ovlp_dev), created on first use;
-    // aux_busy (atomic) lets one call at a time use them, a concurrent call takes the serial path
     // device buffers kept between host-form calls (fmd_scratch_*): hipFree + hipMalloc of tens of GB per call cost
     // 1-2 s (`unitig` on 10 M reads: 1.05 s of a 1.2 s table pass); released by fmd_dev_close
     struct { void *p; size_t bytes; int busy; } scratch[24];
     int scratch_lock;
-    hipStream_t aux_stream;
-    hipEvent_t aux_ev[FMD_OVLP_MAX_PARTS + 1];
-    int aux_ready, aux_busy;
-    // side stream of fm6_get_nei's lane-per-strand kernel (k_ovl_nei on the strands k_ovl_classify sets aside runs beside the group
-    // kernels: a few long dependent chains, nothing to gain from having the GPU to itself); same ownership rule as aux_*
-    hipStream_t slow_stream;
-    hipEvent_t slow_ev[2];
-    int slow_ready, slow_busy;
+    // second stream + events of the pipelined overlap batch (fmd_ovlp_dev), and the side stream of fm6_get_nei's lane-per-strand kernel
+    // (k_ovl_nei on the strands k_ovl_classify sets aside runs beside the group kernels: a few long dependent chains, nothing to gain
+    // from having the GPU to itself).  Made on first use; one call at a time uses each, a concurrent call takes the serial path.
+    FmdSideStream aux, slow;
 };
 #define FMD_N_QUEUES 256
-
-void fmd_set_hip_error(hipError_t e, const char *what);
 
 #define FMD_HIP_TRY(expr)                                       \
     do {                                                        \
@@ -67,11 +70,6 @@ static inline FmdIndexView fmd_view(const fmd_dev *h)
     return v;
 }
 
-// A device buffer of at least `bytes` from the handle's cache (hipMalloc when none fits); give it back with
-// fmd_scratch_release.  Thread-safe; nullptr when the device is out of memory.
-void *fmd_scratch_acquire(fmd_dev *h, size_t bytes);
-void fmd_scratch_release(fmd_dev *h, void *p);
-
 // the in-place index builder's hooks into fmd_index.hip
 int fmd_index_alloc(int device, uint64_t n_sym, fmd_dev **out);
 int fmd_index_put_slice(fmd_dev *h, hipStream_t st, const uint8_t *d_slice, uint64_t first, uint64_t m);
@@ -92,7 +90,6 @@ int fmd_grid_for_lds(const fmd_dev *h, size_t n_items, size_t lds_bytes);
 // their work statically (round-robin or by ranges): a workgroup beyond the resident set would start when
 // the others are done and then work through a full share alone.  The runtime's occupancy query, bounded by
 // the LDS granule (1280 bytes on gfx950: 160 KiB / 128) and by `cap`.
-#include <stdlib.h>
 template <typename K>
 static inline int fmd_resident_per_cu(K kernel, size_t lds_bytes, int cap, const char *name)
 {
@@ -104,6 +101,3 @@ static inline int fmd_resident_per_cu(K kernel, size_t lds_bytes, int cap, const
     if (getenv("FMD_DEBUG_OCC")) fprintf(stderr, "[occupancy] %s: %d workgroups per CU\n", name, nb);
     return nb;
 }
-
-// the owning host-side resources (device / pinned buffers, streams, events, scratch leases): a .hip file uses these and defines none
-#include "fmd_hostres.h"

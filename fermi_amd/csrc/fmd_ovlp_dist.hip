@@ -18,12 +18,8 @@
 #include <time.h>
 #include <algorithm>
 #include <vector>
-#include "fmd_kernel_common.h"
+#include "fmd_ovlp_internal.h"
 #include "fmd_internal.h"
-
-// (fmd_ovlp_sort.hip)
-size_t fmd_park_sort_temp_bytes(size_t n);
-int fmd_park_sort(hipStream_t st, size_t n, const FmdWalkPark *park, uint32_t *keys_a, uint32_t *keys_b, uint32_t *vals_a, uint32_t *vals_b, void *tmp, size_t tmp_bytes);
 
 static inline double now_s() { struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return (double)t.tv_sec + 1e-9 * (double)t.tv_nsec; }
 static inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -191,7 +187,7 @@ __global__ void k_ks_gather(size_t n, const uint32_t *__restrict__ order, const 
         uint4 v = ((const uint4 *)(park + row))[l4];
         const uint4 a = l4 == 0 ? v : ((const uint4 *)(park + row))[0];
         const bool ended = a.x == 0xffffffffu && a.y == 0xffffffffu;
-        if (l4 == 3) { const uint64_t id = ids[row]; v = make_uint4((uint32_t)id, (uint32_t)(id >> 32), v.z, v.w); }   // (pad.z / pad.w: the bases and the depth of a strand parked beyond 32 bases, fmd_ovlp.hip)
+        if (l4 == 3) { const uint64_t id = ids[row]; v = make_uint4((uint32_t)id, (uint32_t)(id >> 32), v.z, v.w); }   // (pad.z / pad.w: the bases and the depth of a strand parked beyond 32 bases, fmd_ovlp_walk.hip)
         if (ended && l4 == 0) { const uint64_t rk = rec[row].rank; v.z = (uint32_t)rk; v.w = (uint32_t)(rk >> 32); }
         if (ended && l4 == 1) { v.x = (uint32_t)rec[row].len; v.y = 0; }
         ((uint4 *)(send + t))[l4] = v;
@@ -204,7 +200,7 @@ __global__ void k_ks_unpack(size_t m, const FmdWalkPark *__restrict__ park, uint
     for (size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x; j < m; j += step) {
         const FmdWalkPark *p = park + j;
         ids[j] = (uint64_t)p->pad.y << 32 | p->pad.x;
-        if (p->k == ~0ull) {   // what k_ovl_walk<WALK_HEAD> wrote for it on the rank that took it in (fmd_ovlp.hip)
+        if (p->k == ~0ull) {   // what k_ovl_walk<WALK_HEAD> wrote for it on the rank that took it in (fmd_ovlp_walk.hip)
             fmd_ovlp_rec_t o;
             o.rank = p->x0; o.k[0] = o.k[1] = o.k[2] = 0; o.len = (int32_t)p->x1; o.status = FMD_OVLP_SHORT; o.n_ovlp = 0; o.rbeg = -1;
             o.ext_len = 0; o.n_nei = 0; o.flags = 0; o.reserved = 2; o.lfork = 0;

@@ -1,7 +1,7 @@
 // fmd_ovlp_grp.hip -- fm6_get_nei (unitig.c:93-179) with ONE LANE PER CANDIDATE INTERVAL.
 //
 // fm6_get_nei advances a list of candidate intervals (one per read that might overlap the strand)
-// by one base per round.  The lane-per-strand kernel (k_ovl_nei, fmd_ovlp.hip) keeps those lists
+// by one base per round.  The lane-per-strand kernel (k_ovl_nei, fmd_ovlp_nei.hip) keeps those lists
 // in HBM and pays for it: profiles/r1_ovlp showed 154 GB of traffic per 4 M-strand launch against
 // 53 GB of rank blocks.  Here a strand owns a group of G lanes (G = 8, 12, 16, 21 or 32: the smallest
 // that holds its candidates, fmd_grp_size) and its candidate list IS the group's registers:
@@ -18,7 +18,7 @@
 // Strands that do not fit the fast shape -- more than 32 candidates, an interval wider than 63,
 // more neighbours than max_nei, or the fake-fork fix-up of unitig.c:158-176 -- are handed
 // to k_ovl_nei through the `slow` work list; nothing is approximated.
-#include "fmd_kernel_common.h"
+#include "fmd_ovlp_internal.h"
 
 // LDS per wave: one block slot per lane for the k side of the forward extension (slot 0) and, in the first round of
 // a candidate that came without D / r0, of its x[0] range (slot 1); the l sides, needed only when a range leaves its

@@ -14,7 +14,7 @@
 // words in registers beside the round's state instead of 128-168); the class of 32 keeps the group form.  Same results by
 // construction: the arithmetic of a round is k_ovl_nei_fast's, statement by statement; a strand that leaves the simple regime is handed to
 // k_ovl_nei_grp in the same FMD_LIST_RESUME form.  FMD_NEI_LANE=0 runs the group form instead (the A/B switch, and the tests' second opinion).
-#include "fmd_kernel_common.h"
+#include "fmd_ovlp_internal.h"
 
 #define LANE_CHUNK FMD_LANE_CHUNK          // list slots a wave reserves at a time for the strands it hands on (64: every lane may hand on in one step)
 

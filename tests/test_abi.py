@@ -57,6 +57,28 @@ def test_product_does_not_reference_oracle():
     assert not bad, bad
 
 
+def test_environment_table_lists_what_the_code_reads():
+    """INTEGRATION.md's table of environment switches names exactly the FMD_* variables the library, the host code and the public header
+    pass to getenv: a switch nobody documents, or a row for a switch nothing reads, fails here.  (FMD_BENCH_* belongs to bench.py.)"""
+    read = set()
+    for base in ("fermi_amd/csrc", "fermi_amd/host", "include"):
+        for dp, _, fns in os.walk(os.path.join(ROOT, base)):
+            for fn in fns:
+                if fn.endswith((".c", ".h", ".hip", ".inc", ".cpp")):
+                    txt = open(os.path.join(dp, fn), errors="ignore").read()
+                    assert not re.search(r"getenv\(\s*[^\s\")]", txt), (fn, "getenv of a name that is not a literal")
+                    read.update(re.findall(r'getenv\(\s*"(FMD_[A-Z0-9_]+)"', txt))
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    sect = doc[doc.index("## Environment switches"):]
+    sect = sect[:sect.index("\n## ", 1)] if "\n## " in sect[1:] else sect
+    listed = set()
+    for row in re.findall(r"^\|([^|]*(?:\\\|[^|]*)*)\|", sect, flags=re.M):
+        listed.update(re.findall(r"\bFMD_[A-Z0-9_]+", row))
+    listed = {v for v in listed if not v.startswith("FMD_BENCH_")}
+    assert len(read) > 60 and len(listed) > 60
+    assert listed == read, ("read but not in the table: %s; in the table but not read: %s" % (sorted(read - listed), sorted(listed - read)))
+
+
 def test_no_kernel_spills_to_scratch():
     """Every gfx950 kernel of the built library keeps its registers: no VGPR spills, no private segment (tools/kernel_resources.py reads
     the code-object metadata of build/*.o).  A spilling k_ovl_nei_fast returned wrong neighbours for a few strands in 10^7 when it ran

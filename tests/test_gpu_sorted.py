@@ -40,6 +40,13 @@ def test_sorted_job_equals_id_order_and_oracle(gpu, oracle_lib, monkeypatch, L, 
     monkeypatch.setenv("FMD_OVLP_FAST", "0")                        # every strand through the general group kernels
     _same(want, d.overlap_sorted(ids, mm, L, 8, batch), 8)
     monkeypatch.delenv("FMD_OVLP_FAST")
+    if (L, cov, mm, err, N, batch) == (100, 60, 40, 0.003, 10000, 4096):   # several batches of reads with errors: the second pass the older way
+        monkeypatch.setenv("FMD_WALK_TAIL2", "0")                   # k_ovl_walk<WALK_TAIL>: the stash in HBM, rows by k_ovl_seq_out, lists by k_ovl_classify
+        _same(want, d.overlap_sorted(ids, mm, L, 8, batch), 8)
+        monkeypatch.delenv("FMD_WALK_TAIL2")
+        monkeypatch.setenv("FMD_WALK_CLS", "0")                     # k_ovl_walk<WALK_TAIL2> writes the rows, k_ovl_classify makes the work lists
+        _same(want, d.overlap_sorted(ids, mm, L, 8, batch), 8)
+        monkeypatch.delenv("FMD_WALK_CLS")
     o = orcbind.OrcIndex(bwt=bwt)
     sub = np.sort(np.random.default_rng(L + cov).choice(len(ids), 3000, replace=False)).astype(U64)
     wrec, wnei, _ = o.overlap_batch(sub, mm, L, 8, 4, check_left=False)
