@@ -43,6 +43,12 @@ fermi_amd/bin/fermi-amd: fermi_amd/host/main.c fermi_amd/lib/libfmdhost.so fermi
 	@mkdir -p fermi_amd/bin
 	$(CC) $(CFLAGS) -Iinclude -Ifermi_amd/host fermi_amd/host/main.c -o $@ -Lfermi_amd/lib -lfmdhost -lfmdhip -Wl,-rpath,'$$ORIGIN/../lib'
 
+# the graph module under the sanitizers, as a program of its own (host code only; nothing is loaded into python, nothing runs on a GPU)
+asan-mag: build/mag_asan
+build/mag_asan: tools/clean_main.c $(addprefix fermi_amd/host/,mag.c mag_bubble.c swscore.c clean_cmd.c seqio.c rld_writer.c) $(HOST_HDRS)
+	@mkdir -p build
+	$(CC) -O1 -g -Wall -std=gnu11 -fsanitize=address,undefined -fno-sanitize-recover=undefined -Iinclude -Ifermi_amd/host $(filter %.c,$^) -o $@ -lpthread -lm -lz
+
 oracle:
 	$(MAKE) -s -C oracle oracle
 ref:
@@ -57,4 +63,4 @@ variant:
 clean:
 	rm -rf build fermi_amd/lib/*.so
 	$(MAKE) -s -C oracle clean
-.PHONY: all host cli oracle ref clean variant
+.PHONY: all host cli oracle ref clean variant asan-mag

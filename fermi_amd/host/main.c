@@ -389,7 +389,10 @@ int main(int argc, char *argv[])
         fprintf(stderr, "         cnt2qual   occurrence counts -> qualities, no GPU needed (fermi cnt2qual)\n");
         fprintf(stderr, "         fltuniq    drop reads that hold a k-mer seen once, and their mates (fermi fltuniq)\n");
         fprintf(stderr, "         seqsort    rank -> read index map for `unitig -r` (fermi seqsort)\n");
+        fprintf(stderr, "         seqrank    the same under the name the reference's driver script uses\n");
         fprintf(stderr, "         unitig     construct unitigs (fermi unitig)\n");
+        fprintf(stderr, "         clean      clean the unitig graph: tips, weak arcs, bubbles, no GPU needed (fermi clean)\n");
+        fprintf(stderr, "         example    reads -> corrected reads or (cleaned) unitigs through the in-memory API (fermi example)\n");
         fprintf(stderr, "         correct    error correction (fermi correct)\n");
         fprintf(stderr, "         exact      find super-maximal exact matches (fermi exact)\n");
         fprintf(stderr, "         chkbwt     print / check the BWT held on the GPU (fermi chkbwt)\n");
@@ -409,6 +412,7 @@ int main(int argc, char *argv[])
     if (strcmp(argv[1], "pe2cofq") == 0) return fmdh_main_pe2cofq(argc - 1, argv + 1);
     if (strcmp(argv[1], "splitfa") == 0) return fmdh_main_splitfa(argc - 1, argv + 1);
     if (strcmp(argv[1], "cnt2qual") == 0) return fmdh_main_cnt2qual(argc - 1, argv + 1);
+    if (strcmp(argv[1], "clean") == 0) return fmdh_main_clean(argc - 1, argv + 1);
     { const int node = stay_on_one_node(argv[1]); if (timing && node >= 0) fprintf(stderr, "[M::main] the process stays on NUMA node %d\n", node); }
     if (strcmp(argv[1], "fltuniq") != 0 && fmd_device_count() <= 0) {   /* (fltuniq looks at its arguments first, as the reference does, then for the device) */
         fprintf(stderr, "[E::main] %s\n", fmd_strerror(FMD_E_NODEV));
@@ -422,7 +426,8 @@ int main(int argc, char *argv[])
     else if (strcmp(argv[1], "contrast") == 0) rc = main_contrast(argc - 1, argv + 1);
     else if (strcmp(argv[1], "sub") == 0) rc = main_sub(argc - 1, argv + 1);
     else if (strcmp(argv[1], "fltuniq") == 0) rc = fmdh_main_fltuniq(argc - 1, argv + 1);
-    else if (strcmp(argv[1], "seqsort") == 0) rc = main_seqsort(argc - 1, argv + 1);
+    else if (strcmp(argv[1], "seqsort") == 0 || strcmp(argv[1], "seqrank") == 0) rc = main_seqsort(argc - 1, argv + 1);   /* main.c:109 */
+    else if (strcmp(argv[1], "example") == 0) rc = fmdh_main_example(argc - 1, argv + 1);
     else if (strcmp(argv[1], "exact") == 0) rc = main_exact(argc - 1, argv + 1);
     else if (strcmp(argv[1], "correct") == 0) rc = main_correct(argc - 1, argv + 1);
     else if (strcmp(argv[1], "remap") == 0) rc = main_remap(argc - 1, argv + 1);

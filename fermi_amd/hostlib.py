@@ -61,6 +61,7 @@ def lib():
         L.fmdh_api_unitig.argtypes = [C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]
         L.fmdh_api_correct.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]
         L.fmdh_api_seqlen.argtypes = [C.c_int64, C.c_void_p, C.c_double]
+        L.fmdh_sw_score.argtypes = [C.c_int, C.c_char_p, C.c_int, C.c_char_p]
         _lib = L
     return _lib
 
@@ -262,6 +263,29 @@ def remap_contigs(contigs, mems, n_seq, out_path, err_path, skip=50, min_pcv=0, 
         L.fmdh_remap_finish(st, fe)
     finally:
         _libc.fclose(fp); _libc.fclose(fe)
+
+
+BIN_PATH = os.path.join(_HERE, "bin", "fermi-amd")
+
+
+def clean(in_path, out_path, args=()):
+    """`fermi-amd clean <args> in_path > out_path` (host/clean_cmd.c; no GPU): the graph cleaned as `fermi clean` cleans it."""
+    import subprocess
+    if not os.path.exists(BIN_PATH):
+        raise RuntimeError("fermi-amd is not built; run `make cli`")
+    with open(out_path, "wb") as out:
+        p = subprocess.run([BIN_PATH, "clean"] + list(args) + [in_path], stdout=out, stderr=subprocess.PIPE)
+    if p.returncode:
+        raise RuntimeError("fermi-amd clean failed: " + p.stderr.decode(errors="replace").strip())
+
+
+_NT4 = bytes.maketrans(b"ACGTacgt", bytes([0, 1, 2, 3, 0, 1, 2, 3]))
+
+
+def sw_score(a, b):
+    """fmdh_sw_score (host/swscore.c) of two sequences given as ACGT byte strings: the score of the local alignment the bubble poppers ask for."""
+    a, b = bytes(a).translate(_NT4), bytes(b).translate(_NT4)
+    return int(lib().fmdh_sw_score(len(a), a, len(b), b))
 
 
 def _read_buffer(reads):
