@@ -49,6 +49,12 @@ build/mag_asan: tools/clean_main.c $(addprefix fermi_amd/host/,mag.c mag_bubble.
 	@mkdir -p build
 	$(CC) -O1 -g -Wall -std=gnu11 -fsanitize=address,undefined -fno-sanitize-recover=undefined -Iinclude -Ifermi_amd/host $(filter %.c,$^) -o $@ -lpthread -lm -lz
 
+# the host side of `scaf` the same way: reader, statistics, alignment, link choice and joiner; the link stage restated on the host (tools/scaf_main.c)
+asan-scaf: build/scaf_asan
+build/scaf_asan: tools/scaf_main.c $(addprefix fermi_amd/host/,scaf_core.c scaf_stat.c mag.c mag_bubble.c swscore.c seqio.c rld_writer.c) $(HOST_HDRS)
+	@mkdir -p build
+	$(CC) -O1 -g -Wall -std=gnu11 -fsanitize=address,undefined -fno-sanitize-recover=undefined -Iinclude -Ifermi_amd/host $(filter %.c,$^) -o $@ -lpthread -lm -lz
+
 oracle:
 	$(MAKE) -s -C oracle oracle
 ref:
@@ -63,4 +69,4 @@ variant:
 clean:
 	rm -rf build fermi_amd/lib/*.so
 	$(MAKE) -s -C oracle clean
-.PHONY: all host cli oracle ref clean variant asan-mag
+.PHONY: all host cli oracle ref clean variant asan-mag asan-scaf

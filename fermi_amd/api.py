@@ -43,6 +43,7 @@ ABI_SYMBOLS = [
     "fmd_fltuniq_table_bytes", "fmd_fltuniq_count_dev", "fmd_fltuniq_test_dev", "fmd_fltuniq", "fmd_fltuniq_table",
     "fmd_fltuniq_open", "fmd_fltuniq_slot", "fmd_fltuniq_count", "fmd_fltuniq_test", "fmd_fltuniq_sync", "fmd_fltuniq_export", "fmd_fltuniq_close",
     "fmd_fltuniq_batch_limits",
+    "fmd_scaf_links_work_bytes", "fmd_scaf_links_dev", "fmd_scaf_links",
 ]
 
 
@@ -103,6 +104,9 @@ def _configure(L):
     L.fmd_fltuniq_export.argtypes = [vp, C.c_uint64, C.c_uint64, u64p]
     L.fmd_fltuniq_close.restype = None; L.fmd_fltuniq_close.argtypes = [vp]
     L.fmd_fltuniq_batch_limits.restype = None; L.fmd_fltuniq_batch_limits.argtypes = [u64p, u64p]
+    L.fmd_scaf_links_work_bytes.restype = sz; L.fmd_scaf_links_work_bytes.argtypes = [C.c_uint64]
+    L.fmd_scaf_links_dev.argtypes = [C.c_int, vp, C.c_uint64, u64p, u64p, vp, C.c_uint64, vp, vp, C.c_int, u64p, u64p, u64p, u64p, vp, u64p, vp, sz]
+    L.fmd_scaf_links.argtypes = [C.c_int, C.c_uint64, u64p, u64p, vp, C.c_uint64, vp, vp, C.c_int, u64p, u64p, u64p, u64p, vp, u64p]
     L.fmd_dev_close.restype = None; L.fmd_dev_close.argtypes = [vp]
     L.fmd_dev_trim.restype = C.c_uint64; L.fmd_dev_trim.argtypes = [vp]
     L.fmd_dev_info.argtypes = [vp, C.POINTER(Info)]
@@ -616,6 +620,24 @@ def fltuniq_table(seqs, k, device=0):
     tab = np.zeros(fltuniq_table_words(k), dtype=np.uint64)
     check(lib().fmd_fltuniq_table(device, int(k), _ptr(flat), _ptr(off), len(off) - 1, _ptr(tab)))
     return tab
+
+
+SCAF_NONE = NONE64
+
+
+def scaf_links(x, span, utig, length, excluded, max_dist, device=0):
+    """The link stage of `scaf` (collect_nei, scaf.c:189-254) over the UR entries of all unitigs: x = read id << 1 | strand, span = b << 32 | e,
+    utig = unitig of each entry; length / excluded per unitig.  Returns (self, mate, gkey, gval, n_nei) as include/fmd_hip.h describes them."""
+    x = np.ascontiguousarray(x, dtype=np.uint64); span = np.ascontiguousarray(span, dtype=np.uint64); utig = np.ascontiguousarray(utig, dtype=np.uint32)
+    length = np.ascontiguousarray(length, dtype=np.int32); excluded = np.ascontiguousarray(excluded, dtype=np.uint8)
+    n, nu = len(x), len(length)
+    assert len(span) == n and len(utig) == n and len(excluded) == nu
+    own, mate, gkey, gval = (np.zeros(max(n, 1), dtype=np.uint64) for _ in range(4))
+    n_nei = np.zeros(max(2 * nu, 1), dtype=np.uint32)
+    ng = C.c_uint64(0)
+    check(lib().fmd_scaf_links(device, n, _ptr(x), _ptr(span), _ptr(utig), nu, _ptr(length), _ptr(excluded), int(max_dist), _ptr(own), _ptr(mate),
+                               _ptr(gkey), _ptr(gval), _ptr(n_nei), C.byref(ng)))
+    return own[:n], mate[:n], gkey[:ng.value], gval[:ng.value], n_nei[:2 * nu]
 
 
 def probe_gather(ws_bytes, line_bytes, n_access, iters=3, device=0):

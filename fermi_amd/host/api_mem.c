@@ -80,6 +80,30 @@ int fmdh_api_unitig(int device, int min_match, int64_t l, char *seq, FILE *out)
     return rc ? 1 : 0;
 }
 
+/* fm6_api_unitig's own return value: the graph (unitig.c:413-434), for a caller that goes on with it in memory -- `scaf` cleans the local
+ * assembly of every gap (scaf.c:418-428).  The records fmdh_api_unitig writes, read back as they are: the dictionary built, nothing
+ * filtered, amended or merged.  NULL with *rc = 0: no unitig at all; NULL with *rc = 1: failure. */
+fmdh_mag_t *fmdh_api_unitig_mag(int device, int min_match, int64_t l, char *seq, int *rc)
+{
+    char *text = 0;
+    size_t n_text = 0;
+    FILE *mem = open_memstream(&text, &n_text);
+    fmdh_mag_t *g = 0;
+    *rc = 1;
+    if (!mem) return 0;
+    *rc = fmdh_api_unitig(device, min_match, l, seq, mem);
+    fclose(mem);
+    if (*rc == 0 && n_text) {
+        fmdh_magopt_t opt;
+        fmdh_mag_init_opt(&opt);
+        opt.flag = FMDH_MAG_F_READ_ORI | FMDH_MAG_F_NO_AMEND;
+        g = fmdh_mag_read_mem(text, n_text, &opt);
+        if (!g) *rc = 1;
+    }
+    free(text);
+    return g;
+}
+
 int fmdh_api_correct(int device, int kmer, int step, int64_t l, char *seq, char *qual)
 {
     const int w = kmer > 0 ? kmer : 19, min_occ = 3, suf_len = w > 15 ? w - 15 : 1;   /* correct.c:477-481 */

@@ -332,12 +332,17 @@ uint64_t fmdh_remap_table_resets(const fmdh_remap_state_t *st);  /* how often th
  * correct.c:471-474): it is a parameter here (the CLI default is 5, 0 switches the heuristic off). */
 int fmdh_api_unitig(int device, int min_match, int64_t l, char *seq, FILE *out);
 int fmdh_api_correct(int device, int kmer, int step, int64_t l, char *seq, char *qual);
+struct fmdh_mag *fmdh_api_unitig_mag(int device, int min_match, int64_t l, char *seq, int *rc);   /* the same graph as an object (NULL, *rc = 0: empty) */
 int fmdh_api_seqlen(int64_t l, const char *seq, double quantile);   /* fm6_api_seqlen, seq.c:430-446 */
 int fmdh_slim_build_dev(fmd_dev_t *dev, int min_match, fmdh_slim_t **out, uint64_t *n_seq_out);
 /* `fermi example [-ceU] [-k ecKmer] [-l utgKmer] <in.fq>` (example.c): the reference's caller of that API; -g GPU; argv[0] = the command's name */
 int fmdh_main_example(int argc, char *argv[]);
 /* ---- the unitig graph on the host: `fermi clean` and the operations behind it (mag.c, mag_bubble.c, swscore.c, clean_cmd.c; no GPU) ---- */
 #include "mag.h"
+
+/* `fermi scaf [-t INT] [-m INT] [-P] [-a FLOAT] [-p FLOAT] [-g GPU] <in.fmd> <in.remapped.mag> <avg> <std>` (cmd.c:560-587, scaf.c);
+ * argv[0] = the command's name.  Looks at its arguments first, then for the device. */
+int fmdh_main_scaf(int argc, char *argv[]);
 
 /* `fermi build -o out.fmd <in.fa>` (cmd.c:378-484); no_fr = trim palindromes (default 1) */
 int fmdh_build(const char *fa_path, const char *out_path, int device, int max_len, int no_fr);

@@ -397,7 +397,8 @@ int main(int argc, char *argv[])
         fprintf(stderr, "         exact      find super-maximal exact matches (fermi exact)\n");
         fprintf(stderr, "         chkbwt     print / check the BWT held on the GPU (fermi chkbwt)\n");
         fprintf(stderr, "         unpack     print the indexed sequences (fermi unpack)\n");
-        fprintf(stderr, "         remap      coverage of contigs by the reads, paired-end breaks (fermi remap)\n\n");
+        fprintf(stderr, "         remap      coverage of contigs by the reads, paired-end breaks (fermi remap)\n");
+        fprintf(stderr, "         scaf       join unitigs across gaps with the read pairs (fermi scaf)\n\n");
         fprintf(stderr, "Environment: FMD_NUMA=off|all|<node>  `unitig` keeps to the CPUs of the NUMA node it started on (never more than the\n");
         fprintf(stderr, "                                      mask it inherited; nothing is done under taskset / numactl / a cpuset);\n");
         fprintf(stderr, "                                      off = no pinning, all = every command, <node> = that node\n\n");
@@ -414,7 +415,7 @@ int main(int argc, char *argv[])
     if (strcmp(argv[1], "cnt2qual") == 0) return fmdh_main_cnt2qual(argc - 1, argv + 1);
     if (strcmp(argv[1], "clean") == 0) return fmdh_main_clean(argc - 1, argv + 1);
     { const int node = stay_on_one_node(argv[1]); if (timing && node >= 0) fprintf(stderr, "[M::main] the process stays on NUMA node %d\n", node); }
-    if (strcmp(argv[1], "fltuniq") != 0 && fmd_device_count() <= 0) {   /* (fltuniq looks at its arguments first, as the reference does, then for the device) */
+    if (strcmp(argv[1], "fltuniq") != 0 && strcmp(argv[1], "scaf") != 0 && fmd_device_count() <= 0) {   /* (fltuniq and scaf look at their arguments first, as the reference does, then for the device) */
         fprintf(stderr, "[E::main] %s\n", fmd_strerror(FMD_E_NODEV));
         return 1;
     }
@@ -426,6 +427,7 @@ int main(int argc, char *argv[])
     else if (strcmp(argv[1], "contrast") == 0) rc = main_contrast(argc - 1, argv + 1);
     else if (strcmp(argv[1], "sub") == 0) rc = main_sub(argc - 1, argv + 1);
     else if (strcmp(argv[1], "fltuniq") == 0) rc = fmdh_main_fltuniq(argc - 1, argv + 1);
+    else if (strcmp(argv[1], "scaf") == 0) rc = fmdh_main_scaf(argc - 1, argv + 1);
     else if (strcmp(argv[1], "seqsort") == 0 || strcmp(argv[1], "seqrank") == 0) rc = main_seqsort(argc - 1, argv + 1);   /* main.c:109 */
     else if (strcmp(argv[1], "example") == 0) rc = fmdh_main_example(argc - 1, argv + 1);
     else if (strcmp(argv[1], "exact") == 0) rc = main_exact(argc - 1, argv + 1);

@@ -62,6 +62,25 @@ def lib():
         L.fmdh_api_correct.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]
         L.fmdh_api_seqlen.argtypes = [C.c_int64, C.c_void_p, C.c_double]
         L.fmdh_sw_score.argtypes = [C.c_int, C.c_char_p, C.c_int, C.c_char_p]
+        class SwAln(C.Structure):
+            _fields_ = [(n, C.c_int) for n in ("score", "te", "qe", "tb", "qb")]
+        L.SwAln = SwAln
+        L.fmdh_sw_align.argtypes = [C.c_int, C.c_char_p, C.c_int, C.c_char_p, C.POINTER(SwAln)]
+        for f, n in (("fmdh_kf_lgamma", 1), ("fmdh_kf_betai", 3), ("fmdh_scaf_correct_mean", 3)):
+            getattr(L, f).restype = C.c_double; getattr(L, f).argtypes = [C.c_double] * n
+        L.fmdh_scaf_pvalue.restype = C.c_double; L.fmdh_scaf_pvalue.argtypes = [C.c_int, C.c_int64, C.c_int64, C.c_double]
+        vp = C.c_void_p
+        L.fmdh_scaf_read.restype = vp; L.fmdh_scaf_read.argtypes = [C.c_char_p]
+        L.fmdh_scaf_count.restype = C.c_size_t; L.fmdh_scaf_count.argtypes = [vp]
+        L.fmdh_scaf_unitig_info.restype = None; L.fmdh_scaf_unitig_info.argtypes = [vp, C.c_size_t, vp, vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
+        L.fmdh_scaf_entries.restype = C.c_uint64; L.fmdh_scaf_entries.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp]
+        L.fmdh_scaf_set_links.argtypes = [vp, vp, vp]
+        L.fmdh_scaf_exclude.restype = None; L.fmdh_scaf_exclude.argtypes = [vp, C.c_double]
+        L.fmdh_scaf_choose.argtypes = [vp, C.c_uint64, vp, vp, vp]
+        L.fmdh_scaf_resolve_contained.restype = None; L.fmdh_scaf_resolve_contained.argtypes = [vp, C.c_uint32, C.c_double, C.c_double, C.c_int, vp]
+        L.fmdh_scaf_print_links.restype = None; L.fmdh_scaf_print_links.argtypes = [vp, vp]
+        L.fmdh_scaf_free.restype = None; L.fmdh_scaf_free.argtypes = [vp]
+        L.fmdh_scaf_cal_rdist.restype = C.c_double; L.fmdh_scaf_cal_rdist.argtypes = [vp]
         _lib = L
     return _lib
 
@@ -286,6 +305,101 @@ def sw_score(a, b):
     """fmdh_sw_score (host/swscore.c) of two sequences given as ACGT byte strings: the score of the local alignment the bubble poppers ask for."""
     a, b = bytes(a).translate(_NT4), bytes(b).translate(_NT4)
     return int(lib().fmdh_sw_score(len(a), a, len(b), b))
+
+
+_NT6 = bytes.maketrans(b"ACGTNacgtn", bytes([1, 2, 3, 4, 5, 1, 2, 3, 4, 5]))
+
+
+def sw_align(query, target):
+    """fmdh_sw_align (host/scaf_stat.c) of two ACGT byte strings, handed over as nt6 codes the way `scaf` does: (score, te, qe, tb, qb) as
+    ksw_align returns them with KSW_XSTART (match 1, mismatch -3, gap 5 + 2k)."""
+    L = lib()
+    q, t = bytes(query).translate(_NT6), bytes(target).translate(_NT6)
+    r = L.SwAln()
+    if L.fmdh_sw_align(len(q), q, len(t), t, C.byref(r)) != 0:
+        raise MemoryError("fmdh_sw_align")
+    return r.score, r.te, r.qe, r.tb, r.qb
+
+
+def scaf_betai(a, b, x):
+    return lib().fmdh_kf_betai(a, b, x)
+
+
+def scaf_correct_mean(l, mu, sigma):
+    return lib().fmdh_scaf_correct_mean(l, mu, sigma)
+
+
+def _scaf_unitig_list(L, s):
+    out = []
+    for i in range(L.fmdh_scaf_count(s)):
+        k, ilm, A, nr = (C.c_uint64 * 2)(), (C.c_int32 * 3)(), C.c_double(0), C.c_uint64(0)
+        L.fmdh_scaf_unitig_info(s, i, k, ilm, C.byref(A), C.byref(nr))
+        out.append(dict(k=(k[0], k[1]), len=ilm[0], nsr=ilm[1], maxo=ilm[2], A=A.value, n_reads=nr.value))
+    return out
+
+
+def scaf_unitigs(mag_path):
+    """The reader and the statistics of `scaf` (host/scaf_core.c; no GPU) over a remapped MAG: (rdist, [dict per unitig with a UR:Z: tag])."""
+    L = lib()
+    s = L.fmdh_scaf_read(os.fsencode(mag_path))
+    if not s:
+        raise IOError("cannot read " + str(mag_path))
+    try:
+        rdist = L.fmdh_scaf_cal_rdist(s)
+        return rdist, _scaf_unitig_list(L, s)
+    finally:
+        L.fmdh_scaf_free(s)
+
+
+def scaf_link_lines(mag_path, links, max_dist, a_thres=20., details=False, avg=None, std=None):
+    """The LK lines of `scaf -P` before any gap is patched, on the host: reader, rdist and A, then `links(x, span, utig, length, excluded,
+    max_dist)` -- the link stage, as api.scaf_links or a restatement of it: (self, mate, gkey, gval, n_nei) -- and the choice of the best two
+    neighbours of every end (fmdh_scaf_choose: the replay of the reference's small table).  Returns the lines; with details, also a dict of
+    the unitigs, the entries' unitig and the two words per entry.
+    With avg and std the contained unitigs are resolved as under -P (their CT lines come first)."""
+    import tempfile
+    L = lib()
+    s = L.fmdh_scaf_read(os.fsencode(mag_path))
+    if not s:
+        raise IOError("cannot read " + str(mag_path))
+    try:
+        L.fmdh_scaf_cal_rdist(s)
+        L.fmdh_scaf_exclude(s, a_thres)
+        us = _scaf_unitig_list(L, s)
+        exc = np.zeros(max(len(us), 1), dtype=np.uint8)
+        px, ps, pu = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        n = L.fmdh_scaf_entries(s, C.byref(px), C.byref(ps), C.byref(pu), exc.ctypes.data)
+        arr = lambda p, t, dt: np.frombuffer((t * n).from_address(p.value), dtype=dt).copy() if n else np.zeros(0, dtype=dt)
+        x, span, utig = arr(px, C.c_uint64, np.uint64), arr(ps, C.c_uint64, np.uint64), arr(pu, C.c_uint32, np.uint32)
+        own, mate, gkey, gval, n_nei = links(x, span, utig, np.array([u["len"] for u in us], dtype=np.int32), exc[:len(us)], max_dist)
+        own, mate, gkey, gval = (np.ascontiguousarray(a, dtype=np.uint64) for a in (own, mate, gkey, gval))
+        n_nei = np.ascontiguousarray(n_nei, dtype=np.uint32)
+        if L.fmdh_scaf_set_links(s, own.ctypes.data, mate.ctypes.data) or L.fmdh_scaf_choose(s, len(gkey), gkey.ctypes.data, gval.ctypes.data, n_nei.ctypes.data):
+            raise RuntimeError("fmdh_scaf_choose failed")
+        with tempfile.NamedTemporaryFile() as tf:
+            fp = _libc.fopen(tf.name.encode(), b"wb")
+            if avg is not None:
+                for i in range(len(us)):
+                    L.fmdh_scaf_resolve_contained(s, i, float(avg), float(std), 1, fp)
+            L.fmdh_scaf_print_links(s, fp)
+            _libc.fclose(fp)
+            lines = open(tf.name).read().split("\n")[:-1]
+        return (lines, dict(unitigs=us, utig=utig, own=own, mate=mate)) if details else lines
+    finally:
+        L.fmdh_scaf_free(s)
+
+
+def scaf(fmd_path, mag_path, avg, std, out_path, args=(), device=0):
+    """`fermi-amd scaf <args> -g device fmd mag avg std > out_path` (host/scaf_cmd.c): scaftigs as `fermi scaf` writes them; returns stderr
+    (with -P in args: the LK / CT / SW lines among it)."""
+    import subprocess
+    if not os.path.exists(BIN_PATH):
+        raise RuntimeError("fermi-amd is not built; run `make cli`")
+    with open(out_path, "wb") as out:
+        p = subprocess.run([BIN_PATH, "scaf"] + list(args) + ["-g", str(device), fmd_path, mag_path, str(avg), str(std)], stdout=out, stderr=subprocess.PIPE)
+    if p.returncode:
+        raise RuntimeError("fermi-amd scaf failed: " + p.stderr.decode(errors="replace").strip())
+    return p.stderr.decode(errors="replace")
 
 
 def _read_buffer(reads):

@@ -606,6 +606,30 @@ int fmd_fltuniq_export(fmd_fltuniq_t *f, uint64_t first_word, uint64_t n_words, 
 void fmd_fltuniq_close(fmd_fltuniq_t *f);
 void fmd_fltuniq_batch_limits(uint64_t *max_bytes, uint64_t *max_reads);
 
+/* ---- `fermi scaf`: the link stage, collect_nei (scaf.c:189-254) -- from the unpaired-read lists of a remapped MAG to links between unitig ends ----
+ * Entry i of the UR lists of all unitigs: x[i] = read id << 1 | strand, span[i] = b << 32 | e (already shifted and clipped to the trimmed
+ * unitig, scaf.c:107), utig[i] = its unitig (< n_utig < 2^31); per unitig len[] and excluded[] (A < a_thres, scaf.c:649-650).
+ * The end of an entry is idd = utig << 1 | ((x & 1) ^ 1), its distance to that end dist = (x & 1) ? e : len - b, its value idd << 32 | dist.
+ * The dictionary (the reference's hash `h`, scaf.c:195-211): read id -> value over the entries of unitigs that are not excluded with
+ * dist <= max_dist, for the ids that occur ONCE among them and whose value is not 0 (0 is the reference's "deleted" mark, scaf.c:207).
+ *   self[i], mate[i]   dictionary[x >> 1] and dictionary[(x >> 1) ^ 1], FMD_SCAF_NONE where absent -- for every entry, dropped ones included:
+ *                      the reference looks a read up by id alone (scaf.c:223, :356-360, :390-394), and so do add_seq and compute_t on these words.
+ *   gkey / gval        the links grouped (the table `t`, scaf.c:221-234): entry i contributes when self and mate are there and the mate's unitig is
+ *                      not utig[i]; key = (utig[i] << 1 | end bit of self) << 32 | the mate's idd, value = count << 40 | sum of both distances.
+ *                      *n_groups of them (<= n), ascending by key.
+ *   n_nei[2 n_utig]    per end, the number of its groups: what the reference's table held when it picked the best two (its bucket count carries
+ *                      over from end to end while it stays below 32, scaf.c:217-220, and decides the order of equal values).
+ * The _dev form enqueues on `stream` and returns; it allocates nothing (work_bytes >= fmd_scaf_links_work_bytes(n): six arrays of n words
+ * and rocPRIM's temporary storage).  The host form copies in, runs, copies out. */
+#define FMD_SCAF_NONE (~0ull)
+size_t fmd_scaf_links_work_bytes(uint64_t n);
+int fmd_scaf_links_dev(int device, void *stream, uint64_t n, const uint64_t *d_x, const uint64_t *d_span, const uint32_t *d_utig, uint64_t n_utig,
+                       const int32_t *d_len, const uint8_t *d_excluded, int max_dist, uint64_t *d_self, uint64_t *d_mate, uint64_t *d_gkey,
+                       uint64_t *d_gval, uint32_t *d_n_nei, uint64_t *d_n_groups, void *d_work, size_t work_bytes);
+int fmd_scaf_links(int device, uint64_t n, const uint64_t *x, const uint64_t *span, const uint32_t *utig, uint64_t n_utig, const int32_t *len,
+                   const uint8_t *excluded, int max_dist, uint64_t *self, uint64_t *mate, uint64_t *gkey, uint64_t *gval, uint32_t *n_nei,
+                   uint64_t *n_groups);
+
 /* device memory for C hosts (the reference has no device; these are what a cgo/C caller uses to
  * stage batches): plain hipMalloc / hipMemcpyAsync behind the ABI. */
 int fmd_dev_malloc(int device, size_t bytes, void **d_ptr);
