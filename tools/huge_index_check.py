@@ -5,7 +5,8 @@ blocks) on ONE GPU, without needing such an index: the "BWT" is a synthetic peri
 rank has a closed form, generated in HBM, transcoded by the product (fmd_dev_open_bwt_dev), then
   * rank1a / rank2a at random and at extreme positions against the closed form,
   * backward search (prefix table + stepping) against the same recurrence evaluated with the closed form.
-The string is not the BWT of any text -- rank and the search recurrence do not care.
+The string is not the BWT of any text -- rank and the search recurrence do not care.  Its four bases alternate, so their counts (and the high count
+bytes of the layout) stay equal: tests/test_gpu_layout_seams.py takes the same idea to arbitrary patterns (tests/periodic.py) and tells those fields apart.
 
     python tools/huge_index_check.py [n_symbols=1.4e11]
 """
