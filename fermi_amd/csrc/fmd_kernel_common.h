@@ -52,11 +52,14 @@ __device__ __forceinline__ FmdCand cand_decode(const uint4 a, const uint4 b)
     }
     return c;
 }
-__device__ __forceinline__ void cand_store_narrow(fmd_intv_t *e, uint64_t x0, uint64_t x1, uint32_t sz, uint32_t depth, uint64_t D, uint64_t r0)
+// (one candidate in either form: the words are chosen first and leave in two 16-byte stores -- a store_entry and a narrow store under an if compile to three)
+__device__ __forceinline__ void cand_store(fmd_intv_t *e, bool narrow, uint64_t x0, uint64_t x1, uint64_t sz, uint32_t depth, uint64_t D, uint64_t r0)
 {
     uint4 *q = (uint4 *)e;
-    q[0] = make_uint4((uint32_t)x0, ((uint32_t)(x0 >> 32) & 0xffu) | ((uint32_t)(r0 >> 32) & 0xffu) << 8 | depth << 16, (uint32_t)x1, (uint32_t)(x1 >> 32));
-    q[1] = make_uint4((uint32_t)D, (uint32_t)(D >> 32), (uint32_t)r0, FMD_CAND_NARROW | sz);
+    const uint32_t x0h = (uint32_t)(x0 >> 32);
+    q[0] = make_uint4((uint32_t)x0, narrow ? ((x0h & 0xffu) | ((uint32_t)(r0 >> 32) & 0xffu) << 8 | depth << 16) : x0h, (uint32_t)x1, (uint32_t)(x1 >> 32));
+    q[1] = make_uint4(narrow ? (uint32_t)D : (uint32_t)sz, narrow ? (uint32_t)(D >> 32) : (uint32_t)(sz >> 32), narrow ? (uint32_t)r0 : depth,
+                      narrow ? (FMD_CAND_NARROW | (uint32_t)sz) : 0u);
 }
 
 // ---- 64-position window over a lane's block images (used when an SA interval is narrower than 64)

@@ -14,7 +14,7 @@
 #ifndef FMD_HEAD_AUX
 #define FMD_HEAD_AUX 0
 #endif
-enum { WK_IDLE = 0, WK_LF, WK_EXT, WK_BOTH, WK_RIGHT, WK_ADM1, WK_ADM2 };
+enum { WK_IDLE = 0, WK_LF, WK_EXT, WK_BOTH, WK_RIGHT, WK_ADM1, WK_ADM2, WK_DONE };   // (WK_DONE: WALK_TAIL2 only)
 // can the LF step at row k be read from a block the backward extension of [x0, x0 + sz) brings in anyway (the block of x0 - 1, or
 // the block of its other end when that one does not reach it)?
 __device__ __forceinline__ bool walk_lf_shares(uint64_t k, uint64_t x0, uint64_t sz)
@@ -68,10 +68,14 @@ __device__ __forceinline__ bool walk_lf_shares(uint64_t k, uint64_t x0, uint64_t
 enum { WALK_WHOLE = 0, WALK_HEAD = 1, WALK_TAIL = 2, WALK_TAIL2 = 3 };   // (FMD_WALK_SPLIT, FmdWalkPark: fmd_kernel_common.h)
 
 // WALK_TAIL2 = WALK_TAIL for sequences of at most WALK_LS_BASES bases, without the stash in HBM and without k_ovl_seq_out behind it: the bases wait in
-// LDS, 2 bits each (code - 1; 7 words per lane: what is left of a CU's 160 KiB beside the gather's 8.25 KiB per wave at 16 waves), and the lane that
-// reaches its sequence's '$' writes the caller's row itself, in read order, from those words (walk_emit_row: ~250 instructions once per strand, where
-// the separate kernel read 112 + wrote 100 bytes per strand and cost the step 14 ms of its 272).  Reads of one length finish a wave together, so
-// nobody waits.  A sequence that holds an N (2 bits do not) is put on a list and k_ovl_seq_redo writes its row afterwards from what WALK_HEAD parked.
+// LDS, 2 bits each (code - 1; 7 words per lane: what is left of a CU's 160 KiB beside the gather's 8.25 KiB per wave at 16 waves), and a lane that
+// is through its sequence writes the caller's row itself, in read order, from those words at the strand's close (walk_emit_row: ~250 instructions for
+// the wave whoever takes part, where the separate kernel read 112 + wrote 100 bytes per strand and cost the step 14 ms of its 272).  A sequence that
+// holds an N (2 bits do not) is put on a list and k_ovl_seq_redo writes its row afterwards from what WALK_HEAD parked.
+// A strand closes in the step after its last (WK_DONE, top of the loop): the record in one piece, the row, its work list.  Reads of one length finish a wave
+// together, so the close has company by itself.  (Starting every strand 16 - o steps late, o = the low five bits of its sort key, so that the strands of one
+// minimizer stand at the same genome position in every step and share their rank blocks' lines: measured, 30 % fewer lines across L2 were expected, the step
+// gained 2.6 ms of 215, and it was not kept -- profiles/walk_phase)
 #define WALK_LS_WORDS 7
 #define WALK_LS_BASES (16 * WALK_LS_WORDS)
 #define WALK_F_HASN 0x80000000u       // (in the walk's `flags` register only: never stored)
@@ -160,8 +164,32 @@ __device__ __forceinline__ void walk_run(const FmdIndexView &ix, size_t n, const
     constexpr bool GUIDED = MODE != WALK_WHOLE;   // guided ticket chunks (fmd_wave.h) in the two passes of a sorted job, fixed ones in the one-pass walk
     fmd_tickets_init(tk_, queue, tickets, GUIDED ? n : 0);
     for (;;) {
+        // The close of a strand that is through its right extension (WK_DONE), in the step after its last: the record in one piece, the row in read order,
+        // the work list the strand belongs on.  Here and not where the right extension ends, so that the wave meets walk_emit_row's ~250 instructions in
+        // one place, with every lane that finished in the last step (reads of one length: the whole wave).
+        if (MODE == WALK_TAIL2 && st == WK_DONE) {   // k = fm_retrieve's row, x0 = k[0], x1 and sz = the two '$' ranks of the right extension (k[1], k[2])
+            uint4 *o = (uint4 *)(rec + gs);
+            o[0] = make_uint4((uint32_t)k, (uint32_t)(k >> 32), (uint32_t)x0, (uint32_t)(x0 >> 32));
+            o[1] = make_uint4((uint32_t)x1, (uint32_t)(x1 >> 32), (uint32_t)sz, (uint32_t)(sz >> 32));
+            o[2] = make_uint4(depth, ret < 0 ? (uint32_t)-3 : 0u, npush, (uint32_t)-1);           // len, status, n_ovlp, rbeg
+            o[3] = make_uint4(0u, 0u, flags & ~WALK_F_INTERNAL, 2u);                               // ext_len, n_nei, flags, reserved = 2 | lfork = 0
+            // (the caller's copy in read order: from LDS a lane writes it without holding up the others; every sequence with a complete record
+            // gets its row -- k_ovl_seq_out's conditions)
+            if (flags & WALK_F_HASN) redo[1 + atomicAdd(redo, 1u)] = (uint32_t)sid;
+            else walk_emit_row(walk_ls + fmd_lane(), depth, seq_out + gs * (size_t)seq_stride);
+            if (cls != nullptr && ret >= 0 && npush > 0 && !(flags & FMD_OVLP_F_OVERFLOW)) {   // k_ovl_classify's rule (fmd_ovlp_grp.hip)
+                int c = FMD_GRP_CLASSES;
+                if ((flags & WALK_F_W63) && depth < 65535u) {
+#pragma unroll
+                    for (int kk = FMD_GRP_CLASSES - 1; kk >= 0; --kk) if (kk >= min_cls && npush <= (uint32_t)fmd_grp_size(kk)) c = kk;
+                    if (c < FMD_GRP_CLASSES && (flags & WALK_F_WNARROW) && use_fast) c += FMD_GRP_CLASSES + 1 + ((flags & WALK_F_W32) ? FMD_GRP_CLASSES : 0);
+                }
+                fin_cls = c;
+            }
+            st = WK_IDLE;
+        }
         if (MODE == WALK_TAIL2 && cls != nullptr) {
-            // k_ovl_classify's work, by the lanes that finished a strand in the last step (reads of one length: the whole wave): one returning atomic per
+            // k_ovl_classify's work, by the lanes that have just closed a strand: one returning atomic per
             // list that gets entries, all of them issued at once (lane j reserves for the j-th distinct list), then every lane writes its entry.  The lists
             // and counters are where ovl_phase_b expects them (FmdOvlClasses over `cls`); depth, npush and sid are still the finished strand's.
             uint64_t rem = __ballot(fin_cls >= 0);
@@ -251,7 +279,7 @@ __device__ __forceinline__ void walk_run(const FmdIndexView &ix, size_t n, const
         }
         const bool was_two_phase = r.two_phase;
         fmd_wave_l_ready<WAUX>(ix, fmd_lds, r);
-        if (st == WK_IDLE || skip) continue;
+        if (st == WK_IDLE || skip || (MODE == WALK_TAIL2 && st == WK_DONE)) continue;
         if (MODE == WALK_HEAD && st == WK_ADM1) {   // the admission record has arrived (FmdHeadAdm, k_ovl_head_adm)
             gs = adm_a.x;
             depth = 0; npush = 0; pack = 0; pk0 = pk1 = pk2 = 0; flags = 0; ret = 0;
@@ -313,7 +341,7 @@ __device__ __forceinline__ void walk_run(const FmdIndexView &ix, size_t n, const
         // sizes, the base at row k (k lies inside the window) and rank_c(k) -- plus ONE absolute rank
         // of ONE symbol, rank_c(x0-1).  ~150 VALU instead of two full six-symbol block ranks (~600).
         const bool narrow = st == WK_BOTH && sz <= 63;
-        uint64_t ws[6] = {0, 0, 0, 0, 0, 0}, wtk = 0, wD = 0, wr0 = 0;  // wD, wr0: cand_store_narrow (fmd_kernel_common.h)
+        uint64_t ws[6] = {0, 0, 0, 0, 0, 0}, wtk = 0, wD = 0, wr0 = 0;  // wD, wr0: the narrow form of cand_store (fmd_kernel_common.h)
         if (narrow) {
             const uint32_t sh = (uint32_t)x0 & 31;
             uint4 a, b, cc;
@@ -393,10 +421,10 @@ __device__ __forceinline__ void walk_run(const FmdIndexView &ix, size_t n, const
                 if (MODE != WALK_HEAD && !info_only && (int)depth >= min_match && s[0]) {
                     if (npush < cap) {
                         fmd_intv_t *e = listA + sid * (size_t)cap + (cap - 1 - npush);
-                        if (narrow && depth < 65536u) cand_store_narrow(e, x0, x1, (uint32_t)sz, depth, wD, wr0);
-                        else store_entry(e, x0, x1, sz, (uint64_t)depth);
+                        const bool nf = narrow && depth < 65536u;
+                        cand_store(e, nf, x0, x1, sz, depth, wD, wr0);
                         if (MODE == WALK_TAIL2 && npush == 0)
-                            flags |= (sz <= 63 ? WALK_F_W63 : 0u) | (narrow && depth < 65536u ? WALK_F_WNARROW : 0u) | (sz > 31 ? WALK_F_W32 : 0u);
+                            flags |= (sz <= 63 ? WALK_F_W63 : 0u) | (nf ? WALK_F_WNARROW : 0u) | (sz > 31 ? WALK_F_W32 : 0u);
                     } else flags |= FMD_OVLP_F_OVERFLOW;
                     ++npush;
                 }
@@ -419,16 +447,16 @@ __device__ __forceinline__ void walk_run(const FmdIndexView &ix, size_t n, const
                     *(uint4 *)(srev + sid * (size_t)stride_r + (depth & ~15u)) = make_uint4(wq == 0 ? pack : pk0, wq == 1 ? pack : pk1, wq == 2 ? pack : pk2, wq == 3 ? pack : 0u);
                 }
                 fmd_ovlp_rec_t *o = rec + gs;
-                o->rank = k; o->len = (int32_t)depth; o->rbeg = -1; o->ext_len = 0; o->n_nei = 0; o->reserved = 2; o->lfork = 0;
-                o->k[0] = o->k[1] = o->k[2] = 0; o->n_ovlp = 0;
+                // (WALK_TAIL2 writes the record once, at the strand's close; here only the record of a strand that ends now)
+                if (MODE != WALK_TAIL2 || depth > stride_r || (!info_only && (int)depth <= min_match)) {
+                    o->rank = k; o->len = (int32_t)depth; o->rbeg = -1; o->ext_len = 0; o->n_nei = 0; o->reserved = 2; o->lfork = 0;
+                    o->k[0] = o->k[1] = o->k[2] = 0; o->n_ovlp = 0;
+                }
                 if (MODE == WALK_HEAD) park[gs].k = ~0ull;   // ended inside the head: shorter than min_match, the record below is final
                 if (depth > stride_r) { o->status = 0; o->flags = FMD_OVLP_F_OVERFLOW; st = WK_IDLE; continue; } // longer than max_len
                 if (!info_only && (int)depth <= min_match) { o->status = -1; o->flags = 0; st = WK_IDLE; continue; } // too short (unitig.c:288)
-                // (the caller's copy in read order is made by k_ovl_seq_out: a lane doing it here, from a stash in HBM, holds up the other 63)
-                if (MODE == WALK_TAIL2) {          // ... from LDS it does not: every sequence with a complete record gets its row now (k_ovl_seq_out's conditions)
-                    if (flags & WALK_F_HASN) redo[1 + atomicAdd(redo, 1u)] = (uint32_t)sid;
-                    else walk_emit_row(walk_ls + fmd_lane(), depth, seq_out + gs * (size_t)seq_stride);
-                }
+                // (the caller's copy in read order is made by k_ovl_seq_out: a lane doing it here, from a stash in HBM, holds up the other 63;
+                // WALK_TAIL2 writes it from LDS at the strand's close)
                 if (sz != s[0]) ret = -1;          // left-contained
                 x0 = tk[0]; sz = s[0];             // ok[0]: x[0] = cnt[0] + tk[0], x[1] unchanged
                 st = WK_RIGHT;
@@ -438,20 +466,12 @@ __device__ __forceinline__ void walk_run(const FmdIndexView &ix, size_t n, const
             const uint64_t t0k = was_two_phase ? tk2[0] : (r.hk ? fmd_block_rank1(r.bk, r.t, r.nk, 0, r.blk_k) : 0);
             const uint64_t t0l = r.hl ? fmd_block_rank1(r.bl, r.tl, r.nl, 0, r.blk_l) : 0;
             if (sz != t0l - t0k) ret = -1;
+            if (MODE == WALK_TAIL2) { x1 = t0k; sz = t0l - t0k; st = WK_DONE; continue; }   // everything else at the close (top of the loop)
             fmd_ovlp_rec_t *o = rec + gs;
             o->k[0] = x0; o->k[1] = t0k; o->k[2] = t0l - t0k;
             o->status = ret < 0 ? -3 : 0;
             o->n_ovlp = (int32_t)npush;
             o->flags = flags & ~WALK_F_INTERNAL;
-            if (MODE == WALK_TAIL2 && cls != nullptr && ret >= 0 && npush > 0 && !(flags & FMD_OVLP_F_OVERFLOW)) {   // k_ovl_classify's rule (fmd_ovlp_grp.hip)
-                int c = FMD_GRP_CLASSES;
-                if ((flags & WALK_F_W63) && depth < 65535u) {
-#pragma unroll
-                    for (int kk = FMD_GRP_CLASSES - 1; kk >= 0; --kk) if (kk >= min_cls && npush <= (uint32_t)fmd_grp_size(kk)) c = kk;
-                    if (c < FMD_GRP_CLASSES && (flags & WALK_F_WNARROW) && use_fast) c += FMD_GRP_CLASSES + 1 + ((flags & WALK_F_W32) ? FMD_GRP_CLASSES : 0);
-                }
-                fin_cls = c;
-            }
             st = WK_IDLE;
             continue;
         }
