@@ -26,7 +26,7 @@ ABI_SYMBOLS = [
     "fmd_rank1a_dev", "fmd_rank2a_dev", "fmd_rank1a_batch", "fmd_rank2a_batch",
     "fmd_extend_dev", "fmd_extend_batch", "fmd_bsearch_dev", "fmd_bsearch_batch",
     "fmd_retrieve_dev", "fmd_retrieve_batch", "fmd_probe_gather",
-    "fmd_build_bwt", "fmd_build_bwt_dev", "fmd_dev_free", "fmd_builder_new", "fmd_builder_add_dev", "fmd_builder_finish", "fmd_builder_free", "fmd_bwt_to_rle6", "fmd_host_free",
+    "fmd_build_bwt", "fmd_build_bwt_dev", "fmd_build_bwt_strands", "fmd_build_bwt_strands_dev", "fmd_dev_free", "fmd_builder_new", "fmd_builder_add_dev", "fmd_builder_finish", "fmd_builder_free", "fmd_bwt_to_rle6", "fmd_host_free",
     "fmd_dev_malloc", "fmd_memcpy_h2d", "fmd_memcpy_d2h",
     "fmd_smem_work_bytes", "fmd_smem_dev", "fmd_smem_batch", "fmd_smem_win_dev", "fmd_smem_win_batch", "fmd_reach_dev", "fmd_reach_batch", "fmd_dev_export_bwt", "fmd_dev_check_rank", "fmd_dev_build_pairs", "fmd_dev_check_pairs", "fmd_dev_line_count3",
     "fmd_kmer_work_bytes", "fmd_kmer_collect_dev", "fmd_kmer_collect_part_dev", "fmd_kmer_collect", "fmd_kmer_collect_seeds",
@@ -123,6 +123,8 @@ def _configure(L):
     L.fmd_retrieve_batch.argtypes = [vp, sz, u64p, vp, C.c_uint32, vp, u64p]
     L.fmd_build_bwt.argtypes = [C.c_int, sz, vp, u64p, vp, C.POINTER(C.c_uint64)]
     L.fmd_build_bwt_dev.argtypes = [C.c_int, vp, sz, vp, u64p, C.c_uint64, C.c_uint32, C.c_int, C.POINTER(vp), C.POINTER(C.c_uint64)]
+    L.fmd_build_bwt_strands.argtypes = [C.c_int, sz, vp, u64p, C.c_uint, vp, C.POINTER(C.c_uint64)]
+    L.fmd_build_bwt_strands_dev.argtypes = [C.c_int, vp, sz, vp, u64p, C.c_uint64, C.c_uint32, C.c_int, C.c_uint, C.POINTER(vp), C.POINTER(C.c_uint64)]
     L.fmd_dev_free.restype = None; L.fmd_dev_free.argtypes = [vp]
     L.fmd_builder_new.argtypes = [C.c_int, C.c_uint64, C.c_uint32, C.POINTER(vp)]
     L.fmd_builder_add_dev.argtypes = [vp, vp, C.c_uint64, vp]
@@ -594,6 +596,20 @@ def build_bwt(seqs, device=0):
     bwt = np.zeros(2 * (int(off[n]) + n), dtype=np.uint8)
     n_sym = C.c_uint64(0)
     check(lib().fmd_build_bwt(device, n, _ptr(flat), _ptr(off), _ptr(bwt), C.byref(n_sym)))
+    assert n_sym.value == len(bwt)
+    return bwt
+
+
+STRAND_FWD, STRAND_REV, STRAND_BOTH = 1, 2, 3   # FMD_STRAND_*: the flags of ropebwt.c:14-15
+
+
+def build_bwt_strands(seqs, strands=STRAND_BOTH, device=0):
+    """`fermi ropebwt [-F] [-R]` BWT of a read collection (ropebwt.c:22-45): the forward strand, the reverse complement, or both per read."""
+    flat, off = flatten_reads(seqs)
+    n = len(off) - 1
+    bwt = np.zeros((2 if strands == STRAND_BOTH else 1) * (int(off[n]) + n), dtype=np.uint8)
+    n_sym = C.c_uint64(0)
+    check(lib().fmd_build_bwt_strands(device, n, _ptr(flat), _ptr(off), int(strands), _ptr(bwt), C.byref(n_sym)))
     assert n_sym.value == len(bwt)
     return bwt
 

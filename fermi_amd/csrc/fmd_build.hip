@@ -12,20 +12,25 @@
 #include <type_traits>
 #include "fmd_internal.h"
 
-// text[T_s ..] for sequence s = 2r (forward) / 2r+1 (reverse complement); one thread per read base
+// The strands of a read that are indexed: the flags of ropebwt.c:14-15 (insert1, ropebwt.c:22-45: the forward strand, then the reverse complement,
+// each a sequence with its own '$').  S = FMD_STRAND_BOTH is `fermi build`'s text  read $ revcomp $ ; one strand alone is  read $  or  revcomp $ .
+
+// text[T_s ..] for sequence s = 2r (forward) / 2r+1 (reverse complement) -- s = r with one strand; one thread per read base
+template <unsigned S>
 __global__ void k_build_text(size_t n_reads, const uint8_t *__restrict__ reads, const uint64_t *__restrict__ off,
                              uint8_t *__restrict__ text)
 {
     // one 64-thread group per read (grid-stride: the grid is capped)
     for (size_t r = blockIdx.x; r < n_reads; r += gridDim.x) {
         const uint64_t o = off[r], len = off[r + 1] - o;
-        const uint64_t t0 = 2 * (o + r); // both strands of all earlier reads, each with its '$'
+        const uint64_t t0 = (S == FMD_STRAND_BOTH ? 2 : 1) * (o + r); // the indexed strands of all earlier reads, each with its '$'
+        const uint64_t rv = S == FMD_STRAND_BOTH ? t0 + len + 1 : t0; // where the reverse complement starts
         for (uint64_t i = threadIdx.x; i < len; i += blockDim.x) {
             const uint8_t c = reads[o + i];
-            text[t0 + i] = c;
-            text[t0 + len + 1 + (len - 1 - i)] = (c >= 1 && c <= 4) ? (uint8_t)(5 - c) : c;
+            if (S & FMD_STRAND_FWD) text[t0 + i] = c;
+            if (S & FMD_STRAND_REV) text[rv + (len - 1 - i)] = (c >= 1 && c <= 4) ? (uint8_t)(5 - c) : c;
         }
-        if (threadIdx.x == 0) { text[t0 + len] = 0; text[t0 + 2 * len + 1] = 0; }
+        if (threadIdx.x == 0) { text[t0 + len] = 0; if (S == FMD_STRAND_BOTH) text[t0 + 2 * len + 1] = 0; }
     }
 }
 
@@ -76,11 +81,13 @@ __global__ void k_emit_bwt(const uint8_t *__restrict__ text, const uint32_t *__r
     }
 }
 
+template <unsigned S>
 __global__ void k_seq_ends(size_t n_reads, const uint64_t *__restrict__ off, uint64_t *__restrict__ send)
 {
     for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n_reads; r += (uint64_t)gridDim.x * blockDim.x) {
-        const uint64_t o = off[r], len = off[r + 1] - o, t0 = 2 * (o + r);
-        send[2 * r] = t0 + len; send[2 * r + 1] = t0 + 2 * len + 1;
+        const uint64_t o = off[r], len = off[r + 1] - o, t0 = (S == FMD_STRAND_BOTH ? 2 : 1) * (o + r);
+        if (S == FMD_STRAND_BOTH) { send[2 * r] = t0 + len; send[2 * r + 1] = t0 + 2 * len + 1; }
+        else send[r] = t0 + len;
     }
 }
 
@@ -481,24 +488,43 @@ static int bucket_depth(uint64_t n, int fixed_bytes_per_symbol_already_allocated
 
 extern "C" void fmd_dev_free(void *d_ptr) { if (d_ptr) hipFree(d_ptr); }
 
+// the text and, for reads of several lengths, the position of every '$' (what RemRagged searches)
+template <unsigned S>
+static void launch_text(hipStream_t st, size_t n_reads, const uint8_t *d_reads, const uint64_t *d_off, uint8_t *text, uint64_t *send)
+{
+    k_build_text<S><<<(unsigned)(n_reads < (1u << 24) ? n_reads : (1u << 24)), 64, 0, st>>>(n_reads, d_reads, d_off, text);
+    if (send) k_seq_ends<S><<<fmd_nblk(n_reads, 256), 256, 0, st>>>(n_reads, d_off, send);
+}
+
 extern "C" int fmd_build_bwt_dev(int device, void *stream_, size_t n_reads, const uint8_t *d_reads, const uint64_t *d_off,
                                  uint64_t total_bases, uint32_t max_len, int uniform_len, uint8_t **d_bwt_out, uint64_t *n_sym_out)
 {
-    if (!d_reads || !d_off || !d_bwt_out || !n_sym_out || n_reads == 0 || max_len == 0) return FMD_E_ARG;
+    if (max_len == 0) return FMD_E_ARG;
+    return fmd_build_bwt_strands_dev(device, stream_, n_reads, d_reads, d_off, total_bases, max_len, uniform_len, FMD_STRAND_BOTH, d_bwt_out, n_sym_out);
+}
+
+// ropebwt.c:22-45.  Everything behind the text -- keys, sorts, buckets -- knows the text only through its length, the distance of a position to
+// its '$' (RemUniform / RemRagged) and the number of sequences; a read of no bases (legal here) is a sequence of its '$' alone.
+extern "C" int fmd_build_bwt_strands_dev(int device, void *stream_, size_t n_reads, const uint8_t *d_reads, const uint64_t *d_off,
+                                         uint64_t total_bases, uint32_t max_len, int uniform_len, unsigned strands, uint8_t **d_bwt_out, uint64_t *n_sym_out)
+{
+    if (!d_reads || !d_off || !d_bwt_out || !n_sym_out || n_reads == 0) return FMD_E_ARG;
+    if (strands != FMD_STRAND_FWD && strands != FMD_STRAND_REV && strands != FMD_STRAND_BOTH) return FMD_E_ARG;
     if (fmd_device_count() <= 0) return FMD_E_NODEV;
     FMD_HIP_TRY(hipSetDevice(device));
     hipStream_t st = (hipStream_t)stream_;
-    const uint64_t n = 2 * (total_bases + n_reads);
+    const uint64_t per = strands == FMD_STRAND_BOTH ? 2 : 1, n = per * (total_bases + n_reads);
     const bool bucketed = n >= 0xffffffffull || getenv("FMD_BUILD_BUCKETED") != nullptr; // 32-bit suffix ids in the one-shot path
     FmdDevBuf text, keys_a, keys_b, ord_a, ord_b, send, tmp, bwt;
     FMD_TRY(text.alloc(n + 64));
-    k_build_text<<<(unsigned)(n_reads < (1u << 24) ? n_reads : (1u << 24)), 64, 0, st>>>(n_reads, d_reads, d_off, (uint8_t *)text.p);
-    RemRagged rr{nullptr, 2 * n_reads};
+    RemRagged rr{nullptr, per * n_reads};
     if (!uniform_len) {
-        FMD_TRY(send.alloc(2 * n_reads * 8));
-        k_seq_ends<<<fmd_nblk(n_reads, 256), 256, 0, st>>>(n_reads, d_off, (uint64_t *)send.p);
+        FMD_TRY(send.alloc(per * n_reads * 8));
         rr.send = (const uint64_t *)send.p;
     }
+    if (strands == FMD_STRAND_BOTH) launch_text<FMD_STRAND_BOTH>(st, n_reads, d_reads, d_off, (uint8_t *)text.p, (uint64_t *)send.p);
+    else if (strands == FMD_STRAND_FWD) launch_text<FMD_STRAND_FWD>(st, n_reads, d_reads, d_off, (uint8_t *)text.p, (uint64_t *)send.p);
+    else launch_text<FMD_STRAND_REV>(st, n_reads, d_reads, d_off, (uint8_t *)text.p, (uint64_t *)send.p);
     if (bucketed) {
         FMD_TRY(bwt.alloc(n + 64));
         FMD_TRY(build_bucketed(st, Text8{(const uint8_t *)text.p}, n, max_len, uniform_len, rr, bucket_depth(n, 2), bwt.as<uint8_t>(), NoSink()));
@@ -615,11 +641,21 @@ extern "C" int fmd_build_bwt(int device, size_t n_reads, const uint8_t *reads, c
 {
     if (!reads || !off || !bwt || !n_sym || n_reads == 0) return FMD_E_ARG;
     if (fmd_device_count() <= 0) return FMD_E_NODEV;
+    for (size_t i = 0; i < n_reads; ++i) if (off[i + 1] == off[i]) return FMD_E_ARG;   // (`fermi build` drops empty records before it gets here)
+    return fmd_build_bwt_strands(device, n_reads, reads, off, FMD_STRAND_BOTH, bwt, n_sym);
+}
+// the same for a chosen set of strands (ropebwt.c:22-45); bwt must hold off[n] + n bytes for one strand, twice that for both
+extern "C" int fmd_build_bwt_strands(int device, size_t n_reads, const uint8_t *reads, const uint64_t *off, unsigned strands, uint8_t *bwt, uint64_t *n_sym)
+{
+    if (!reads || !off || !bwt || !n_sym || n_reads == 0) return FMD_E_ARG;
+    if (strands != FMD_STRAND_FWD && strands != FMD_STRAND_REV && strands != FMD_STRAND_BOTH) return FMD_E_ARG;
+    if (fmd_device_count() <= 0) return FMD_E_NODEV;
     FMD_HIP_TRY(hipSetDevice(device));
     uint32_t max_len = 0; int uniform = 1;
     for (size_t i = 0; i < n_reads; ++i) {
+        if (off[i + 1] < off[i]) return FMD_E_ARG;
         const uint64_t l = off[i + 1] - off[i];
-        if (l == 0 || l > 0xfffffff0ull) return FMD_E_ARG;
+        if (l > 0xfffffff0ull) return FMD_E_ARG;
         if (l > max_len) max_len = (uint32_t)l;
         if (l != off[1] - off[0]) uniform = 0;
     }
@@ -628,7 +664,7 @@ extern "C" int fmd_build_bwt(int device, size_t n_reads, const uint8_t *reads, c
     FMD_HIP_TRY(hipMemcpy(dr.p, reads, off[n_reads], hipMemcpyHostToDevice));
     FMD_HIP_TRY(hipMemcpy(doff.p, off, (n_reads + 1) * 8, hipMemcpyHostToDevice));
     uint8_t *d_bwt = nullptr;
-    int rc = fmd_build_bwt_dev(device, nullptr, n_reads, (uint8_t *)dr.p, (uint64_t *)doff.p, off[n_reads], max_len, uniform, &d_bwt, n_sym);
+    int rc = fmd_build_bwt_strands_dev(device, nullptr, n_reads, (uint8_t *)dr.p, (uint64_t *)doff.p, off[n_reads], max_len, uniform, strands, &d_bwt, n_sym);
     if (rc) return rc;
     hipError_t e = hipMemcpy(bwt, d_bwt, *n_sym, hipMemcpyDeviceToHost);
     fmd_dev_free(d_bwt);

@@ -360,12 +360,16 @@ int fmdh_sub(const char *fmd_path, const char *bits_path, int is_comp, int devic
 int fmdh_bitand(int n_in, char *const *in, FILE *out);
 /* readprep_cmd.c: the read-preparation commands, argv as the reference's main_* take it (argv[0] = the command's name), output on stdout:
  * `fermi fltuniq [-k INT] <in.fa>` (seq.c:122-210; -g GPU; the table and both passes on the GPU, the file streamed twice in batches),
- * and, without a GPU, `trimseq` (seq.c:289-373), `pe2cofq` (seq.c:257-287), `splitfa` (seq.c:79-120), `cnt2qual` (cmd.c:13-45) */
+ * and, without a GPU, `trimseq` (seq.c:289-373), `pe2cofq` (seq.c:257-287), `cg2cofq` (seq.c:212-255), `splitfa` (seq.c:79-120), `cnt2qual` (cmd.c:13-45) */
 int fmdh_main_fltuniq(int argc, char *argv[]);
 int fmdh_main_trimseq(int argc, char *argv[]);
 int fmdh_main_pe2cofq(int argc, char *argv[]);
+int fmdh_main_cg2cofq(int argc, char *argv[]);
 int fmdh_main_splitfa(int argc, char *argv[]);
 int fmdh_main_cnt2qual(int argc, char *argv[]);
+/* ropebwt_cmd.c: `fermi ropebwt` (ropebwt.c:47-158), the index builder of the driver script: one strand or both (fmd_build_bwt_strands), the BWT as text
+ * or as RLE\6 runs; -g GPU.  Looks at its arguments first, then for the device. */
+int fmdh_main_ropebwt(int argc, char *argv[]);
 int fmdh_fltuniq_auto_k(long long file_bytes);   /* the k `fltuniq` takes for an input file of that many bytes on disk (seq.c:147-150) */
 
 /* `fermi correct` (cmd.c:253-291, correct.c:305-456); defaults = cmd.c:258 */

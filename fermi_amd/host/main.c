@@ -378,12 +378,14 @@ int main(int argc, char *argv[])
         fprintf(stderr, "\nProgram: fermi-amd (FMD-index hot path of fermi on AMD MI355X)\n\n");
         fprintf(stderr, "Usage:   fermi-amd <command> [arguments]\n\n");
         fprintf(stderr, "Command: build      generate the FMD-index (fermi build)\n");
+        fprintf(stderr, "         ropebwt    the BWT of one strand or both as text or RLE\\6, the driver script's index builder (fermi ropebwt)\n");
         fprintf(stderr, "         merge      merge FMD-indexes (fermi merge)\n");
         fprintf(stderr, "         recode     RLE\\6 -> RLD\\2 (fermi recode)\n");
         fprintf(stderr, "         contrast   reads with k-mers the other index lacks (fermi contrast)\n");
         fprintf(stderr, "         sub        sub-index of selected reads (fermi sub)\n");
         fprintf(stderr, "         bitand     AND of bit arrays, no GPU needed (fermi bitand)\n");
         fprintf(stderr, "         pe2cofq    interleave two mate files under one name, no GPU needed (fermi pe2cofq)\n");
+        fprintf(stderr, "         cg2cofq    split records that hold both arms of a pair in one line, no GPU needed (fermi cg2cofq)\n");
         fprintf(stderr, "         trimseq    trim / drop reads by quality, no GPU needed (fermi trimseq)\n");
         fprintf(stderr, "         splitfa    deal read pairs to N files, no GPU needed (fermi splitfa)\n");
         fprintf(stderr, "         cnt2qual   occurrence counts -> qualities, no GPU needed (fermi cnt2qual)\n");
@@ -411,11 +413,12 @@ int main(int argc, char *argv[])
     if (strcmp(argv[1], "bitand") == 0) return main_bitand(argc - 1, argv + 1);   /* host only: runs where there is no GPU */
     if (strcmp(argv[1], "trimseq") == 0) return fmdh_main_trimseq(argc - 1, argv + 1);
     if (strcmp(argv[1], "pe2cofq") == 0) return fmdh_main_pe2cofq(argc - 1, argv + 1);
+    if (strcmp(argv[1], "cg2cofq") == 0) return fmdh_main_cg2cofq(argc - 1, argv + 1);
     if (strcmp(argv[1], "splitfa") == 0) return fmdh_main_splitfa(argc - 1, argv + 1);
     if (strcmp(argv[1], "cnt2qual") == 0) return fmdh_main_cnt2qual(argc - 1, argv + 1);
     if (strcmp(argv[1], "clean") == 0) return fmdh_main_clean(argc - 1, argv + 1);
     { const int node = stay_on_one_node(argv[1]); if (timing && node >= 0) fprintf(stderr, "[M::main] the process stays on NUMA node %d\n", node); }
-    if (strcmp(argv[1], "fltuniq") != 0 && strcmp(argv[1], "scaf") != 0 && fmd_device_count() <= 0) {   /* (fltuniq and scaf look at their arguments first, as the reference does, then for the device) */
+    if (strcmp(argv[1], "fltuniq") != 0 && strcmp(argv[1], "scaf") != 0 && strcmp(argv[1], "ropebwt") != 0 && fmd_device_count() <= 0) {   /* (fltuniq, scaf and ropebwt look at their arguments first, as the reference does, then for the device) */
         fprintf(stderr, "[E::main] %s\n", fmd_strerror(FMD_E_NODEV));
         return 1;
     }
@@ -428,6 +431,7 @@ int main(int argc, char *argv[])
     else if (strcmp(argv[1], "sub") == 0) rc = main_sub(argc - 1, argv + 1);
     else if (strcmp(argv[1], "fltuniq") == 0) rc = fmdh_main_fltuniq(argc - 1, argv + 1);
     else if (strcmp(argv[1], "scaf") == 0) rc = fmdh_main_scaf(argc - 1, argv + 1);
+    else if (strcmp(argv[1], "ropebwt") == 0) rc = fmdh_main_ropebwt(argc - 1, argv + 1);
     else if (strcmp(argv[1], "seqsort") == 0 || strcmp(argv[1], "seqrank") == 0) rc = main_seqsort(argc - 1, argv + 1);   /* main.c:109 */
     else if (strcmp(argv[1], "example") == 0) rc = fmdh_main_example(argc - 1, argv + 1);
     else if (strcmp(argv[1], "exact") == 0) rc = main_exact(argc - 1, argv + 1);

@@ -64,10 +64,35 @@ int fmdh_merge_pair_to_file(fmd_dev_t *h0, fmd_dev_t *h1, const char *out_path)
     return 0;
 }
 
+/* `-`: the index from stdin (rld_restore_header, rld.c:273), as the driver's `ropebwt ... | recode -` would hand it over: all of it read
+ * into memory, then the container's payload (header as rld.c:242-263) or the run bytes behind a 4-byte magic (rld.c:295-308) */
+static int open_stdin(int device, fmd_dev_t **h)
+{
+    size_t n = 0, m = 1 << 20, k;
+    uint8_t *buf = (uint8_t *)malloc(m);
+    int rc;
+    while (buf && (k = fread(buf + n, 1, m - n, stdin)) > 0)
+        if ((n += k) == m) buf = (uint8_t *)realloc(buf, m <<= 1);
+    if (!buf) return FMD_E_NOMEM;
+    if (n <= 4) rc = FMD_E_FORMAT;
+    else if (memcmp(buf, "RLD\2", 4) == 0) {
+        uint32_t a = 0; uint64_t hdr[3] = {0, 0, 0}, mcnt[7];
+        if (n >= 80) { memcpy(&a, buf + 4, 4); memcpy(hdr, buf + 8, 24); memcpy(mcnt + 1, buf + 32, 48); }
+        if (n < 80 || (a >> 16) != 6 || (a & 0xffff) != 3 || (hdr[1] & 7) || hdr[1] > n - 80) rc = FMD_E_FORMAT;
+        else {
+            int j;
+            for (mcnt[0] = 0, j = 1; j < 7; ++j) mcnt[0] += mcnt[j];
+            rc = fmd_dev_open_rld(device, (const uint64_t *)(buf + 80), hdr[1] / 8, mcnt, h);   /* (a malloc'ed block + 80: aligned) */
+        }
+    } else rc = fmd_dev_open_rle6(device, buf + 4, n - 4, h);
+    free(buf);
+    return rc;
+}
+
 static fmd_dev_t *open_input(const char *fn, int device, const char *func)
 {
     fmd_dev_t *h = 0;
-    const int rc = fmd_dev_open_file_ex(device, fn, FMD_OPEN_NO_TABLES, &h);
+    const int rc = strcmp(fn, "-") ? fmd_dev_open_file_ex(device, fn, FMD_OPEN_NO_TABLES, &h) : open_stdin(device, &h);
     if (rc) { fprintf(stderr, "[E::%s] Fail to open the index file `%s': %s.\n", func, fn, fmd_strerror(rc)); return 0; }
     return h;
 }

@@ -1,11 +1,11 @@
 /* readprep_cmd.c -- the read-preparation commands of fermi's driver script: `fermi fltuniq` (seq.c:122-210), `trimseq` (seq.c:289-373),
- * `pe2cofq` (seq.c:257-287), `splitfa` (seq.c:79-120) and `cnt2qual` (cmd.c:13-45), same argv, messages and output bytes.
+ * `pe2cofq` (seq.c:257-287), `cg2cofq` (seq.c:212-255), `splitfa` (seq.c:79-120) and `cnt2qual` (cmd.c:13-45), same argv, messages and output bytes.
  * fltuniq: the k-mer table lives on the GPU (fmd_fltuniq_*: include/fmd_hip.h); the file is read twice in batches of at most
  * fmd_fltuniq_batch_limits() bases and reads -- pass 1 counts, pass 2 tests -- and a batch is parsed while the one before it is copied and worked on.  What the host keeps
  * is two batches of bases and, in pass 2, the text of their records until their verdicts are back; the pairing machine of
  * seq.c:185-204 then runs over (name, verdict) in file order exactly as the reference runs it over the records.
  * Bytes >= 128 in a sequence: the reference indexes seq_nt6_table out of range with them (undefined); here they are non-bases.
- * The other four touch no GPU. */
+ * The other five touch no GPU. */
 #include <ctype.h>
 #include <math.h>
 #include <stdio.h>
@@ -300,6 +300,39 @@ int fmdh_main_pe2cofq(int argc, char *argv[])
         fputs(str.s, stdout);
     }
     fmdh_seq_close(io[0]); fmdh_seq_close(io[1]);
+    free(str.s);
+    return 0;
+}
+
+/* ---- cg2cofq ---- */
+/* A record whose sequence is two runs of letters with something else between them -- the two arms of a pair in one line -- becomes two records
+ * under the one name (no comment): the letters up to the first other character, then everything from the next letter on, each with its part of
+ * the quality.  A record without a second run of letters gives the first record alone: the reference's scan for the second run has no
+ * end (seq.c:238 tests the length, not the index) and reads past the sequence there. */
+int fmdh_main_cg2cofq(int argc, char *argv[])
+{
+    fmdh_seqio_t *io;
+    str_t str = {0, 0, 0};
+    int len;
+    if (argc == 1) {
+        fprintf(stderr, "Usage: fermi-amd cg2cofq <in.cgfq>\n");
+        return 1;
+    }
+    io = fmdh_seq_open(argv[1]);
+    if (!io) { fprintf(stderr, "[E::main_cg2cofq] fail to open file '%s'\n", argv[1]); return 1; }
+    while ((len = fmdh_seq_read(io)) >= 0) {
+        const char *name = fmdh_seq_name(io), *seq = fmdh_seq_bases(io), *qual = fmdh_seq_qual(io);
+        int i, j;
+        str.l = 0;
+        for (i = 0; i < len; ++i)
+            if (!isalpha((unsigned char)seq[i])) break;
+        write_seq(&str, name, strlen(name), 0, seq, (size_t)i, qual);
+        for (j = i; j < len; ++j)
+            if (isalpha((unsigned char)seq[j])) break;
+        if (j < len) write_seq(&str, name, strlen(name), 0, seq + j, (size_t)(len - j), qual ? qual + j : 0);
+        fputs(str.s, stdout);
+    }
+    fmdh_seq_close(io);
     free(str.s);
     return 0;
 }

@@ -402,6 +402,18 @@ def scaf(fmd_path, mag_path, avg, std, out_path, args=(), device=0):
     return p.stderr.decode(errors="replace")
 
 
+def ropebwt(in_path, out_path, args=("-a", "bcr", "-bN"), device=0):
+    """`fermi-amd ropebwt <args> -g device -o out_path in_path` (host/ropebwt_cmd.c over api.build_bwt_strands' entry, fmd_build_bwt_strands): the BWT
+    of one strand or both as text, or with -b as RLE\\6 runs; returns stderr (the reference's warnings, and with -v3 the phase lines)."""
+    import subprocess
+    if not os.path.exists(BIN_PATH):
+        raise RuntimeError("fermi-amd is not built; run `make cli`")
+    p = subprocess.run([BIN_PATH, "ropebwt"] + list(args) + ["-g", str(device), "-o", out_path, in_path], stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+    if p.returncode:
+        raise RuntimeError("fermi-amd ropebwt failed: " + p.stderr.decode(errors="replace").strip())
+    return p.stderr.decode(errors="replace")
+
+
 def _read_buffer(reads):
     """list of byte strings -> one buffer with a NUL after every read (what fm6_api_readseq returns, seq.c:385-408)"""
     return np.frombuffer(b"".join(r + b"\0" for r in reads), dtype=np.uint8).copy()

@@ -505,6 +505,20 @@ int fmd_seqinfo_batch(fmd_dev_t *h, size_t n, const uint64_t *ids, uint32_t max_
 int fmd_build_bwt(int device, size_t n_reads, const uint8_t *reads, const uint64_t *off, uint8_t *bwt, uint64_t *n_sym);
 int fmd_build_bwt_dev(int device, void *stream, size_t n_reads, const uint8_t *d_reads, const uint64_t *d_off,
                       uint64_t total_bases, uint32_t max_len, int uniform_len, uint8_t **d_bwt, uint64_t *n_sym);
+/* The BWT of a chosen set of strands: what `fermi ropebwt [-F] [-R]` inserts per read (insert1, ropebwt.c:22-45) -- the forward
+ * strand, then the reverse complement, each a sequence of its own closed by its '$'; `strands` takes ropebwt.c's flag values.
+ *   FMD_STRAND_BOTH   read $ revcomp $   n_sym = 2 * (total_bases + n_reads)   (= fmd_build_bwt, byte for byte)
+ *   FMD_STRAND_FWD    read $             n_sym = total_bases + n_reads
+ *   FMD_STRAND_REV    revcomp $          n_sym = total_bases + n_reads
+ * Any other value is FMD_E_ARG.  Sentinels are ordered by insertion order, symbol 5 (N) is its own complement.  Unlike
+ * fmd_build_bwt, a read of no bases is legal: a sequence of its '$' alone (bpr_insert_string with l = 0, bprope6.c:218-224).
+ * bwt (host) must hold n_sym bytes.  Reads and arguments otherwise as above. */
+#define FMD_STRAND_FWD  1u
+#define FMD_STRAND_REV  2u
+#define FMD_STRAND_BOTH 3u
+int fmd_build_bwt_strands(int device, size_t n_reads, const uint8_t *reads, const uint64_t *off, unsigned strands, uint8_t *bwt, uint64_t *n_sym);
+int fmd_build_bwt_strands_dev(int device, void *stream, size_t n_reads, const uint8_t *d_reads, const uint64_t *d_off,
+                              uint64_t total_bases, uint32_t max_len, int uniform_len, unsigned strands, uint8_t **d_bwt, uint64_t *n_sym);
 void fmd_dev_free(void *d_ptr);
 /* The same index without the byte BWT, for read sets whose text + BWT do not fit next to the index (7*10^8 x 100 bp:
  * 1.4*10^11 symbols): reads of ONE length appended in any number of calls (n x read_len nt6 bytes on the device, no
