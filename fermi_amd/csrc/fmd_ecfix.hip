@@ -789,6 +789,22 @@ extern "C" int fmd_ectab_build(int device, int w, int suf_len, uint64_t n, const
     return FMD_OK;
 }
 
+// Two test aids that change no result, behind FMD_ECFIX_TEST_HOOKS=1 (as FMD_FLTUNIQ_TEST_HOOKS, fmd_fltuniq.hip): without the gate neither variable is
+// read, and the environment is read on every call.  FMD_ECFIX_TEST_WAVES=v (v >= 1) caps the waves ec_grid returns -- the work area (fmd_ecfix_work_bytes) and
+// the launch (fmd_ecfix_dev) both ask ec_grid, so they stay consistent -- and a few hundred reads make every lane take read after read from the ticket queue.
+// FMD_ECFIX_TEST_TRACE=v (v >= 16) replaces the trace capacity fmd_ecfix_batch starts with (1024), so that its re-run loop runs several times on short reads.
+static bool ec_test_hooks_on()
+{
+    const char *on = getenv("FMD_ECFIX_TEST_HOOKS");
+    return on && atoi(on) == 1;
+}
+static long ec_test_value(const char *e, long least)   // the value of a test variable; 0: not set or out of range
+{
+    if (!e) return 0;
+    const long v = strtol(e, nullptr, 10);
+    return v >= least && v <= (1l << 20) ? v : 0;
+}
+
 static int ec_grid(int device, size_t n)   // the resident set: a workgroup (one wave) holds EC_LDS_BYTES of the CU's 160 KiB
 {
     hipDeviceProp_t prop;
@@ -796,6 +812,8 @@ static int ec_grid(int device, size_t n)   // the resident set: a workgroup (one
     if (hipGetDeviceProperties(&prop, device) == hipSuccess) cus = prop.multiProcessorCount;
     const size_t per_cu = (160 * 1024) / (((size_t)EC_LDS_BYTES + 1279) / 1280 * 1280);
     size_t waves = (size_t)cus * per_cu, need = (n + 63) / 64;
+    const long cap = ec_test_hooks_on() ? ec_test_value(getenv("FMD_ECFIX_TEST_WAVES"), 1) : 0;
+    if (cap && (size_t)cap < waves) waves = (size_t)cap;
     return (int)(need < waves ? (need ? need : 1) : waves);
 }
 
@@ -859,6 +877,8 @@ extern "C" int fmd_ecfix_batch(fmd_ectab_t *t, size_t n, uint8_t *seqs, uint8_t 
     FMD_HIP_TRY(hipSetDevice(t->device));
     const uint64_t total = off[n] - off[0];
     uint32_t cap = 1024;
+    if (ec_test_hooks_on())
+        if (const long hook = ec_test_value(getenv("FMD_ECFIX_TEST_TRACE"), 16)) cap = (uint32_t)hook;
     EcBuf B(t);
     void *ds = B.get(0, total + 16), *dq = B.get(1, total + 16), *doff = B.get(2, (n + 1) * 8), *dinfo = B.get(3, n * 4);
     if (!ds || !dq || !doff || !dinfo) return FMD_E_NOMEM;

@@ -111,6 +111,7 @@ typedef struct { uint64_t x, y; } st_t;
 typedef struct {
     st_t *heap; size_t hn, hm;
     uint64_t *stack; size_t sn, sm;
+    size_t max_hn, max_sn;   /* statistics (orc_ecfix_batch_ex): the largest heap.n / stack.n seen right after a push */
 } fix_t;
 
 static inline int st_lt(const st_t *a, const st_t *b) { return (int64_t)a->y > (int64_t)b->y; } /* mag.c:22 */
@@ -140,11 +141,13 @@ static void push_stack(fix_t *f, uint64_t v)
 {
     if (f->sn == f->sm) { f->sm = f->sm ? f->sm << 1 : 256; f->stack = (uint64_t *)realloc(f->stack, f->sm * 8); }
     f->stack[f->sn++] = v;
+    if (f->sn > f->max_sn) f->max_sn = f->sn;
 }
 static void push_heap(fix_t *f, st_t v)
 {
     if (f->hn == f->hm) { f->hm = f->hm ? f->hm << 1 : 256; f->heap = (st_t *)realloc(f->heap, f->hm * sizeof(st_t)); }
     f->heap[f->hn++] = v;
+    if (f->hn > f->max_hn) f->max_hn = f->hn;
 }
 static void save_state(fix_t *f, const st_t *p, int c, int score, int shift, int has_match)
 {
@@ -268,8 +271,13 @@ void *orc_ectab_new(int suf_len, uint64_t n, const uint32_t *bucket, const uint3
 void orc_ectab_free(void *t) { if (t) { solid_free((solid_t *)t); free(t); } }
 
 /* ec_fix (correct.c:232-246) for n reads: seqs = nt6 codes, quals = phred + 33, read i = bytes [off[i], off[i+1]);
- * both rewritten in place, info[i] = the value at correct.c:246 (before the lower-case count). */
-void orc_ecfix_batch(void *tab, int w, int step, size_t n, uint8_t *seqs, uint8_t *quals, const uint64_t *off, int32_t *info)
+ * both rewritten in place, info[i] = the value at correct.c:246 (before the lower-case count).
+ * The _ex form also reports, per read and as the maximum over its two ec_fix1 passes, the largest number of entries the
+ * trace (stack.n, the root included) and the queue (heap.n) held right after a push (0: the read was never seeded) -- what a
+ * test needs to prove that its inputs reach the GPU kernel's spilled queue, its budget rule and its trace capacity.  Either
+ * pointer may be null. */
+void orc_ecfix_batch_ex(void *tab, int w, int step, size_t n, uint8_t *seqs, uint8_t *quals, const uint64_t *off, int32_t *info,
+                        uint32_t *max_stack, uint32_t *max_heap)
 {
     fix_t fa;
     uint64_t n_query = 0;
@@ -279,6 +287,7 @@ void orc_ecfix_batch(void *tab, int w, int step, size_t n, uint8_t *seqs, uint8_
         char *s = (char *)seqs + off[i], *q = (char *)quals + off[i];
         const int l = (int)(off[i + 1] - off[i]);
         int ret0, ret1;
+        fa.max_hn = fa.max_sn = 0;
         revcomp(l, s); rev(l, q);
         ret0 = ec_fix1(w, step, (const solid_t *)tab, l, s, q, &fa, &n_query);
         rev(l, q); revcomp(l, s);
@@ -287,6 +296,12 @@ void orc_ecfix_batch(void *tab, int w, int step, size_t n, uint8_t *seqs, uint8_
             info[i] = ((ret0 & 0xffff) + (ret1 & 0xffff)) | (ret0 >> 18 < ret1 >> 18 ? ret0 >> 18 : ret1 >> 18) << 18;
             if ((ret0 >> 17 & 1) && (ret1 >> 17 & 1)) info[i] |= 1 << 16;
         } else info[i] = ret0;
+        if (max_stack) max_stack[i] = (uint32_t)fa.max_sn;
+        if (max_heap) max_heap[i] = (uint32_t)fa.max_hn;
     }
     free(fa.heap); free(fa.stack);
+}
+void orc_ecfix_batch(void *tab, int w, int step, size_t n, uint8_t *seqs, uint8_t *quals, const uint64_t *off, int32_t *info)
+{
+    orc_ecfix_batch_ex(tab, w, step, n, seqs, quals, off, info, 0, 0);
 }

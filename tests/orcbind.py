@@ -71,6 +71,7 @@ def lib():
         L.orc_ectab_new.argtypes = [C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.orc_ectab_free.argtypes = [C.c_void_p]
         L.orc_ecfix_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.orc_ecfix_batch_ex.argtypes = L.orc_ecfix_batch.argtypes + [C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -247,20 +248,37 @@ class OrcIndex:
         return out, cnt
 
 
-def ec_fix(w, bucket, key, val, seqs_nt6, quals, step=5):
-    """ec_fix (correct.c:232-246) of a list of reads against a (bucket, key, val) table: lists of corrected nt6 arrays
-    and qualities (phred + 33 bytes) and the info array -- the contract of fmd_ecfix_batch (include/fmd_hip.h)."""
-    L = lib()
-    suf_len = w - 15 if w > 15 else 1
+def ec_tab_new(w, bucket, key, val):
+    """the oracle's table of (bucket, key, val) triples for ec_fix(tab=...): kept by the caller, freed with ec_tab_free"""
     bucket = np.ascontiguousarray(bucket, dtype=np.uint32); key = np.ascontiguousarray(key, dtype=np.uint32); val = np.ascontiguousarray(val, dtype=np.uint8)
-    t = L.orc_ectab_new(suf_len, len(key), bucket.ctypes.data, key.ctypes.data, val.ctypes.data)
+    t = lib().orc_ectab_new(w - 15 if w > 15 else 1, len(key), bucket.ctypes.data, key.ctypes.data, val.ctypes.data)
     assert t
+    return t
+
+
+def ec_tab_free(t):
+    lib().orc_ectab_free(t)
+
+
+def ec_fix(w, bucket, key, val, seqs_nt6, quals, step=5, stats=False, tab=None):
+    """ec_fix (correct.c:232-246) of a list of reads against a (bucket, key, val) table: lists of corrected nt6 arrays
+    and qualities (phred + 33 bytes) and the info array -- the contract of fmd_ecfix_batch (include/fmd_hip.h).
+    stats=True: two more arrays, per read the largest trace (stack.n, root included) and the largest queue (heap.n)
+    right after a push, over both strands (orc_ecfix_batch_ex).  tab: the triples' table from ec_tab_new, for many calls."""
+    L = lib()
+    t = tab if tab is not None else ec_tab_new(w, bucket, key, val)
     n = len(seqs_nt6)
     off = np.zeros(n + 1, dtype=np.uint64)
     np.cumsum([len(x) for x in seqs_nt6], out=off[1:])
     s = np.concatenate([np.asarray(x, dtype=np.uint8) for x in seqs_nt6] + [np.zeros(8, np.uint8)])
     q = np.concatenate([np.asarray(x, dtype=np.uint8) for x in quals] + [np.zeros(8, np.uint8)])
     info = np.zeros(n, dtype=np.int32)
-    L.orc_ecfix_batch(t, w, step, n, s.ctypes.data, q.ctypes.data, off.ctypes.data, info.ctypes.data)
-    L.orc_ectab_free(t)
-    return s[: int(off[n])], q[: int(off[n])], off, info
+    tmax = np.zeros(n, dtype=np.uint32); hmax = np.zeros(n, dtype=np.uint32)
+    if stats:
+        L.orc_ecfix_batch_ex(t, w, step, n, s.ctypes.data, q.ctypes.data, off.ctypes.data, info.ctypes.data, tmax.ctypes.data, hmax.ctypes.data)
+    else:
+        L.orc_ecfix_batch(t, w, step, n, s.ctypes.data, q.ctypes.data, off.ctypes.data, info.ctypes.data)
+    if tab is None:
+        ec_tab_free(t)
+    out = (s[: int(off[n])], q[: int(off[n])], off, info)
+    return out + (tmax, hmax) if stats else out

@@ -494,12 +494,10 @@ def test_ecfix_kernel_equals_oracle_and_fermi_correct(gpu, gold, oracle_lib, ste
         assert finish_correct([r[1] for r in recs], *g) == gold.text_gz("tiny.ec.fq.gz")
 
 
-def test_ecfix_kernel_odd_reads_vs_oracle(gpu, gold, oracle_lib):
-    """Reads the fixture does not hold: shorter than k, all N, Ns near either end (a strand without a clean k-mer), very
-    low and very high qualities, reads of other genomes (every look-up misses: the longest searches, trace re-runs)."""
-    v = gold.npz("tiny_solid.npz")
+def _odd_reads(base):
+    """600 reads made of the reads `base` that the fixture does not hold: shorter than k, all N, Ns near either end (a strand without a
+    clean k-mer), very low and very high qualities, reads of other genomes, reads of 300 bases -> (reads, qualities)"""
     rng = np.random.default_rng(7)
-    base = gold.fastq_nt6("tiny.fq.gz")
     seqs, quals = [], []
     for i in range(600):
         r = base[i % len(base)].copy()
@@ -514,6 +512,14 @@ def test_ecfix_kernel_odd_reads_vs_oracle(gpu, gold, oracle_lib):
         elif kind == 7: r = np.concatenate([r, r[::-1], r])            # 300 bases
         q = rng.integers(33, 33 + 45, size=len(r)).astype(np.uint8) if kind % 2 else np.full(len(r), 33 + (2 if kind == 8 else 30), dtype=np.uint8)
         seqs.append(r); quals.append(q)
+    return seqs, quals
+
+
+def test_ecfix_kernel_odd_reads_vs_oracle(gpu, gold, oracle_lib):
+    """Reads the fixture does not hold: shorter than k, all N, Ns near either end (a strand without a clean k-mer), very
+    low and very high qualities, reads of other genomes (every look-up misses: the longest searches, trace re-runs)."""
+    v = gold.npz("tiny_solid.npz")
+    seqs, quals = _odd_reads(gold.fastq_nt6("tiny.fq.gz"))
     for step in (5, 0):
         g = _ecfix_gpu(gpu, 17, v["w17_o3_bucket"], v["w17_o3_key"], v["w17_o3_val"], seqs, quals, step)
         w = orcbind.ec_fix(17, v["w17_o3_bucket"], v["w17_o3_key"], v["w17_o3_val"], seqs, quals, step)

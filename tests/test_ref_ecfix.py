@@ -29,6 +29,17 @@ def _sorted_trip(v):
     return (np.ascontiguousarray(v["w17_o3_bucket"][o], dtype=np.uint32), np.ascontiguousarray(v["w17_o3_key"][o], dtype=np.uint32), np.ascontiguousarray(v["w17_o3_val"][o], dtype=np.uint8))
 
 
+def suf_len_of(w):
+    return w - 15 if w > 15 else 1
+
+
+def _trip_of(tabs, w):
+    """the table of k-mer length w among `tabs` (tiny_solid.npz's, tiny_refec_fix_params.npz's), sorted by bucket as refec_fix wants it"""
+    tag = [k[:-7] for k in tabs if k.startswith("w%d_o" % w) and k.endswith("_bucket")][0]
+    o = np.argsort(tabs[tag + "_bucket"], kind="stable")
+    return tuple(np.ascontiguousarray(tabs[tag + "_" + f][o], dtype=dt) for f, dt in (("bucket", np.uint32), ("key", np.uint32), ("val", np.uint8)))
+
+
 def _kept_records(text):
     return {int(r[0].lstrip(b"@").split(b"_")[0]): (r[0].lstrip(b"@"), r[1], r[2]) for r in _fastq_records(text)}
 
@@ -77,3 +88,57 @@ def test_marking_rule_in_numpy_equals_the_reference(gold, oracle_lib):
     m_txt, m_q, m_inf = bench.mark_corrected(nt6, s.reshape(nt6.shape), qq.reshape(nt6.shape), inf)
     assert np.array_equal(m_txt, want["text"]) and np.array_equal(m_q, want["qual"]) and np.array_equal(m_inf, want["info"])
     assert (m_txt >= ord("a")).sum() > 1000 and (m_inf >> 16 & 1).sum() > 100
+
+
+# (k-mer length, step) beyond the w 17 / step 5 of tiny_refec_fix.npz: the other two golden tables, step 1 (no hop), 8 (the full mask of the kernel's
+# batched hop) and 12 (beyond it), and the two ends of the k-mer lengths the table builder accepts below and at the reference's MAX_KMER
+PARAM_CASES = [(21, 5), (23, 2), (17, 1), (17, 8), (17, 12), (11, 5), (27, 5)]
+
+
+def _param_inputs(gold):
+    """every fourth read of _marking_inputs: 500 reads of tiny.fq and 100 of those the filter rejects"""
+    nt6, q = _marking_inputs(gold)
+    return np.ascontiguousarray(nt6[::4]), np.ascontiguousarray(q[::4])
+
+
+@pytest.mark.parametrize("w,step", PARAM_CASES)
+def test_oracle_ecfix_at_other_k_and_step(gold, oracle_lib, w, step):
+    """the oracle's ec_fix + bench.mark_corrected == the reference's ec_fix at other k-mer lengths and steps (tests/golden/make_ref_ecfix_params.py;
+    the reference itself is run as well where oracle/_ref was built); the oracle's ec_collect gives the stored tables of w 11 and 27"""
+    want = gold.npz("tiny_refec_fix_params.npz")
+    tabs = gold.npz("tiny_solid.npz")
+    tabs.update({k: a for k, a in want.items() if k.endswith(("_bucket", "_key", "_val"))})
+    B, K, V = _trip_of(tabs, w)
+    nt6, q = _param_inputs(gold)
+    tag = "w%d_s%d_" % (w, step)
+    if bench.ref_ec_lib() is not None:
+        (txt, q2, info), _, _, _, kind, _ = bench.cpu_ecfix(w, suf_len_of(w), step, (B, K, V), nt6, q)
+        assert kind == "reference" and np.array_equal(txt, want[tag + "text"]) and np.array_equal(q2, want[tag + "qual"]) and np.array_equal(info, want[tag + "info"])
+    s, qq, off, inf = orcbind.ec_fix(w, B, K, V, list(nt6), list(q), step)
+    m_txt, m_q, m_inf = bench.mark_corrected(nt6, s.reshape(nt6.shape), qq.reshape(nt6.shape), inf)
+    assert np.array_equal(m_txt, want[tag + "text"]) and np.array_equal(m_q, want[tag + "qual"]) and np.array_equal(m_inf, want[tag + "info"])
+    assert (m_txt >= ord("a")).sum() > 250 and (m_inf >> 16 & 1).sum() > 25      # (a quarter of the floors of the test above)
+    if w in (11, 27):
+        o = orcbind.OrcIndex(gold.path("tiny.fmd"))
+        ob, ok, ov, _ = o.ec_range(w, 3, suf_len_of(w), 0, 1 << (2 * suf_len_of(w)), 2)
+        o.close()
+        srt = np.lexsort([ov, ok, ob])
+        assert np.array_equal(ob[srt], B) and np.array_equal(ok[srt], K) and np.array_equal(ov[srt], V) and len(B) > 10000
+
+
+def test_oracle_ecfix_statistics_form_changes_nothing(gold, oracle_lib):
+    """orc_ecfix_batch_ex == orc_ecfix_batch on bases, qualities and info; its two numbers per read are what they say: 0 for a read that is never
+    seeded, at least 2 entries of trace (the root and one choice) for every other read, a queue within the budget of correct.c:114 plus one expansion"""
+    nt6, q = _marking_inputs(gold)
+    v = gold.npz("tiny_solid.npz")
+    nt6 = list(nt6) + [nt6[0][:17], nt6[1][:5]]
+    q = list(q) + [q[0][:17], q[1][:5]]
+    for step in (5, 0):
+        a = orcbind.ec_fix(17, v["w17_o3_bucket"], v["w17_o3_key"], v["w17_o3_val"], nt6, q, step)
+        b = orcbind.ec_fix(17, v["w17_o3_bucket"], v["w17_o3_key"], v["w17_o3_val"], nt6, q, step, stats=True)
+        assert len(b) == 6 and all(np.array_equal(x, y) for x, y in zip(a, b[:4]))
+        tmax, hmax = b[4], b[5]
+        unseeded = a[3] == 0xffff
+        assert unseeded[-2:].all() and unseeded.sum() < 500
+        assert (tmax[unseeded] == 0).all() and (hmax[unseeded] == 0).all()
+        assert (tmax[~unseeded] >= 2).all() and (hmax[~unseeded] >= 1).all() and hmax.max() <= 257 and tmax.max() >= 256   # (256: past the first allocation of the oracle's stack)
