@@ -44,6 +44,7 @@ ABI_SYMBOLS = [
     "fmd_fltuniq_open", "fmd_fltuniq_slot", "fmd_fltuniq_count", "fmd_fltuniq_test", "fmd_fltuniq_sync", "fmd_fltuniq_export", "fmd_fltuniq_close",
     "fmd_fltuniq_batch_limits",
     "fmd_scaf_links_work_bytes", "fmd_scaf_links_dev", "fmd_scaf_links",
+    "fmd_multi_bsearch_work_bytes", "fmd_multi_bsearch_dev", "fmd_multi_bsearch_batch",
 ]
 
 
@@ -119,6 +120,9 @@ def _configure(L):
     L.fmd_extend_batch.argtypes = [vp, sz, vp, vp, vp]
     L.fmd_bsearch_dev.argtypes = [vp, vp, sz, vp, u64p, u64p, u64p, u64p]
     L.fmd_bsearch_batch.argtypes = [vp, sz, vp, u64p, u64p, u64p, u64p]
+    L.fmd_multi_bsearch_work_bytes.restype = sz; L.fmd_multi_bsearch_work_bytes.argtypes = [C.c_int, sz]
+    L.fmd_multi_bsearch_dev.argtypes = [C.c_int, vp, vp, sz, vp, u64p, u64p, u64p, u64p, vp, sz]
+    L.fmd_multi_bsearch_batch.argtypes = [C.c_int, vp, sz, vp, u64p, u64p, u64p, u64p]
     L.fmd_retrieve_dev.argtypes = [vp, vp, sz, u64p, vp, C.c_uint32, vp, u64p]
     L.fmd_retrieve_batch.argtypes = [vp, sz, u64p, vp, C.c_uint32, vp, u64p]
     L.fmd_build_bwt.argtypes = [C.c_int, sz, vp, u64p, vp, C.POINTER(C.c_uint64)]
@@ -271,9 +275,13 @@ class DevIndex:
 
     # ---- rld_restore (rld.c:288) and friends
     @classmethod
-    def open(cls, fn, device=0):
+    def open(cls, fn, device=0, empty_ok=False):
+        """empty_ok: a file of no symbols opens as an index of no rows (FMD_OPEN_EMPTY_OK), a part for multi_backward_search"""
         h = C.c_void_p()
-        check(lib().fmd_dev_open_file(device, fn.encode(), C.byref(h)))
+        if empty_ok:
+            check(lib().fmd_dev_open_file_ex(device, fn.encode(), FMD_OPEN_EMPTY_OK, C.byref(h)))
+        else:
+            check(lib().fmd_dev_open_file(device, fn.encode(), C.byref(h)))
         return cls(h)
 
     @classmethod
@@ -396,6 +404,21 @@ class DevIndex:
             l = min(int(ln[i]), stride)
             out[i, :l] = seqs[i, :l][::-1]
         return out, ln.astype(np.int32), rank
+
+
+FMD_MULTI_MAX = 16   # include/fmd_hip.h
+FMD_OPEN_EMPTY_OK = 4
+
+
+def multi_backward_search(indexes, seqs):
+    """fm_multi_backward_search (exact.c:25-57) for each read: (cnt, beg, end) in the MERGED index of `indexes` (DevIndex objects on one GPU, in
+    merge order; the same one may appear twice), computed from the parts -- nothing is merged.  A miss is cnt = beg = end = 0."""
+    flat, off = flatten_reads(seqs)
+    n = len(off) - 1
+    hs = (C.c_void_p * max(len(indexes), 1))(*[d.h for d in indexes])
+    cnt = np.zeros(n, dtype=np.uint64); beg = np.zeros(n, dtype=np.uint64); end = np.zeros(n, dtype=np.uint64)
+    check(lib().fmd_multi_bsearch_batch(len(indexes), hs, n, _ptr(flat), _ptr(off), _ptr(cnt), _ptr(beg), _ptr(end)))
+    return cnt, beg, end
 
 
 def _ovlp(self, ids, min_match, max_len=100, max_nei=4, check_left=True):

@@ -213,7 +213,7 @@ __global__ void k_ptab_level(FmdIndexView ix, int d, const uint4 *__restrict__ p
     if (i >= (1ull << (2 * d))) return;
     const int c = (int)(i >> (2 * (d - 1))) + 1;
     uint64_t k, l;
-    if (d == 1) { k = ix.cnt[c]; l = ix.cnt[c + 1] - 1; }
+    if (d == 1) { k = ix.cnt[c]; l = ix.cnt[c + 1]; if (k < l) --l; else { k = 1; l = 0; } }   // (cnt[c + 1] = 0 in an empty index: no l - 1)
     else {
         const uint4 e = prev[i & ((1ull << (2 * (d - 1))) - 1)];
         k = (uint64_t)e.y << 32 | e.x; l = (uint64_t)e.w << 32 | e.z;
@@ -305,11 +305,12 @@ static int scan_u64(uint64_t *d_in, uint64_t *d_out, uint64_t n, hipStream_t st)
     return fmd_with_tmp(st, true, "scan", [&](void *tmp, size_t &bytes) { return fmd_exclusive_sum(tmp, bytes, d_in, d_out, (size_t)n, st); });
 }
 
-static int dev_alloc_index(int device, uint64_t n_sym, fmd_dev **out)
+// empty_ok: n_sym = 0 gives the pad block alone (FMD_OPEN_EMPTY_OK)
+static int dev_alloc_index(int device, uint64_t n_sym, fmd_dev **out, bool empty_ok = false)
 {
     int ndev = fmd_device_count();
     if (ndev <= 0 || device < 0 || device >= ndev) return FMD_E_NODEV;
-    if (n_sym == 0 || n_sym >= (1ull << 40)) return FMD_E_ARG; // 40-bit absolute counts
+    if ((n_sym == 0 && !empty_ok) || n_sym >= (1ull << 40)) return FMD_E_ARG; // 40-bit absolute counts
     if ((n_sym + FMD_BLK_STRIDE - 1) / FMD_BLK_STRIDE + 1 >= 0xffffffffull) return FMD_E_ARG; // 32-bit block numbers
     FMD_HIP_TRY(hipSetDevice(device));
     hipDeviceProp_t prop;
@@ -466,7 +467,7 @@ static int open_rle6(int device, const uint8_t *runs, uint64_t n_bytes, int tabl
 extern "C" int fmd_dev_open_rle6(int device, const uint8_t *runs, uint64_t n_bytes, fmd_dev_t **out) { return open_rle6(device, runs, n_bytes, 1, out); }
 
 // The payload words of an RLD\2 file, already in device memory ((n_words / 8 + 1) * 64 bytes, zero behind the payload): the index.  Takes w over.
-static int open_rld_words_dev(int device, FmdDevBuf w_b, uint64_t n_words, const uint64_t mcnt[7], int tables, fmd_dev_t **out)
+static int open_rld_words_dev(int device, FmdDevBuf w_b, uint64_t n_words, const uint64_t mcnt[7], int tables, fmd_dev_t **out, bool empty_ok = false)
 {
     // blocks 0 .. last/8-1 carry payload; the block at word `last` is header-only (rld.h:64)
     const uint64_t n_rld = n_words / 8;
@@ -477,7 +478,7 @@ static int open_rld_words_dev(int device, FmdDevBuf w_b, uint64_t n_words, const
     hipMemset(d_tot, 0, 16);
     k_rld_sizes<<<fmd_nblk(n_rld, 256), 256>>>(d_w, n_rld, d_size);
     FMD_TRY(scan_u64(d_size, d_start, n_rld, 0));
-    FMD_TRY(dev_alloc_index(device, mcnt[0], &h));
+    FMD_TRY(dev_alloc_index(device, mcnt[0], &h, empty_ok));
     h->mcnt[0] = mcnt[0];
     k_rld_scatter<<<fmd_nblk(n_rld, 64), 64>>>(d_w, n_rld, d_start, (uint32_t *)h->blocks, mcnt[0], d_tot);
     uint64_t tot[2] = {0, 0};
@@ -541,7 +542,7 @@ static int upload_payload(int device, int fd, off_t at, uint64_t bytes, uint8_t 
 // .fmd file: header = "RLD\2", u32 asize<<16|sbits, u64 0, u64 n_bytes, u64 n_frames, u64 mcnt[1..6]
 // (rld.c:242-263); anything else is treated as a raw run-length byte stream after a 4-byte
 // magic, as rld_restore does (rld.c:295-308).
-static int open_file(int device, const char *fn, int tables, fmd_dev_t **out)
+static int open_file(int device, const char *fn, int tables, bool empty_ok, fmd_dev_t **out)
 {
     if (!fn || !out) return FMD_E_ARG;
     FILE *fp = fopen(fn, "rb");
@@ -575,7 +576,7 @@ static int open_file(int device, const char *fn, int tables, fmd_dev_t **out)
             rc = upload_payload(device, fileno(fp), at, n_words * 8, w.as<uint8_t>());
             fclose(fp); // the rank frames that follow are not needed: the device layout has none
             if (rc) return rc;
-            return open_rld_words_dev(device, std::move(w), n_words, mcnt, tables, out);
+            return open_rld_words_dev(device, std::move(w), n_words, mcnt, tables, out, empty_ok);
         }
     } else {
         fseek(fp, 0, SEEK_END);
@@ -591,12 +592,14 @@ static int open_file(int device, const char *fn, int tables, fmd_dev_t **out)
         return rc;
     }
 }
-extern "C" int fmd_dev_open_file(int device, const char *fn, fmd_dev_t **out) { return open_file(device, fn, 1, out); }
-// the same without the prefix and tail tables (FMD_OPEN_NO_TABLES): an index that is only ranked and decoded -- the inputs of a merge
+extern "C" int fmd_dev_open_file(int device, const char *fn, fmd_dev_t **out) { return open_file(device, fn, 1, false, out); }
+// the same without the prefix and tail tables (FMD_OPEN_NO_TABLES): an index that is only ranked and decoded -- the inputs of a merge;
+// FMD_OPEN_EMPTY_OK: an RLD\2 file of no symbols (what `sub` writes when nothing is kept) becomes a handle of the pad block alone, all counts 0 --
+// a part of fmd_multi_bsearch_*
 extern "C" int fmd_dev_open_file_ex(int device, const char *fn, unsigned flags, fmd_dev_t **out)
 {
-    if (flags & ~FMD_OPEN_NO_TABLES) return FMD_E_ARG;
-    return open_file(device, fn, !(flags & FMD_OPEN_NO_TABLES), out);
+    if (flags & ~(FMD_OPEN_NO_TABLES | FMD_OPEN_EMPTY_OK)) return FMD_E_ARG;
+    return open_file(device, fn, !(flags & FMD_OPEN_NO_TABLES), (flags & FMD_OPEN_EMPTY_OK) != 0, out);
 }
 extern "C" int fmd_dev_open_bwt_ex(int device, const uint8_t *bwt, uint64_t n, unsigned flags, fmd_dev_t **out)
 {

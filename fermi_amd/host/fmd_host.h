@@ -370,6 +370,9 @@ int fmdh_main_cnt2qual(int argc, char *argv[]);
 /* ropebwt_cmd.c: `fermi ropebwt` (ropebwt.c:47-158), the index builder of the driver script: one strand or both (fmd_build_bwt_strands), the BWT as text
  * or as RLE\6 runs; -g GPU.  Looks at its arguments first, then for the device. */
 int fmdh_main_ropebwt(int argc, char *argv[]);
+/* msearch_cmd.c: `fermi-amd msearch [-g dev] <query.fa> <a.fmd> [<b.fmd> ...]`: count and SA interval of every query in the merged index of the files, from
+ * the files as they are (fmd_multi_bsearch_batch; fm_multi_backward_search exact.c:25-57); usage and unreadable-file errors return 1 before the device is looked for */
+int fmdh_main_msearch(int argc, char *argv[]);
 int fmdh_fltuniq_auto_k(long long file_bytes);   /* the k `fltuniq` takes for an input file of that many bytes on disk (seq.c:147-150) */
 
 /* `fermi correct` (cmd.c:253-291, correct.c:305-456); defaults = cmd.c:258 */

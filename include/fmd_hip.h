@@ -68,6 +68,10 @@ int fmd_dev_open_bwt_dev(int device, const uint8_t *d_bwt, uint64_t n, fmd_dev_t
  * only ranked and decoded -- the inputs of fmd_dev_merge -- needs neither, and at 2^31 symbols and more they are 4.3 GB + 8 bytes
  * per sequence.  Every entry point works on such a handle; the overlap and search jobs take the steps the tables would save. */
 #define FMD_OPEN_NO_TABLES 1u
+/* FMD_OPEN_EMPTY_OK: an RLD\2 file of no symbols (the 216 bytes `sub` writes when nothing is kept; rld_restore reads it) is opened as a
+ * handle of no rows, all counts 0, instead of FMD_E_ARG.  Such a handle is a part for fmd_multi_bsearch_* -- a lane of the driver that got
+ * no reads -- and for fmd_dev_info / fmd_dev_close; every other job assumes at least one sequence and must not be given it.  (2u is no flag.) */
+#define FMD_OPEN_EMPTY_OK 4u
 int fmd_dev_open_file_ex(int device, const char *fn, unsigned flags, fmd_dev_t **out);
 int fmd_dev_open_bwt_ex(int device, const uint8_t *bwt, uint64_t n, unsigned flags, fmd_dev_t **out);
 void fmd_dev_close(fmd_dev_t *h);
@@ -104,6 +108,20 @@ int fmd_bsearch_dev(fmd_dev_t *h, void *stream, size_t n, const uint8_t *d_seqs,
                     uint64_t *d_cnt, uint64_t *d_beg, uint64_t *d_end);
 int fmd_bsearch_batch(fmd_dev_t *h, size_t n, const uint8_t *seqs, const uint64_t *off,
                       uint64_t *cnt, uint64_t *beg, uint64_t *end);
+
+/* ---- fm_multi_backward_search (exact.c:25-57): backward search over n_idx indexes at once ---------
+ * The SA interval each read has in the MERGED index of h[0], h[1], .. (fm_merge, in that order), from the parts alone: nothing is merged, no
+ * second copy is held.  Reads and results as fmd_bsearch_dev (cnt[i] = 0: a miss, beg/end written as 0; the read bytes 4-byte aligned and
+ * readable to the next multiple of 4).  All handles on one device; the same handle may be given twice; at most FMD_MULTI_MAX of them.
+ * Two-base blocks on a handle are not used.  The _dev form enqueues on `stream` and returns: it neither allocates nor synchronises, and takes
+ * a work area of fmd_multi_bsearch_work_bytes(n_idx, n) bytes, 16-byte aligned (0 for an n_idx out of range).
+ * FMD_E_ARG: n_idx < 1, n_idx > FMD_MULTI_MAX, a null handle, handles on different devices, a work area too small.  n = 0 is a no-op. */
+#define FMD_MULTI_MAX 16
+size_t fmd_multi_bsearch_work_bytes(int n_idx, size_t n);
+int fmd_multi_bsearch_dev(int n_idx, fmd_dev_t *const *h, void *stream, size_t n, const uint8_t *d_seqs, const uint64_t *d_off,
+                          uint64_t *d_cnt, uint64_t *d_beg, uint64_t *d_end, void *d_work, size_t work_bytes);
+int fmd_multi_bsearch_batch(int n_idx, fmd_dev_t *const *h, size_t n, const uint8_t *seqs, const uint64_t *off,
+                            uint64_t *cnt, uint64_t *beg, uint64_t *end);
 
 /* ---- fm_retrieve (exact.c:59-70): LF-walk from row x[i] until '$' --------------------------
  * Row i of seqs (stride bytes) receives the sequence REVERSED, exactly as fm_retrieve emits it
