@@ -611,8 +611,7 @@ extern "C" int fmd_builder_add_dev(fmd_builder_t *b, void *stream, uint64_t n, c
     FMD_HIP_TRY(hipSetDevice(b->device));
     k_text4_add<<<fmd_nblk(n * ((uint64_t)b->len + 1), 256), 256, 0, (hipStream_t)stream>>>(n, b->len, b->added, d_reads, b->text4);
     b->added += n;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { fmd_set_hip_error(e, "k_text4_add"); return FMD_E_HIP; }
+    FMD_CHECK_LAUNCH("k_text4_add");
     return FMD_OK;
 }
 extern "C" int fmd_builder_finish(fmd_builder_t *b, fmd_dev_t **out)

@@ -838,8 +838,7 @@ extern "C" int fmd_ecfix_dev(fmd_ectab_t *t, void *stream_, size_t n, uint8_t *d
     uint64_t *traces = (uint64_t *)(heaps + (size_t)grid * 64 * EC_HEAP_SLOTS);
     FMD_HIP_TRY(hipMemsetAsync(t->queue, 0, 4, st));
     k_ecfix<<<grid, 64, 0, st>>>(n, d_seqs, d_quals, d_off, t->w, step, t->slots, t->n_slots - 1, d_info, heaps, traces, trace_cap, t->queue);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { fmd_set_hip_error(e, "k_ecfix"); return FMD_E_HIP; }
+    FMD_CHECK_LAUNCH("k_ecfix");
     return FMD_OK;
 }
 

@@ -57,6 +57,13 @@ struct fmd_dev {
 
 #define FMD_TRY(expr) do { int rc__ = (expr); if (rc__) return rc__; } while (0)   // an FMD_* code
 
+// after kernel launches: what the runtime says of them, recorded under `what`; FMD_E_HIP whatever the error (FMD_HIP_TRY maps out-of-memory)
+#define FMD_CHECK_LAUNCH(what)                                  \
+    do {                                                        \
+        hipError_t e__ = hipGetLastError();                     \
+        if (e__ != hipSuccess) { fmd_set_hip_error(e__, what); return FMD_E_HIP; } \
+    } while (0)
+
 static inline FmdIndexView fmd_view(const fmd_dev *h)
 {
     FmdIndexView v;

@@ -7,6 +7,8 @@
 
 __device__ __forceinline__ int comp6(int c) { return (c >= 1 && c <= 4) ? 5 - c : c; }
 
+#include "fmd_search.h"   // the read window, the prefix-table start and the result triple of the backward-search kernels
+
 template <class T>
 __device__ __forceinline__ T sel6(int c, T a0, T a1, T a2, T a3, T a4, T a5)
 {

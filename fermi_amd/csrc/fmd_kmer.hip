@@ -359,8 +359,7 @@ extern "C" int fmd_kmer_collect_part_dev(fmd_dev_t *h, void *stream_, int w, int
     FMD_HIP_TRY(fmd_exclusive_sum(tail, tmp_bytes, tile_cnt, tile_off, (size_t)n_tiles, st));
     k_km_scatter<<<(unsigned)n_tiles, 256, 0, st>>>(r_flag, cap, tile_off, tile_cnt, n_tiles, r_bucket, r_key, r_val, d_bucket, d_key, d_val, ctr);
     FMD_HIP_TRY(hipMemcpyAsync(d_status, ctr + KM_OUT, 4 * 8, hipMemcpyDeviceToDevice, st));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { fmd_set_hip_error(e, "kmer kernels"); return FMD_E_HIP; }
+    FMD_CHECK_LAUNCH("kmer kernels");
     return FMD_OK;
 }
 

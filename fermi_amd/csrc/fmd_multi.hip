@@ -37,36 +37,6 @@ __global__ void k_multi_put_view(FmdMultiView v, FmdMultiView *__restrict__ dst)
     if (threadIdx.x == 0) *dst = v;
 }
 
-// fmd_wave_rank2_fetch_compact without its wait: the gathers of the lane's two blocks (k side: dense slot; l side: pool, when another block) are posted.
-__device__ __forceinline__ FmdRank2c fmd_multi_post(const FmdIndexView &ix, uint4 *lds, uint64_t k, uint64_t l)
-{
-    const int q = fmd_lane();
-    FmdRank2c r;
-    r.hk = k != ~0ull; r.hl = l != ~0ull;
-    uint32_t ok_, ol_;
-    fmd_split(k, r.blk_k, ok_);
-    fmd_split(l, r.blk_l, ol_);
-    fmd_l_from_k(r.hk && r.hl, l, r.blk_k, r.blk_l, ol_);
-    r.l_sep = r.hl && !(r.hk && r.blk_k == r.blk_l);
-    fmd_fetch_slot<0>(ix, lds, r.blk_k, r.hk);
-    r.t = fmd_chunk_xor(q);
-    r.bk = lds + fmd_lds_base(q, 0);
-    r.bl = r.bk; r.tl = r.t;
-    r.two_phase = false;
-    const uint64_t m = __ballot(r.l_sep);
-    if (m) {
-        uint4 *pool = lds + FMD_SLOT_U4;
-        uint32_t *ids = (uint32_t *)(pool + FMD_POOL_BLOCKS * FMD_BLK_U4);
-        const int p = fmd_below(m);
-        if (r.l_sep) ids[p] = r.blk_l;
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        fmd_fetch_pool(ix, pool, ids, __popcll(m));
-        if (r.l_sep) { r.bl = pool + p * FMD_BLK_U4; r.tl = fmd_pool_xor(p); }
-    }
-    r.nk = ok_ + 1; r.nl = ol_ + 1;
-    return r;
-}
-
 template <int NI>
 __global__ __launch_bounds__(64) void k_multi_bsearch(const FmdMultiView *__restrict__ views, int n_idx, int tab_d, size_t n,
                                                       const uint8_t *__restrict__ seqs, const uint64_t *__restrict__ off,
@@ -89,16 +59,9 @@ __global__ __launch_bounds__(64) void k_multi_bsearch(const FmdMultiView *__rest
     uint64_t k[NI], l[NI];
 #pragma unroll
     for (int j = 0; j < NI; ++j) k[j] = l[j] = 0;
-    uint4 cq = make_uint4(0, 0, 0, 0);                      // the 16 bases around pos, as in k_bsearch: only dwords at or below pos are read
+    FmdReadWindow cq;                                       // the 16 bases around pos, nothing above pos (fmd_search.h)
+    const FmdHitOut out = {d_cnt, d_beg, d_end};
     bool live = false, exhausted = false;
-#define MS_LOAD16(at_)                                                                                           \
-    do {                                                                                                         \
-        const uint64_t a_ = (at_), b_ = a_ & ~15ull, top_ = a_ & ~3ull;                                          \
-        const uint32_t *w_ = (const uint32_t *)(seqs + b_);                                                      \
-        cq.x = w_[0];                                                                                            \
-        cq.y = b_ + 4 <= top_ ? w_[1] : 0u; cq.z = b_ + 8 <= top_ ? w_[2] : 0u; cq.w = b_ + 12 <= top_ ? w_[3] : 0u; \
-    } while (0)
-#define MS_MISS(i_) do { d_cnt[i_] = 0; d_beg[i_] = 0; d_end[i_] = 0; } while (0)
 
     FmdTickets tk_;
     fmd_tickets_init(tk_, queue, 64, n);
@@ -110,35 +73,21 @@ __global__ __launch_bounds__(64) void k_multi_bsearch(const FmdMultiView *__rest
                 if (my < n) {
                     rid = my; sbase = off[my];
                     const int len = (int)(off[my + 1] - sbase);
-                    if (len <= 0) MS_MISS(my);
+                    if (len <= 0) out.miss(my);
                     else {
                         bool from_table = false;
-                        if (tab_d > 0 && len >= tab_d) {
-                            const uint64_t beg = sbase + (uint64_t)(len - tab_d), end = sbase + (uint64_t)len;
-                            uint64_t idx = 0; bool acgt = true;
-                            for (uint64_t a = beg & ~3ull; a < end; a += 4) {
-                                const uint32_t w = *(const uint32_t *)(seqs + a);
+                        uint64_t idx;
+                        if (tab_d > 0 && len >= tab_d && fmd_ptab_fold_back(seqs, sbase + (uint64_t)(len - tab_d), sbase + (uint64_t)len, idx)) {
+                            from_table = true;          // (if every part holds the string: the intervals are the walk's after tab_d bases)
 #pragma unroll
-                                for (int b = 0; b < 4; ++b) {
-                                    const uint32_t c = (w >> (8 * b)) & 0xff;
-                                    if (a + b >= beg && a + b < end) { acgt = acgt && c >= 1 && c <= 4; idx = idx << 2 | ((c - 1) & 3); }
+                            for (int j = 0; j < NI; ++j)
+                                if (j < n_idx) {
+                                    const FmdPtabEntry e = fmd_ptab_unpack(views[j].ptab[idx]);
+                                    { FmdIndexView t_; t_.stat = views[j].stat; fmd_count_lane(t_, 1, 1); }
+                                    k[j] = e.k; l[j] = e.l + 1;
+                                    from_table = from_table && e.present;
                                 }
-                            }
-                            if (acgt) {
-                                bool all = true;
-#pragma unroll
-                                for (int j = 0; j < NI; ++j)
-                                    if (j < n_idx) {
-                                        const uint4 e = views[j].ptab[idx];
-                                        { FmdIndexView t_; t_.stat = views[j].stat; fmd_count_lane(t_, 1, 1); }
-                                        k[j] = (uint64_t)e.y << 32 | e.x;
-                                        const uint64_t el = (uint64_t)e.w << 32 | e.z;
-                                        all = all && k[j] <= el;
-                                        l[j] = el + 1;
-                                    }
-                                from_table = all;       // (every part holds the string: the intervals are the walk's after tab_d bases)
-                                pos = len - tab_d - 1;
-                            }
+                            pos = len - tab_d - 1;
                         }
                         if (!from_table) {
                             int c = seqs[sbase + len - 1];
@@ -150,10 +99,10 @@ __global__ __launch_bounds__(64) void k_multi_bsearch(const FmdMultiView *__rest
                         bool empty = true;
 #pragma unroll
                         for (int j = 0; j < NI; ++j) empty = empty && k[j] == l[j];
-                        if (empty) MS_MISS(my);                     // no part holds the last base
+                        if (empty) out.miss(my);                    // no part holds the last base
                         else {
                             live = true;
-                            if (pos >= 0) MS_LOAD16(sbase + pos);
+                            if (pos >= 0) cq.load(seqs, sbase + pos, sbase + pos);
                         }
                     }
                 } else exhausted = true;
@@ -165,9 +114,7 @@ __global__ __launch_bounds__(64) void k_multi_bsearch(const FmdMultiView *__rest
         bool fin = live && pos < 0;
         int c = 0;
         if (live && !fin) {
-            const uint64_t a = sbase + pos;
-            const uint32_t wq = (uint32_t)(a >> 2) & 3u, cw_ = wq == 0 ? cq.x : wq == 1 ? cq.y : wq == 2 ? cq.z : cq.w;
-            c = (int)((cw_ >> (8 * (a & 3))) & 0xff);
+            c = cq.base(sbase + pos);
             c = c > 5 ? 5 : c;
         }
         const bool step = live && !fin;
@@ -179,12 +126,12 @@ __global__ __launch_bounds__(64) void k_multi_bsearch(const FmdMultiView *__rest
                 FmdRank2c r0, r1;
                 ix0.blocks = views[j0].blocks; ix0.stat = views[j0].stat;
                 // part j: rank21(k - 1, l - 1, c) while its interval is not empty, rank11(k - 1, c) once it is; k = 0: k - 1 is "none" and ranks to 0
-                r0 = fmd_multi_post(ix0, fmd_lds, step ? k[j0] - 1 : NONE64, step && k[j0] != l[j0] ? l[j0] - 1 : NONE64);
+                r0 = fmd_wave_rank2_post_compact(ix0, fmd_lds, step ? k[j0] - 1 : NONE64, step && k[j0] != l[j0] ? l[j0] - 1 : NONE64);
                 const bool two = B == 2 && j0 + 1 < n_idx;
                 if (two) {
                     const int j1 = j0 + 1 < NI ? j0 + 1 : j0;
                     ix1.blocks = views[j1].blocks; ix1.stat = views[j1].stat;
-                    r1 = fmd_multi_post(ix1, fmd_lds + (B - 1) * FMD_COMPACT_LDS_U4, step ? k[j1] - 1 : NONE64, step && k[j1] != l[j1] ? l[j1] - 1 : NONE64);
+                    r1 = fmd_wave_rank2_post_compact(ix1, fmd_lds + (B - 1) * FMD_COMPACT_LDS_U4, step ? k[j1] - 1 : NONE64, step && k[j1] != l[j1] ? l[j1] - 1 : NONE64);
                 }
                 fmd_fetch_wait();
                 if (step) {
@@ -208,22 +155,14 @@ __global__ __launch_bounds__(64) void k_multi_bsearch(const FmdMultiView *__rest
             bool empty = true;
 #pragma unroll
             for (int j = 0; j < NI; ++j) { sk += k[j]; sl += l[j]; empty = empty && k[j] == l[j]; }
-            if (empty) { MS_MISS(rid); live = false; }               // empty in every part: the search ends at once (exact.c:50)
-            else if (pos < 0) { d_cnt[rid] = sl - sk; d_beg[rid] = sk; d_end[rid] = sl - 1; live = false; }   // exact.c:53-56
-            else if (step && ((sbase + pos) & 15) == 15) MS_LOAD16(sbase + pos);
+            if (empty) { out.miss(rid); live = false; }              // empty in every part: the search ends at once (exact.c:50)
+            else if (pos < 0) { out.store(rid, sk, sl - 1); live = false; }   // exact.c:53-56 (not empty: sl > sk)
+            else if (step && ((sbase + pos) & 15) == 15) cq.load(seqs, sbase + pos, sbase + pos);
         }
     }
-#undef MS_LOAD16
-#undef MS_MISS
 }
 
 // ------------------------------------------------------------------------------- host entry
-#define FMD_CHECK_LAUNCH()                                              \
-    do {                                                                \
-        hipError_t e__ = hipGetLastError();                             \
-        if (e__ != hipSuccess) { fmd_set_hip_error(e__, "kernel launch"); return FMD_E_HIP; } \
-    } while (0)
-
 static int multi_check(int n_idx, fmd_dev_t *const *h)
 {
     if (n_idx < 1 || n_idx > FMD_MULTI_MAX || !h) return FMD_E_ARG;
@@ -271,7 +210,7 @@ extern "C" int fmd_multi_bsearch_dev(int n_idx, fmd_dev_t *const *h, void *strea
     else if (n_idx <= 4) multi_launch<4>(h[0], S(stream), views, n_idx, tab_d, n, d_seqs, d_off, d_cnt, d_beg, d_end, q);
     else if (n_idx <= 8) multi_launch<8>(h[0], S(stream), views, n_idx, tab_d, n, d_seqs, d_off, d_cnt, d_beg, d_end, q);
     else multi_launch<FMD_MULTI_MAX>(h[0], S(stream), views, n_idx, tab_d, n, d_seqs, d_off, d_cnt, d_beg, d_end, q);
-    FMD_CHECK_LAUNCH();
+    FMD_CHECK_LAUNCH("kernel launch");
     return FMD_OK;
 }
 

@@ -6,8 +6,6 @@
 #include <string.h>
 #include "fmd_kernel_common.h"
 
-#define NONE64 (~0ull)
-
 // ------------------------------------------------------------------------------ rank kernels
 // rld_rank1a (rld.c:424-446)
 __global__ __launch_bounds__(64) void k_rank1a(FmdIndexView ix, size_t n, const uint64_t *__restrict__ d_k,
@@ -131,20 +129,9 @@ __global__ __launch_bounds__(64) void k_bsearch(FmdIndexView ix, size_t n, const
     uint64_t sbase = 0;           // off[rid]
     int pos = -1;                 // next base to prepend
     uint64_t k = 0, l = 0;
-    // 16 bases of the read around pos: the four dwords of the 16-byte block of the read buffer that holds base pos, fetched together.  A lane
-    // reads its read backwards, one base per step; fetched one dword every fourth step (round 1-3), each of a line's 16 dwords was a request of
-    // its own, four steps after the last -- long enough for the random block traffic of the other waves to have pushed the line out of L2:
-    // the kernel fetched 1.18 x the bytes it asked for, 1 KB per read of refetched read lines (PMC).  Only dwords at or below
-    // pos are loaded (the bases above it are behind us), so nothing beyond what the contract makes readable is touched.
-    uint4 cq = make_uint4(0, 0, 0, 0);
+    FmdReadWindow cq;             // the 16 bases around pos, nothing above pos (fmd_search.h)
+    const FmdHitOut out = {d_cnt, d_beg, d_end};
     bool live = false, exhausted = false;
-#define BS_LOAD16(at_)                                                                                           \
-    do {                                                                                                         \
-        const uint64_t a_ = (at_), b_ = a_ & ~15ull, top_ = a_ & ~3ull;                                          \
-        const uint32_t *w_ = (const uint32_t *)(seqs + b_);                                                      \
-        cq.x = w_[0];                                                                                            \
-        cq.y = b_ + 4 <= top_ ? w_[1] : 0u; cq.z = b_ + 8 <= top_ ? w_[2] : 0u; cq.w = b_ + 12 <= top_ ? w_[3] : 0u; \
-    } while (0)
 
     FmdTickets tk_;
     fmd_tickets_init(tk_, queue, 64, n);   // guided chunks (fmd_wave.h)
@@ -156,32 +143,21 @@ __global__ __launch_bounds__(64) void k_bsearch(FmdIndexView ix, size_t n, const
                 if (my < n && !(MODE == 2 && d_cnt[my] != BS_AGAIN)) {
                     rid = my; sbase = off[my];
                     const int len = (int)(off[my + 1] - sbase);
-                    if (len <= 0) { d_cnt[my] = 0; d_beg[my] = 0; d_end[my] = 0; }
+                    if (len <= 0) out.miss(my);
                     else {
                         // the last ptab_d bases in one table look-up (the top of the search tree, two lines
                         // per step while the interval is wider than a block), when they are all A/C/G/T
                         const int D = ix.ptab_d;
                         bool from_table = false;
-                        if (ix.ptab && len >= D) {
-                            const uint64_t beg = sbase + (uint64_t)(len - D), end = sbase + (uint64_t)len;
-                            uint64_t idx = 0; bool acgt = true;
-                            for (uint64_t a = beg & ~3ull; a < end; a += 4) {
-                                const uint32_t w = *(const uint32_t *)(seqs + a);
-#pragma unroll
-                                for (int b = 0; b < 4; ++b) {
-                                    const uint32_t c = (w >> (8 * b)) & 0xff;
-                                    if (a + b >= beg && a + b < end) { acgt = acgt && c >= 1 && c <= 4; idx = idx << 2 | ((c - 1) & 3); }
-                                }
-                            }
-                            if (acgt) {
-                                const uint4 e = ix.ptab[idx];
-                                fmd_count_lane(ix, 1, 1);
-                                k = (uint64_t)e.y << 32 | e.x; l = (uint64_t)e.w << 32 | e.z;
-                                pos = len - D - 1;
-                                from_table = true;
-                                if (k > l) { d_cnt[my] = 0; d_beg[my] = 0; d_end[my] = 0; } // already a miss
-                                else live = true;
-                            }
+                        uint64_t idx;
+                        if (ix.ptab && len >= D && fmd_ptab_fold_back(seqs, sbase + (uint64_t)(len - D), sbase + (uint64_t)len, idx)) {
+                            const FmdPtabEntry e = fmd_ptab_unpack(ix.ptab[idx]);
+                            fmd_count_lane(ix, 1, 1);
+                            k = e.k; l = e.l;
+                            pos = len - D - 1;
+                            from_table = true;
+                            if (!e.present) out.miss(my); // already a miss
+                            else live = true;
                         }
                         if (!from_table) {
                             const int c = seqs[sbase + len - 1];
@@ -189,7 +165,7 @@ __global__ __launch_bounds__(64) void k_bsearch(FmdIndexView ix, size_t n, const
                             pos = len - 2;
                             live = true;
                         }
-                        if (live && pos >= 0) BS_LOAD16(sbase + pos);
+                        if (live && pos >= 0) cq.load(seqs, sbase + pos, sbase + pos);
                     }
                 } else if (my >= n) exhausted = true;
             }
@@ -197,11 +173,7 @@ __global__ __launch_bounds__(64) void k_bsearch(FmdIndexView ix, size_t n, const
         if (__ballot(live) == 0) { if (__ballot(!exhausted) == 0) break; else continue; }   // (a wave whose lanes all drew reads that need nothing draws again)
 
         // ---- retire lanes that have consumed their whole read (len == 1 lands here directly)
-        if (live && pos < 0) {
-            const bool hit = k <= l;
-            d_cnt[rid] = hit ? l - k + 1 : 0; d_beg[rid] = hit ? k : 0; d_end[rid] = hit ? l : 0;
-            live = false;
-        }
+        if (live && pos < 0) { out.store(rid, k, l); live = false; }
         // ---- MODE 1: narrow, and an even number of bases left: the search goes on in k_bsearch_pair
         if (MODE == 1 && live && pos >= 1 && (pos & 1) && l - k < 64) {
             d_cnt[rid] = BS_HANDED; d_beg[rid] = k; d_end[rid] = (uint64_t)(uint32_t)(pos + 1) << 32 | (l - k + 1);
@@ -211,9 +183,7 @@ __global__ __launch_bounds__(64) void k_bsearch(FmdIndexView ix, size_t n, const
         int c = 0;
         uint64_t qk = NONE64, ql = NONE64;
         if (live) {
-            const uint64_t a = sbase + pos;
-            const uint32_t wq = (uint32_t)(a >> 2) & 3u, cw_ = wq == 0 ? cq.x : wq == 1 ? cq.y : wq == 2 ? cq.z : cq.w;
-            c = (int)((cw_ >> (8 * (a & 3))) & 0xff);
+            c = cq.base(sbase + pos);
             qk = k - 1; ql = l;
         }
         FmdRank2c r = fmd_wave_rank2_fetch_compact(ix, fmd_lds, qk, ql);
@@ -224,16 +194,10 @@ __global__ __launch_bounds__(64) void k_bsearch(FmdIndexView ix, size_t n, const
             k = ix.cnt[c] + ok;
             l = ix.cnt[c] + ol - 1;
             --pos;
-            if (k > l || pos < 0) {
-                const bool hit = k <= l;
-                d_cnt[rid] = hit ? l - k + 1 : 0; d_beg[rid] = hit ? k : 0; d_end[rid] = hit ? l : 0;
-                live = false;
-            } else if (((sbase + pos) & 15) == 15) {
-                BS_LOAD16(sbase + pos);
-            }
+            if (k > l || pos < 0) { out.store(rid, k, l); live = false; }
+            else if (((sbase + pos) & 15) == 15) cq.load(seqs, sbase + pos, sbase + pos);
         }
     }
-#undef BS_LOAD16
 }
 
 // fm_backward_search two bases per request (round 6): for a read handed over by k_bsearch<1>, the interval [k, k + size) and `left` bases (even) to go.
@@ -252,16 +216,9 @@ __global__ __launch_bounds__(64, 5) void k_bsearch_pair(FmdIndexView ix, size_t 
     uint64_t k = 0, sbase = 0, hk = 0, he = 0, hc = 0, ho = 0;
     uint32_t size = 0;
     int pos = -1, st = 0;                 // st: 0 idle, 1 the hand-over record on its way, 2 running
-    uint4 cq = make_uint4(0, 0, 0, 0), cp = cq;      // the 16 bases around pos, and the 16 below them
+    FmdReadWindow cq, cp;                 // the 16 bases around pos, and the 16 below them
+    const FmdHitOut out = {d_cnt, d_beg, d_end};
     bool exhausted = false;
-#define BSP_LOAD16(dst_, at_, top_at_)                                                                           \
-    do {                                                                                                         \
-        const uint64_t b_ = (at_) & ~15ull, top_ = (top_at_) & ~3ull;                                            \
-        const uint32_t *w_ = (const uint32_t *)(seqs + b_);                                                      \
-        dst_.x = w_[0];                                                                                          \
-        dst_.y = b_ + 4 <= top_ ? w_[1] : 0u; dst_.z = b_ + 8 <= top_ ? w_[2] : 0u; dst_.w = b_ + 12 <= top_ ? w_[3] : 0u; \
-    } while (0)
-#define BSP_BASE(a_, win_) ({ const uint32_t wq_ = (uint32_t)((a_) >> 2) & 3u, cw_ = wq_ == 0 ? win_.x : wq_ == 1 ? win_.y : wq_ == 2 ? win_.z : win_.w; (int)((cw_ >> (8 * ((a_) & 3))) & 0xff); })
     FmdTickets tk_;
     fmd_tickets_init(tk_, queue, 64, n);
     for (;;) {
@@ -278,16 +235,16 @@ __global__ __launch_bounds__(64, 5) void k_bsearch_pair(FmdIndexView ix, size_t 
             if (hc == BS_HANDED) {
                 k = hk; size = (uint32_t)he; pos = (int)(he >> 32) - 1; sbase = ho;
                 const uint64_t a = sbase + (uint64_t)pos;
-                BSP_LOAD16(cq, a, a);
-                if ((a & ~15ull) > (sbase & ~15ull)) BSP_LOAD16(cp, (a & ~15ull) - 16, (a & ~15ull) - 1); // (never below the read's own first block)
+                cq.load(seqs, a, a);
+                if ((a & ~15ull) > (sbase & ~15ull)) cp.load(seqs, (a & ~15ull) - 16, (a & ~15ull) - 1); // (never below the read's own first block)
                 st = 2;
             }
             continue;
         }
         if (st != 2) continue;
         const uint64_t a1 = sbase + (uint64_t)pos, a2 = a1 - 1;
-        const int c1 = BSP_BASE(a1, cq);
-        const int c2 = (a2 & ~15ull) == (a1 & ~15ull) ? BSP_BASE(a2, cq) : BSP_BASE(a2, cp);
+        const int c1 = cq.base(a1);
+        const int c2 = (a2 & ~15ull) == (a1 & ~15ull) ? cq.base(a2) : cp.base(a2);
         if (c1 < 1 || c1 > 4 || c2 < 1 || c2 > 4) { d_cnt[rid] = BS_AGAIN; atomicAdd(again_n, 1u); st = 0; continue; }
         const uint32_t offp = (uint32_t)k & 31u;
         const uint4 A0 = img[0 ^ px], A1 = img[1 ^ px], A2 = img[2 ^ px], B0 = img[3 ^ px], B1 = img[4 ^ px], B2 = img[5 ^ px];
@@ -298,7 +255,7 @@ __global__ __launch_bounds__(64, 5) void k_bsearch_pair(FmdIndexView ix, size_t 
         const uint32_t pm2 = (A2.x ^ e0x) & (A2.y ^ e0y) & (A2.z ^ e0z) & (A2.w ^ e1x) & (B2.x ^ e1y) & (B2.y ^ e1z);
         const uint64_t Mp = win64(pm0, pm1, pm2, offp) & bits_below((int)size);
         const uint32_t nsz = (uint32_t)__popcll(Mp);
-        if (nsz == 0) { d_cnt[rid] = 0; d_beg[rid] = 0; d_end[rid] = 0; st = 0; continue; }      // a miss (exact.c:17-18: the outputs of a miss are not defined; zeros, as k_bsearch)
+        if (nsz == 0) { out.miss(rid); st = 0; continue; }
         const int pr = 4 * (c1 - 1) + (c2 - 1), bp = 28 * pr, tw = bp >> 5, tw1 = tw < 13 ? tw + 1 : 13;
 #define WP_CW(t) iw[(((t) < 6 ? 3 + ((t) >> 1) : 6 + (((t) - 6) >> 2)) ^ px) * 4 + ((t) < 6 ? 2 + ((t) & 1) : (((t) - 6) & 3))]
         const uint32_t cwl = WP_CW(tw), cwh = WP_CW(tw1);
@@ -307,15 +264,13 @@ __global__ __launch_bounds__(64, 5) void k_bsearch_pair(FmdIndexView ix, size_t 
         k = ix.pair_tab[(k >> (5 + FMD_PAIR_SB_SHIFT)) * 16 + (uint64_t)pr] + rel + (uint32_t)__builtin_popcount(pm0 & fmd_mask32((int)offp));
         size = nsz;
         pos -= 2;
-        if (pos < 0) { d_cnt[rid] = size; d_beg[rid] = k; d_end[rid] = k + size - 1; st = 0; continue; }
+        if (pos < 0) { out.store(rid, k, k + size - 1); st = 0; continue; }
         if (((sbase + (uint64_t)pos) & ~15ull) != (a1 & ~15ull)) {   // into the block below: it is here already; the one below that is asked for now
             cq = cp;
             const uint64_t nb_ = (sbase + (uint64_t)pos) & ~15ull;
-            if (nb_ > (sbase & ~15ull)) BSP_LOAD16(cp, nb_ - 16, nb_ - 1);
+            if (nb_ > (sbase & ~15ull)) cp.load(seqs, nb_ - 16, nb_ - 1);
         }
     }
-#undef BSP_LOAD16
-#undef BSP_BASE
 }
 
 // ------------------------------------------------------------------------------ forward reach
@@ -348,25 +303,13 @@ __global__ __launch_bounds__(64) void k_reach(FmdIndexView ix, size_t n, const u
                     if (c == 0 || c > 5) out_len[p] = 0;
                     else {
                         // first ptab_d symbols in one look-up when that many A/C/G/T follow and all of them match
-                        // (the sweep consumes comp(q[p]), comp(q[p+1]), ..: the table string read backwards)
                         const int D = ix.ptab_d;
                         bool from_table = false;
-                        if (ix.ptab) {
-                            uint64_t idx = 0; bool acgt = true;
-                            for (size_t a = p & ~(size_t)3; a < p + (size_t)D && acgt; a += 4) {
-                                const uint32_t w = *(const uint32_t *)(seqs + a);
-#pragma unroll
-                                for (int b = 0; b < 4; ++b) {
-                                    const uint32_t x = (w >> (8 * b)) & 0xff;
-                                    if (a + b >= p && a + b < p + (size_t)D) { acgt = acgt && x >= 1 && x <= 4; idx |= (uint64_t)((4 - x) & 3) << (2 * (a + b - p)); }
-                                }
-                            }
-                            if (acgt) {
-                                const uint4 e = ix.ptab[idx];
-                                fmd_count_lane(ix, 1, 1);
-                                const uint64_t tk = (uint64_t)e.y << 32 | e.x, tl = (uint64_t)e.w << 32 | e.z;
-                                if (tk <= tl) { k = tk; l = tl; i = p + (size_t)D; live = true; from_table = true; }
-                            }
+                        uint64_t idx;
+                        if (ix.ptab && fmd_ptab_fold_fwd(seqs, p, D, idx)) {
+                            const FmdPtabEntry e = fmd_ptab_unpack(ix.ptab[idx]);
+                            fmd_count_lane(ix, 1, 1);
+                            if (e.present) { k = e.k; l = e.l; i = p + (size_t)D; live = true; from_table = true; }
                         }
                         if (!from_table) {
                             k = ix.cnt[cc]; l = ix.cnt[cc + 1] - 1;
@@ -436,19 +379,13 @@ __global__ __launch_bounds__(64) void k_retrieve(FmdIndexView ix, size_t n, cons
 }
 
 // ------------------------------------------------------------------------------- host entry
-#define FMD_CHECK_LAUNCH()                                              \
-    do {                                                                \
-        hipError_t e__ = hipGetLastError();                             \
-        if (e__ != hipSuccess) { fmd_set_hip_error(e__, "kernel launch"); return FMD_E_HIP; } \
-    } while (0)
-
 extern "C" int fmd_rank1a_dev(fmd_dev_t *h, void *stream, size_t n, const uint64_t *d_k, uint64_t *d_ok, int8_t *d_sym)
 {
     if (!h || (n && (!d_k || !d_ok))) return FMD_E_ARG;
     if (n == 0) return FMD_OK;
     FMD_HIP_TRY(hipSetDevice(h->device));
     k_rank1a<<<fmd_grid_for(h, n), 64, 0, S(stream)>>>(fmd_view(h), n, d_k, d_ok, d_sym);
-    FMD_CHECK_LAUNCH();
+    FMD_CHECK_LAUNCH("kernel launch");
     return FMD_OK;
 }
 
@@ -459,7 +396,7 @@ extern "C" int fmd_rank2a_dev(fmd_dev_t *h, void *stream, size_t n, const uint64
     if (n == 0) return FMD_OK;
     FMD_HIP_TRY(hipSetDevice(h->device));
     k_rank2a<<<fmd_grid_for(h, n), 64, 0, S(stream)>>>(fmd_view(h), n, d_k, d_l, d_ok, d_ol);
-    FMD_CHECK_LAUNCH();
+    FMD_CHECK_LAUNCH("kernel launch");
     return FMD_OK;
 }
 
@@ -470,7 +407,7 @@ extern "C" int fmd_extend_dev(fmd_dev_t *h, void *stream, size_t n, const fmd_in
     if (n == 0) return FMD_OK;
     FMD_HIP_TRY(hipSetDevice(h->device));
     k_extend<<<fmd_grid_for(h, n), 64, 0, S(stream)>>>(fmd_view(h), n, d_ik, d_is_back, d_ok);
-    FMD_CHECK_LAUNCH();
+    FMD_CHECK_LAUNCH("kernel launch");
     return FMD_OK;
 }
 
@@ -500,7 +437,7 @@ extern "C" int fmd_bsearch_dev(fmd_dev_t *h, void *stream, size_t n, const uint8
         k_bsearch<2><<<grid, 64, 0, S(stream)>>>(ix, n, d_seqs, d_off, d_cnt, d_beg, d_end, q3, again_n);
     } else
     k_bsearch<0><<<grid, 64, 0, S(stream)>>>(ix, n, d_seqs, d_off, d_cnt, d_beg, d_end, q);
-    FMD_CHECK_LAUNCH();
+    FMD_CHECK_LAUNCH("kernel launch");
     return FMD_OK;
 }
 
@@ -512,7 +449,7 @@ extern "C" int fmd_reach_dev(fmd_dev_t *h, void *stream, size_t n_bytes, const u
     FMD_HIP_TRY(hipSetDevice(h->device));
     uint32_t *q = fmd_next_queue(h, S(stream));
     k_reach<<<fmd_grid_for_lds(h, n_bytes, FMD_COMPACT_LDS_U4 * 16), 64, 0, S(stream)>>>(fmd_view(h), n_bytes, d_seqs, d_len, q);
-    FMD_CHECK_LAUNCH();
+    FMD_CHECK_LAUNCH("kernel launch");
     return FMD_OK;
 }
 
@@ -525,7 +462,7 @@ extern "C" int fmd_retrieve_dev(fmd_dev_t *h, void *stream, size_t n, const uint
     FMD_HIP_TRY(hipSetDevice(h->device));
     uint32_t *q = fmd_next_queue(h, S(stream));
     k_retrieve<<<fmd_grid_for(h, n), 64, 0, S(stream)>>>(fmd_view(h), n, d_x, d_seqs, stride, d_len, d_rank, q);
-    FMD_CHECK_LAUNCH();
+    FMD_CHECK_LAUNCH("kernel launch");
     return FMD_OK;
 }
 

@@ -246,8 +246,7 @@ extern "C" int fmd_ovlp_dev(fmd_dev_t *h, void *stream_, size_t n, const uint64_
         h->aux.release();
     }
     if (rc != FMD_OK) return rc;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { fmd_set_hip_error(e, "overlap kernels"); return FMD_E_HIP; }
+    FMD_CHECK_LAUNCH("overlap kernels");
     return FMD_OK;
 }
 
@@ -319,8 +318,7 @@ extern "C" int fmd_ovlp_head_dev(fmd_dev_t *h, void *stream_, size_t n, const ui
     const int rc = fmd_ovlp_head(h, (hipStream_t)stream_, n, d_ids, min_match, d_rec, (FmdWalkPark *)d_park, (uint32_t *)(w + L.keys_a), (uint32_t *)(w + L.vals_a),
                             d_keys, d_order, w + L.tmp, L.tmp_bytes, (uint4 *)(w + L.adm));
     if (rc != FMD_OK) return rc;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { fmd_set_hip_error(e, "sorted overlap job: head"); return FMD_E_HIP; }
+    FMD_CHECK_LAUNCH("sorted overlap job: head");
     return FMD_OK;
 }
 
@@ -351,8 +349,7 @@ extern "C" int fmd_ovlp_tail_dev(fmd_dev_t *h, void *stream_, size_t np, const u
     FMD_HIP_TRY(hipSetDevice(h->device));
     const int rc = ovl_tail(h, (hipStream_t)stream_, np, d_rows, (FmdWalkPark *)d_park, nullptr, min_match, max_len, max_nei, d_rec, d_nei, d_seq, seq_stride, (uint8_t *)d_work, np);
     if (rc != FMD_OK) return rc;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { fmd_set_hip_error(e, "sorted overlap job: tail"); return FMD_E_HIP; }
+    FMD_CHECK_LAUNCH("sorted overlap job: tail");
     return FMD_OK;
 }
 
@@ -393,8 +390,7 @@ extern "C" int fmd_ovlp_sorted_dev(fmd_dev_t *h, void *stream_, size_t n, const 
         const int rc = ovl_tail(h, st, np, sorted + b, park, d_ids, min_match, max_len, max_nei, d_rec, d_nei, d_seq, seq_stride, w + L.batch_area, batch);
         if (rc != FMD_OK) return rc;
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { fmd_set_hip_error(e, "sorted overlap job"); return FMD_E_HIP; }
+    FMD_CHECK_LAUNCH("sorted overlap job");
     return FMD_OK;
 }
 
@@ -480,8 +476,7 @@ extern "C" int fmd_ovlp_check_left_dev(fmd_dev_t *h, void *stream_, size_t n, in
     fmd_intv_t *listA = (fmd_intv_t *)((uint8_t *)d_work + align_up(n * (size_t)stride_r, 256));
     fmd_intv_t *listB = (fmd_intv_t *)((uint8_t *)listA + align_up(n * (size_t)cap * sizeof(fmd_intv_t), 256));
     fmd_launch_check_left(fmd_grid_for(h, n), st, fmd_next_queue(h, st), fmd_view(h), n, min_match, cap, listA, listB, d_rec, d_seq, seq_stride);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { fmd_set_hip_error(e, "k_ovl_cls"); return FMD_E_HIP; }
+    FMD_CHECK_LAUNCH("k_ovl_cls");
     return FMD_OK;
 }
 
@@ -502,8 +497,7 @@ extern "C" int fmd_seqinfo_dev(fmd_dev_t *h, void *stream_, size_t n, const uint
     a.ix = fmd_view(h); a.n = n; a.ids = d_ids; a.info_only = 1; a.rec = d_rec; a.srev = (uint8_t *)d_work; a.stride_r = stride_r;
     a.listA = (fmd_intv_t *)((uint8_t *)d_work + align_up(n * (size_t)stride_r, 256)); a.cap = cap;
     fmd_launch_walk_whole(h, st, a, max_len, d_seq, seq_stride, 0, FMD_TICKET_CHUNK);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { fmd_set_hip_error(e, "k_ovl_walk"); return FMD_E_HIP; }
+    FMD_CHECK_LAUNCH("k_ovl_walk");
     return FMD_OK;
 }
 

@@ -860,8 +860,7 @@ extern "C" int fmd_ovlp_dist_step(fmd_ovlp_dist_t *d, void *stream_, fmd_ovlp_di
     S.step_ms = (t_end - t_begin) * 1e3;
     d->last = S;
     if (stats) *stats = S;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { fmd_set_hip_error(e, "overlap job on N GPUs"); return FMD_E_HIP; }
+    FMD_CHECK_LAUNCH("overlap job on N GPUs");
     return FMD_OK;
 }
 

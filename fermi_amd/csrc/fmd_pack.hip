@@ -198,8 +198,7 @@ static int pack_core(fmd_dev_t *h, hipStream_t st, size_t n, const uint32_t *d_r
     blocks = (n + 31) / 32;
     if (blocks > (1u << 20)) blocks = 1u << 20;
     k_pack_rows<<<(unsigned)blocks, 256, 0, st>>>(n, d_rec, d_nei, max_nei, d_seq, seq_stride, d_prec, d_off, p4, d_var, var_cap, d_rows, d_row_ids, id_first, id_step, d_pid);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { fmd_set_hip_error(e, "overlap pack kernels"); return FMD_E_HIP; }
+    FMD_CHECK_LAUNCH("overlap pack kernels");
     return FMD_OK;
 }
 
@@ -335,8 +334,7 @@ extern "C" int fmd_ovlp_link_dev(fmd_dev_t *h, void *stream_, size_t n, fmd_ovlp
         FMD_HIP_TRY(hipMemsetAsync(d_row_of, 0xff, n * 4, st));
         k_link_rows32<<<(unsigned)blocks, 256, 0, st>>>(n, d_rec, d_row_of);
         k_link_edges32<<<(unsigned)blocks, 256, 0, st>>>(n, d_rec, d_nei_x01, nei_stride_u64, d_row_of, d_link, d_undecided, (unsigned long long *)d_n_undecided, force_exact);
-        hipError_t e32 = hipGetLastError();
-        if (e32 != hipSuccess) { fmd_set_hip_error(e32, "link kernels"); return FMD_E_HIP; }
+        FMD_CHECK_LAUNCH("link kernels");
         return FMD_OK;
     }
     if (hipMemsetAsync(map, 0xff, n * 8, st) != hipSuccess) { fmd_set_hip_error(hipGetLastError(), "link kernels"); return FMD_E_HIP; }

@@ -362,8 +362,7 @@ extern "C" int fmd_smem_dev(fmd_dev_t *h, void *stream_, size_t n, const uint8_t
     k_smem<<<grid, 64, 0, st>>>(fmd_view(h), n, d_seqs, d_off, self_match ? 1 : 0, 2 * max_len + 2,
                                 (fmd_intv_t *)(((uintptr_t)d_work + 63) & ~(uintptr_t)63), max_mem, d_mem, d_n_mem, q, rf ? atoi(rf) : 8, nullptr,
                                 rf ? nullptr : uniform, pt ? atoi(pt) : 96);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { fmd_set_hip_error(e, "k_smem"); return FMD_E_HIP; }
+    FMD_CHECK_LAUNCH("k_smem");
     return FMD_OK;
 }
 
@@ -385,8 +384,7 @@ extern "C" int fmd_smem_win_dev(fmd_dev_t *h, void *stream_, size_t n, const uin
     if (grid > SMEM_MAX_WAVES) grid = SMEM_MAX_WAVES;
     k_smem<<<grid, 64, 0, st>>>(fmd_view(h), n, d_seqs, nullptr, self_match ? 1 : 0, 2 * max_len + 2,
                                 (fmd_intv_t *)(((uintptr_t)d_work + 63) & ~(uintptr_t)63), max_mem, d_mem, d_n_mem, q, 1, d_wins, nullptr, 0);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { fmd_set_hip_error(e, "k_smem (windows)"); return FMD_E_HIP; }
+    FMD_CHECK_LAUNCH("k_smem (windows)");
     return FMD_OK;
 }
 

@@ -69,7 +69,7 @@ struct FmdIndexView {            // passed by value as a kernel argument (lives 
     // exactly these ptab_d dependent steps -- one DRAM line each, a ninth of all lines of overlap discovery -- for every
     // sequence, every time; they are taken once, when the index is loaded (8 bytes per sequence; nullptr = not built).
     const unsigned long long *tail;
-    // Two-base blocks (fmd_pair.hip; nullptr = not built): 128 bytes per 64 positions, for the steps of a walk below min_match -- nothing is pushed
+    // Two-base blocks (fmd_pair.hip; nullptr = not built): 128 bytes per 32 positions (FMD_PAIR_STRIDE), for the steps of a walk below min_match -- nothing is pushed
     // there, so a step may take TWO bases from one line (a 128-byte random line costs this memory system what a 64-byte one costs: profiles/r6_probe).
     // pair_tab[(block >> FMD_PAIR_SB_SHIFT) * 16 + pair]: where the pair's range starts + the pairs before that superblock (see fmd_pair_step).
     const uint4 *pair;
@@ -421,39 +421,50 @@ struct FmdRank2 {
     int t, tl;             // chunk XOR of each image
     uint32_t nk, nl;       // positions to count in each
     uint32_t blk_k, blk_l; // block numbers
-    bool hk, hl;           // side present
+    bool hk, hl, l_sep;    // side present; the l side lives in another block than the k side
+    bool two_phase;        // compact engine, wave-uniform: bl is not valid until fmd_wave_l_ready()
 };
+typedef FmdRank2 FmdRank2c;
 
-__device__ __forceinline__ FmdRank2 fmd_wave_rank2_fetch(const FmdIndexView &ix, uint4 *lds, uint64_t k, uint64_t l)
+// The opening every rank pair shares, nothing waited for: the k side posted to the dense slot 0 of `lds`, the lanes whose l side is another block
+// compacted by ballot prefix, their block ids written to `ids` and gathered into `pool`.  Returns true when more lanes straddle than the pool holds
+// (never with 64-byte blocks: the branch folds at compile time): nothing of the l side has been posted then, and the caller says what happens.
+// THE WAIT: the ids go through LDS from the lanes that own them to the lanes that fetch them -- lgkmcnt(0) stands between the write and the gather.
+template <int AUX = FMD_GLDS_AUX>
+__device__ __forceinline__ bool fmd_wave_rank2_post(const FmdIndexView &ix, uint4 *lds, uint4 *pool, uint32_t *ids, uint64_t k, uint64_t l, FmdRank2 &r)
 {
     const int q = fmd_lane();
-    FmdRank2 r;
     r.hk = k != ~0ull; r.hl = l != ~0ull;
     uint32_t ok_, ol_;
     fmd_split(k, r.blk_k, ok_); fmd_split(l, r.blk_l, ol_);
     fmd_l_from_k(r.hk && r.hl, l, r.blk_k, r.blk_l, ol_);
-    const bool l_sep = r.hl && !(r.hk && r.blk_k == r.blk_l);
-    fmd_fetch_slot<0>(ix, lds, r.blk_k, r.hk);
+    r.nk = ok_ + 1; r.nl = ol_ + 1;
+    r.l_sep = r.hl && !(r.hk && r.blk_k == r.blk_l);
+    fmd_fetch_slot<0, AUX>(ix, lds, r.blk_k, r.hk);
     r.t = fmd_chunk_xor(q);
     r.bk = lds + fmd_lds_base(q, 0);
     r.bl = r.bk; r.tl = r.t;
-    const uint64_t m = __ballot(l_sep);
-    if (m) {
-        const int n_sep = __popcll(m);
-        if (n_sep <= FMD_POOL_BLOCKS) { // compact pool in slot 1; block ids after the two slots
-            uint4 *pool = lds + FMD_SLOT_U4;
-            uint32_t *ids = (uint32_t *)(lds + 2 * FMD_SLOT_U4);
-            const int p = fmd_below(m);
-            if (l_sep) ids[p] = r.blk_l;
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            fmd_fetch_pool(ix, pool, ids, n_sep);
-            if (l_sep) { r.bl = pool + p * FMD_BLK_U4; r.tl = fmd_pool_xor(p); }
-        } else {
-            fmd_fetch_slot<1>(ix, lds, r.blk_l, l_sep);
-            if (l_sep) r.bl = lds + fmd_lds_base(q, 1);
-        }
+    r.two_phase = false;
+    const uint64_t m = __ballot(r.l_sep);
+    if (m == 0) return false;
+    const int n_sep = __popcll(m);
+    if (FMD_POOL_BLOCKS < 64 && n_sep > FMD_POOL_BLOCKS) return true;
+    const int p = fmd_below(m);
+    if (r.l_sep) ids[p] = r.blk_l;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    fmd_fetch_pool<AUX>(ix, pool, ids, n_sep);
+    if (r.l_sep) { r.bl = pool + p * FMD_BLK_U4; r.tl = fmd_pool_xor(p); }
+    return false;
+}
+
+// compact pool in slot 1, block ids after the two slots; a pool that overflows becomes a dense l slot
+__device__ __forceinline__ FmdRank2 fmd_wave_rank2_fetch(const FmdIndexView &ix, uint4 *lds, uint64_t k, uint64_t l)
+{
+    FmdRank2 r;
+    if (fmd_wave_rank2_post(ix, lds, lds + FMD_SLOT_U4, (uint32_t *)(lds + 2 * FMD_SLOT_U4), k, l, r)) {
+        fmd_fetch_slot<1>(ix, lds, r.blk_l, r.l_sep);
+        if (r.l_sep) r.bl = lds + fmd_lds_base(fmd_lane(), 1);
     }
-    r.nk = ok_ + 1; r.nl = ol_ + 1;
     fmd_fetch_wait();
     return r;
 }
@@ -469,44 +480,21 @@ __device__ __forceinline__ FmdRank2 fmd_wave_rank2_fetch(const FmdIndexView &ix,
 #define FMD_COMPACT_LDS_U4 (FMD_SLOT_U4 + FMD_POOL_BLOCKS * FMD_BLK_U4 + FMD_POOL_BLOCKS / 4)
 #define FMD_DECLARE_COMPACT_LDS() __shared__ uint4 fmd_lds[FMD_COMPACT_LDS_U4]
 
-struct FmdRank2c {
-    const uint4 *bk, *bl;
-    int t, tl;
-    uint32_t nk, nl, blk_k, blk_l;
-    bool hk, hl, l_sep;
-    bool two_phase;        // wave-uniform: bl is not valid until fmd_wave_l_ready()
-};
+// The posting half: `lds` is the landing area (FMD_COMPACT_LDS_U4: dense slot, pool, ids).  A caller with several landing areas posts to each and
+// waits once (fmd_fetch_wait); a pool that overflows makes the step two-phase.
+template <int AUX = FMD_GLDS_AUX>
+__device__ __forceinline__ FmdRank2c fmd_wave_rank2_post_compact(const FmdIndexView &ix, uint4 *lds, uint64_t k, uint64_t l)
+{
+    FmdRank2c r;
+    uint4 *pool = lds + FMD_SLOT_U4;
+    r.two_phase = fmd_wave_rank2_post<AUX>(ix, lds, pool, (uint32_t *)(pool + FMD_POOL_BLOCKS * FMD_BLK_U4), k, l, r);
+    return r;
+}
 
 template <int AUX = FMD_GLDS_AUX>
 __device__ __forceinline__ FmdRank2c fmd_wave_rank2_fetch_compact(const FmdIndexView &ix, uint4 *lds, uint64_t k, uint64_t l)
 {
-    const int q = fmd_lane();
-    FmdRank2c r;
-    r.hk = k != ~0ull; r.hl = l != ~0ull;
-    uint32_t ok_, ol_;
-    fmd_split(k, r.blk_k, ok_);
-    fmd_split(l, r.blk_l, ol_);
-    fmd_l_from_k(r.hk && r.hl, l, r.blk_k, r.blk_l, ol_);
-    r.l_sep = r.hl && !(r.hk && r.blk_k == r.blk_l);
-    fmd_fetch_slot<0, AUX>(ix, lds, r.blk_k, r.hk);
-    r.t = fmd_chunk_xor(q);
-    r.bk = lds + fmd_lds_base(q, 0);
-    r.bl = r.bk; r.tl = r.t;
-    r.two_phase = false;
-    const uint64_t m = __ballot(r.l_sep);
-    if (m) {
-        const int n_sep = __popcll(m);
-        if (n_sep <= FMD_POOL_BLOCKS) {
-            uint4 *pool = lds + FMD_SLOT_U4;
-            uint32_t *ids = (uint32_t *)(pool + FMD_POOL_BLOCKS * FMD_BLK_U4);
-            const int p = fmd_below(m);
-            if (r.l_sep) ids[p] = r.blk_l;
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            fmd_fetch_pool<AUX>(ix, pool, ids, n_sep);
-            if (r.l_sep) { r.bl = pool + p * FMD_BLK_U4; r.tl = fmd_pool_xor(p); }
-        } else r.two_phase = true;
-    }
-    r.nk = ok_ + 1; r.nl = ol_ + 1;
+    const FmdRank2c r = fmd_wave_rank2_post_compact<AUX>(ix, lds, k, l);
     fmd_fetch_wait();
     return r;
 }

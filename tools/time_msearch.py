@@ -27,8 +27,8 @@ def timed(fn, sync):
 
 
 def stats(v):
-    v = sorted(v)
-    return {"median_s": v[len(v) // 2], "min_s": v[0], "max_s": v[-1]}
+    runs, v = list(v), sorted(v)
+    return {"median_s": v[len(v) // 2], "min_s": v[0], "max_s": v[-1], "runs_s": runs}
 
 
 def line_counts(L, handles):
