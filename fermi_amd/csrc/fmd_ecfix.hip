@@ -30,58 +30,38 @@
 #define EC_HEAP_SLOTS 264          // 256 + the slack of one expansion
 #define EC_INFO_TRACE_FULL 0x80000000u
 
+enum { EC_BUF_SEQ = 0, EC_BUF_QUAL, EC_BUF_OFF, EC_BUF_INFO, EC_BUF_WORK, EC_N_BUF };   // the device buffers of the host form: the four arrays of a run and its work area
 struct fmd_ectab {
     int device, w, suf_len;
     uint64_t n_slots;              // power of two
     uint64_t *slots;               // device: kmer << 10 | val << 2 | best base, or EC_EMPTY
     uint32_t *queue;               // device: ticket counter of the persistent kernel (+ EC_FULL_FLAG)
-    void *buf[5]; size_t buf_bytes[5]; int buf_busy;   // device buffers of fmd_ecfix_batch, kept between calls (EcBuf)
+    void *buf[EC_N_BUF]; size_t buf_bytes[EC_N_BUF]; int buf_busy;   // device buffers of fmd_ecfix_batch, kept between calls (EcBuf)
 };
 #define EC_EMPTY (~0ull)
-#ifndef EC_NT_TABLE
-#define EC_NT_TABLE 0
-#endif
-// What a lane keeps in LDS decides how many waves a CU holds (160 KiB), and this kernel lives on resident waves (profiles/r6_ecfix): three knobs.
-#ifndef EC_STAGE_QUAL  // 1: the qualities of a staged read wait in LDS beside its bases (8 KiB per wave)
-#define EC_STAGE_QUAL 0
-#endif
-#ifndef EC_TR_LINE     // trace entries per piece written / read at once through an LDS piece per lane: 0 = entry by entry, 4 = 32-byte pieces, 8 = whole 64-byte lines
+// The tuning values a new part would be swept on again (make variant EXTRA=-D...); the measurements behind the shipped ones: profiles/r6_ecfix, profiles/r6_hop.
+// What a lane keeps in LDS decides how many waves a CU holds (160 KiB), and this kernel lives on resident waves (profiles/r6_ecfix): the first two.
+#ifndef EC_TR_LINE     // trace entries per piece written / read at once through an LDS piece per lane: 4 = 32-byte pieces, 8 = whole 64-byte lines
 #define EC_TR_LINE 4
 #endif
 #ifndef EC_LDS_H       // entries of the lane's queue (a binary heap) that live in LDS, the rest in its slice of HBM
 #define EC_LDS_H 4
 #endif
-#ifndef EC_QWIN        // 1: the lane keeps the 16 aligned bytes of qualities around the last position it asked for in registers (a strand is searched position by position)
-#define EC_QWIN 1
-#endif
-#ifndef EC_HOP_LOOP
-#define EC_HOP_LOOP 1      // the hop chains in a loop of their own (below); 0: every hop a turn of the general form
-#endif
 #ifndef EC_HOP_MIN
-#define EC_HOP_MIN 16      // ... which runs (once at least, if anybody hops) while at least this many lanes of the wave are hopping: 1 -> 218 ms (a last hopping lane holds 63 up), 8 -> 173, 16 -> 160, 24 -> 162, 32 and more -> 172 (profiles/r6_hop)
-#endif
-#ifndef EC_HOP_ONLY
-#define EC_HOP_ONLY 1      // 1: the general turn holds no hop at all (a hopping lane sits it out; the loop gives every one of them a hop per turn at least)
-#endif
-#ifndef EC_PUSH_AB
-#define EC_PUSH_AB 1       // 1: a turn's pushes through two shared calls
-#endif
-#ifndef EC_GATE
-#define EC_GATE 1          // taking reads in / seeding strands / closing strands wait until EC_GATE_IN / EC_GATE_CL lanes of the wave want to (k_ecfix)
+#define EC_HOP_MIN 16      // the hop loop of k_ecfix runs (once at least, if anybody hops) while at least this many lanes of the wave are hopping: 1 -> 218 ms (a last hopping lane holds 63 up), 8 -> 173, 16 -> 160, 24 -> 162, 32 and more -> 172 (profiles/r6_hop)
 #endif
 #ifndef EC_GATE_IN
-#define EC_GATE_IN 16      // 0 (no gates): 143.8 ms per 5*10^7 reads; 4: 130.4; 8: 117.9; 16: 114.2; 24: 122.1 (profiles/r6_hop/ab_gate.txt)
+#define EC_GATE_IN 16      // taking reads in and seeding strands wait until this many lanes of the wave want to (k_ecfix): no gates: 143.8 ms per 5*10^7 reads; 4: 130.4; 8: 117.9; 16: 114.2; 24: 122.1 (profiles/r6_hop/ab_gate.txt)
 #endif
 #ifndef EC_GATE_CL
-#define EC_GATE_CL 8
+#define EC_GATE_CL 8       // ... and closing strands until this many do
 #endif
-#ifndef EC_HOP_WARM
-#define EC_HOP_WARM 0      // 1: the hop loop asks for the NEXT hop's table line beside this hop's (speculation: most hops stand)
+#ifndef EC_LB              // waves per SIMD that k_ecfix's registers are budgeted for (__launch_bounds__)
+#define EC_LB 4
 #endif
-#ifndef EC_HOP_BATCH   // 1: the bases a hop passes over are taken from the lane's LDS words in one piece, not one LDS read and one 64-bit shift per base
-#define EC_HOP_BATCH 1
-#endif
-#define EC_STAGE (EC_TR_LINE > 0)
+static_assert(EC_TR_LINE >= 2 && EC_TR_LINE <= 8 && (EC_TR_LINE & (EC_TR_LINE - 1)) == 0, "EC_TR_LINE: 2, 4 or 8 (a piece is moved as 16-byte halves and indexed by a mask)");
+static_assert(EC_LDS_H >= 1, "EC_LDS_H: the top of the queue lives in LDS");
+static_assert(EC_HOP_MIN >= 1 && EC_HOP_MIN <= 64 && EC_GATE_IN >= 1 && EC_GATE_IN <= 64 && EC_GATE_CL >= 1 && EC_GATE_CL <= 64, "EC_HOP_MIN, EC_GATE_IN, EC_GATE_CL: lanes of one wave, 1..64");
 // One triple encodes to EC_EMPTY itself: the 27-mer of 27 Ts (54 one bits) with the largest packed depths (255) and best base T.
 // k_ectab_fill does not store it -- it would read as an empty slot and the solid k-mer as a miss -- but raises queue[EC_FULL_FLAG],
 // and a look-up of that k-mer that runs into an empty slot answers from the flag.
@@ -136,14 +116,7 @@ __device__ __forceinline__ int ec_lookup(const uint64_t *__restrict__ slots, uin
     uint64_t ln = ec_hash(x) & lmask;
     for (;;) {
         const uint4 *q = (const uint4 *)(slots + ln * EC_LINE);
-#if EC_NT_TABLE   // a table line is asked for once: "nt" keeps it from pushing the lanes' own reads out of the caches (profiles/r6_ecfix)
-        typedef uint32_t ec_u32x4 __attribute__((ext_vector_type(4)));
-        const ec_u32x4 a_ = __builtin_nontemporal_load((const ec_u32x4 *)q), b_ = __builtin_nontemporal_load((const ec_u32x4 *)q + 1),
-                       c_ = __builtin_nontemporal_load((const ec_u32x4 *)q + 2), d_ = __builtin_nontemporal_load((const ec_u32x4 *)q + 3);
-        const uint4 a = make_uint4(a_.x, a_.y, a_.z, a_.w), b = make_uint4(b_.x, b_.y, b_.z, b_.w), c = make_uint4(c_.x, c_.y, c_.z, c_.w), d = make_uint4(d_.x, d_.y, d_.z, d_.w);
-#else
         const uint4 a = q[0], b = q[1], c = q[2], d = q[3];
-#endif
         C.add(0, EC_LINE);
         int hit = -2;
         bool free_slot = false;
@@ -169,8 +142,7 @@ struct EcNode { uint64_t x; int64_t y; };
 // 8-byte store to the trace.  Round 4's kernel kept all of it in HBM behind byte loads -- ~17 dependent round trips per expansion, 409 ms per 5*10^7 reads.
 #define EC_LDS_BASES 128
 #define EC_LDS_BW (EC_LDS_BASES / 8)          // words of bases per lane
-#define EC_LDS_QW (EC_LDS_BASES / 4)          // words of quality bytes per lane
-#define EC_LDS_BYTES (EC_LDS_H * 64 * 16 + EC_LDS_BW * 64 * 4 + (EC_STAGE_QUAL ? EC_LDS_QW * 64 * 4 : 0) + EC_TR_LINE * 64 * 8)   // 4 + 4 + 0 + 2 = 10 KiB per wave: 16 waves per CU
+#define EC_LDS_BYTES (EC_LDS_H * 64 * 16 + EC_LDS_BW * 64 * 4 + EC_TR_LINE * 64 * 8)   // queue 4 + bases 4 + trace piece 2 = 10 KiB per wave: 16 waves per CU
 
 struct EcHeap {                                // entry k of the lane's queue
     uint4 *lds; uint4 *hbm;                    // lds + k * 64 for k < EC_LDS_H, hbm + k beyond
@@ -220,7 +192,6 @@ __device__ __forceinline__ EcNode ec_pop(const EcHeap &H, uint32_t &hn, EcCount 
 struct EcRead {
     uint8_t *s, *q; int len; bool rc, staged;
     uint32_t *lb;                              // the lane's words of bases in LDS (staged reads)
-    uint32_t *lq;                              // EC_STAGE_QUAL: the lane's words of quality bytes in LDS, in read order
     __device__ __forceinline__ int at(int i) const { return rc ? len - 1 - i : i; }
     __device__ __forceinline__ int base(int i) const
     {
@@ -235,43 +206,23 @@ struct EcRead {
         s[j] = (uint8_t)v;
         if (staged) { uint32_t *w = lb + (j >> 3) * 64; *w = (*w & ~(0xfu << (4 * (j & 7)))) | v << (4 * (j & 7)); }
     }
-#if EC_STAGE_QUAL
-    __device__ __forceinline__ int qual(int i) const { const int j = at(i); return staged ? (int)((lq[(j >> 2) * 64] >> (8 * (j & 3))) & 0xffu) : (int)q[j]; }
-    __device__ __forceinline__ void set_qual(int i, int v)
-    {
-        const int j = at(i);
-        q[j] = (uint8_t)v;
-        if (staged) { uint32_t *w = lq + (j >> 2) * 64; *w = (*w & ~(0xffu << (8 * (j & 3)))) | (uint32_t)(v & 0xff) << (8 * (j & 3)); }
-    }
-#else
-#if EC_QWIN
-    // The quality of position i is asked for once per expansion, of a position a few bases from the last one: the 16 aligned bytes around it stay in four
-    // registers, and three accesses in four are answered from them.  (Byte by byte every access paid a 64-byte line that the table's lines had pushed out of
-    // the caches since the last one: 155 GB of table lines pass through them per 5*10^7 reads.  profiles/r6_ecfix.)
-    // (the window lives in the kernel's own registers, EcQwin: as members of this struct the whole struct went to scratch)
-    __device__ __forceinline__ int qual(int i) const { return (int)q[at(i)]; }
-    __device__ __forceinline__ void set_qual(int i, int v) { q[at(i)] = (uint8_t)v; }
-#else
-    __device__ __forceinline__ int qual(int i) const { return (int)q[at(i)]; }
-    __device__ __forceinline__ void set_qual(int i, int v) { q[at(i)] = (uint8_t)v; }
-#endif
-#endif
+    __device__ __forceinline__ void set_qual(int i, int v) { q[at(i)] = (uint8_t)v; }   // (whoever calls this drops the lane's window, EcQwin)
 };
+// The quality of position i is asked for once per expansion, of a position a few bases from the last one: the 16 aligned bytes around it stay in four
+// registers, and three accesses in four are answered from them.  (Byte by byte every access paid a 64-byte line that the table's lines had pushed out of
+// the caches since the last one: 155 GB of table lines pass through them per 5*10^7 reads.  profiles/r6_ecfix.)
+// (the window lives in the kernel's own registers: as members of EcRead the whole struct went to scratch)
 struct EcQwin { uint32_t w0, w1, w2, w3; uint64_t tag; };
 __device__ __forceinline__ int ec_qual(const EcRead &r, int i, EcQwin &W)
 {
-#if EC_QWIN && !EC_STAGE_QUAL
     const uint64_t a = (uint64_t)(uintptr_t)(r.q + r.at(i)), t = a & ~15ull;
     if (t != W.tag) { const uint4 v = *(const uint4 *)(uintptr_t)t; W.w0 = v.x; W.w1 = v.y; W.w2 = v.z; W.w3 = v.w; W.tag = t; }
     const uint32_t o = (uint32_t)a & 15u, wv = (o >> 2) == 0 ? W.w0 : (o >> 2) == 1 ? W.w1 : (o >> 2) == 2 ? W.w2 : W.w3;
     return (int)((wv >> (8 * (o & 3))) & 0xffu);
-#else
-    return r.qual(i);
-#endif
 }
-// The read into the lane's LDS words: aligned 4-byte loads funnel-shifted into place, whatever the alignment of its first byte; a word is loaded only if
-// it holds a byte of the read (bytes past the read's end inside its last word: whatever follows, never looked at).
-__device__ __forceinline__ void ec_stage_words(const uint8_t *p, int len, uint32_t *dst, bool nibbles)
+// The read into the lane's LDS words, a nibble per base: aligned 4-byte loads funnel-shifted into place, whatever the alignment of its first byte; a word is
+// loaded only if it holds a byte of the read (bytes past the read's end inside its last word: whatever follows, never looked at).
+__device__ __forceinline__ void ec_stage_words(const uint8_t *p, int len, uint32_t *dst)
 {
     const uint32_t *al = (const uint32_t *)((uintptr_t)p & ~(uintptr_t)3);
     const uint32_t sh = 8u * (uint32_t)((uintptr_t)p & 3);
@@ -282,52 +233,48 @@ __device__ __forceinline__ void ec_stage_words(const uint8_t *p, int len, uint32
         const uint32_t nxt = al + w + 1 <= last ? al[w + 1] : 0u;
         const uint32_t d = sh ? __builtin_amdgcn_alignbit(nxt, carry, sh) : carry;
         carry = nxt;
-        if (!nibbles) dst[w * 64] = d;
-        else {
-            uint32_t t = (d | d >> 4) & 0x00ff00ffu; t = (t | t >> 8) & 0xffffu;   // four bases -> four nibbles
-            if (w & 1) dst[(w >> 1) * 64] = acc | t << 16; else acc = t;
-        }
+        uint32_t t = (d | d >> 4) & 0x00ff00ffu; t = (t | t >> 8) & 0xffffu;   // four bases -> four nibbles
+        if (w & 1) dst[(w >> 1) * 64] = acc | t << 16; else acc = t;
     }
-    if (nibbles && (nw & 1)) dst[(nw >> 1) * 64] = acc;
+    if (nw & 1) dst[(nw >> 1) * 64] = acc;
 }
 __device__ __forceinline__ void ec_stage(EcRead &r)
 {
     r.staged = r.len > 0 && r.len <= EC_LDS_BASES;
-    if (!r.staged) return;
-    ec_stage_words(r.s, r.len, r.lb, true);
-#if EC_STAGE_QUAL
-    ec_stage_words(r.q, r.len, r.lq, false);
-#endif
+    if (r.staged) ec_stage_words(r.s, r.len, r.lb);
 }
 
 // The trace of a lane (correct.c:104: one entry per path, each naming its parent) is written in order and read back along ONE chain of parents.  Entry by
 // entry that is an 8-byte access to a line of the lane's own (64 lanes, 64 lines per wave instruction: every entry pays a 64-byte line -- 92 GB of traffic for
-// 11.5 GB of entries on 5*10^7 reads, profiles/r5_final).  EC_STAGE: the open line -- EC_TR_LINE entries -- waits in LDS (entry e of lane l at [e * 64 + l]) and
-// leaves whole; the walk back loads the line of the entry it wants into the same LDS line and takes every entry of its chain that the line holds.
+// 11.5 GB of entries on 5*10^7 reads, profiles/r5_final).  So the open line -- EC_TR_LINE entries -- waits in LDS (entry e of lane l at [e * 64 + l]) and
+// leaves whole; the walk back loads the line of the entry it wants into the same LDS line and takes every entry of its chain that the line holds
+// (profiles/r6_ecfix).
 struct EcTrace {
     uint64_t *hbm;                             // the lane's slice
-    uint64_t *ln;                              // its LDS line (lds + lane)
+    uint64_t *ln;                              // its LDS line (lds + lane), never null
     uint32_t tag;                              // walk back: the line of the slice the LDS line holds
     __device__ __forceinline__ void put(uint32_t t, uint64_t v, EcCount &C)
     {
-#if EC_STAGE
         ln[(t & (EC_TR_LINE - 1)) * 64] = v;
         if ((t & (EC_TR_LINE - 1)) == EC_TR_LINE - 1) flush(t, C);
-#else
-        hbm[t] = v; C.add(2);
-#endif
     }
     __device__ __forceinline__ void flush(uint32_t t, EcCount &C)     // the line that holds entry t, whole
     {
-#if EC_STAGE
         uint4 *dst = (uint4 *)(hbm + (t & ~(uint32_t)(EC_TR_LINE - 1)));
 #pragma unroll
-        for (int e = 0; e < (EC_TR_LINE > 0 ? EC_TR_LINE : 2); e += 2) {
+        for (int e = 0; e < EC_TR_LINE; e += 2) {
             const uint64_t a = ln[e * 64], b = ln[(e + 1) * 64];
             dst[e >> 1] = make_uint4((uint32_t)a, (uint32_t)(a >> 32), (uint32_t)b, (uint32_t)(b >> 32));
         }
         C.add(2, EC_TR_LINE);
-#endif
+    }
+    // walk back: the line that holds entry t is asked for (it goes into the LDS line later in the turn, when it is there: k_ecfix)
+    __device__ __forceinline__ void load(uint32_t t, uint4 (&tl)[EC_TR_LINE / 2], EcCount &C) const
+    {
+        const uint4 *src = (const uint4 *)(hbm + (t & ~(uint32_t)(EC_TR_LINE - 1)));
+#pragma unroll
+        for (int e = 0; e < EC_TR_LINE / 2; ++e) tl[e] = src[e];
+        C.add(2, EC_TR_LINE);
     }
 };
 
@@ -401,9 +348,8 @@ __device__ __forceinline__ int ec_hop(const EcRead &r, EcNode &z, int step, int 
     i = (int)((uint64_t)z.y & 0xffff) - 1;
     const int nav = i < step ? (i < 0 ? 0 : i) : step;             // bases the loop below would take if none of them is an N (i >= 1, l < step)
     bool batched = false;
-#if EC_HOP_BATCH
     if (r.staged && nav > 0 && nav <= 8 && 2 * (nav - 1) <= shift) {
-        // all of them at once: their nibbles are one field of the lane's LDS words (positions i - nav + 1 .. i of the strand; on the reverse strand the
+        // all of them at once, not one LDS read and one 64-bit shift per base (profiles/r6_ecfix): their nibbles are one field of the lane's LDS words (positions i - nav + 1 .. i of the strand; on the reverse strand the
         // bytes run the other way and the bases are complemented), A/C/G/T -> 2 bits each, into the k-mer in the order the loop shifts them in
         const int jl = r.rc ? r.len - 1 - i : i - nav + 1;
         const uint32_t wq = (uint32_t)jl >> 3, sh4 = 4u * ((uint32_t)jl & 7u);
@@ -421,8 +367,7 @@ __device__ __forceinline__ int ec_hop(const EcRead &r, EcNode &z, int step, int 
             batched = true;
         }
     }
-#endif
-    if (!batched)
+    if (!batched)                                                     // base by base: unstaged reads, an N among them, hops of more than 8 bases
     for (l = 0; i >= 1 && l < step; --i, ++l) {
         const int c = r.base(i);
         if (c >= 5) break;
@@ -450,39 +395,22 @@ __device__ __forceinline__ bool ec_hop_good(int hit, int b, int i, int qv, EcNod
 // entry (EL_CLOSE) -- so that the 64 requests of a wave are in flight together whatever its lanes are doing: the reference's inner loops (up to 20 dependent
 // look-ups while a clean read hops along, up to 100 dependent trace entries at the end) are turns here, not loops inside a turn that 63 lanes wait for.
 // A lane whose read is finished draws the next one at once (reads with errors take 10-100x the expansions of clean ones: a wave never waits for its slowest read).
+// The turn's five phases -- take in and seed, hop chain, what the lane wants, the one request, what came back -- are marked "----" in the body.
 enum { EL_IDLE = 0, EL_POP, EL_JUMP, EL_CLOSE, EL_HOPEND, EL_SEED };
-#ifndef EC_LB
-#define EC_LB 4
-#endif
 __global__ __launch_bounds__(64, EC_LB) void k_ecfix(size_t n, uint8_t *__restrict__ seqs, uint8_t *__restrict__ quals, const uint64_t *__restrict__ off, int w, int step,
                                                  const uint64_t *__restrict__ slots, uint64_t mask, int32_t *__restrict__ info, uint4 *heaps, uint64_t *traces,
                                                  uint32_t trace_cap, uint32_t *__restrict__ queue)
 {
     __shared__ uint4 lds_heap[EC_LDS_H * 64];
     __shared__ uint32_t lds_bases[EC_LDS_BW * 64];
-#if EC_STAGE_QUAL
-    __shared__ uint32_t lds_quals[EC_LDS_QW * 64];
-#endif
-#if EC_STAGE
     __shared__ uint64_t lds_trace[EC_TR_LINE * 64];
-#endif
     const int lane = (int)threadIdx.x;
     const size_t slice = (size_t)blockIdx.x * 64 + threadIdx.x;
     EcHeap H; H.lds = lds_heap + lane; H.hbm = heaps + slice * EC_HEAP_SLOTS;
-    EcTrace trace; trace.hbm = traces + slice * (size_t)trace_cap; trace.tag = 0;
-#if EC_STAGE
-    trace.ln = lds_trace + lane;
-#else
-    trace.ln = nullptr;
-#endif
+    EcTrace trace; trace.hbm = traces + slice * (size_t)trace_cap; trace.ln = lds_trace + lane; trace.tag = 0;
     const int shift = (w - 1) << 1;
     EcRead r; r.s = nullptr; r.q = nullptr; r.len = 0; r.rc = true; r.staged = false; r.lb = lds_bases + lane;
     EcQwin QW; QW.w0 = QW.w1 = QW.w2 = QW.w3 = 0; QW.tag = ~0ull;
-#if EC_STAGE_QUAL
-    r.lq = lds_quals + lane;
-#else
-    r.lq = nullptr;
-#endif
     EcSearch S; S.hn = S.tn = 0; S.n_done = 0; S.no_hits = 1; S.done_y0 = S.done_y1 = 0;
     EcNode z, keep;                            // EL_JUMP: the path as the hop in progress leaves it, and as the last accepted hop left it
     z.x = 0; z.y = 0; keep = z;
@@ -497,17 +425,13 @@ __global__ __launch_bounds__(64, EC_LB) void k_ecfix(size_t n, uint8_t *__restri
     EcCount C;
     fmd_tickets_init(tk, queue);
     for (;;) {
-#if EC_GATE
-        // ---- what a lane does ONCE per strand -- take a read and stage it, find the strand's seed k-mer; close a strand: walk its best path back, hand the
+        // ---- take in and seed, behind a gate.  What a lane does ONCE per strand -- take a read and stage it, find the strand's seed k-mer; close a strand: walk its best path back, hand the
         // result on -- costs the wave its whole code every turn in which ANY lane does it, and with 64 lanes and ~18 turns per strand some lane nearly always
         // does.  So these wait for company: reads are taken in and strands seeded when EC_GATE_IN lanes want it, strands closed when EC_GATE_CL do -- or
         // when no lane of the wave is searching (then everything goes ahead: nothing can wait for ever).  Per lane the sequence of operations is unchanged.
         const uint64_t busy_m = __ballot(st == EL_POP || st == EL_JUMP || st == EL_HOPEND);
         const bool gate_in = busy_m == 0 || __popcll(__ballot((st == EL_IDLE && !drained) || st == EL_SEED)) >= EC_GATE_IN;
         const bool gate_cl = busy_m == 0 || __popcll(__ballot(st == EL_CLOSE)) >= EC_GATE_CL;
-#else
-        const bool gate_in = true, gate_cl = true;
-#endif
         const size_t my = fmd_tickets_take(tk, queue, gate_in && st == EL_IDLE && !drained);
         if (gate_in) {
             if (st == EL_IDLE && !drained) {
@@ -530,12 +454,12 @@ __global__ __launch_bounds__(64, EC_LB) void k_ecfix(size_t n, uint8_t *__restri
         }
         if (__ballot(st != EL_IDLE) == 0) { if (__ballot(!drained) == 0) { C.flush(queue); break; } else continue; }
 
-#if EC_HOP_LOOP
         // ---- hop chains first.  A strand in agreement with the table hops `step` bases at a time, one look-up per hop, up to (len - w) / step hops in a row
         // (correct.c:182-196) -- three turns in four of an error-free read -- and a turn of the general form below costs the wave everything any lane might
         // be doing: the queue's sift loops, the branches, the walk back.  So the lanes that are hopping hop on in a loop that holds nothing but the hop, its
         // look-up and the verdict, until fewer than EC_HOP_MIN of them still are (the rest wait; a chain that ends leaves its strand in EL_HOPEND, and the
-        // turn below pushes the kept path and pops the next one as before).  Per lane the sequence of operations is the same as without the loop.
+        // turn below pushes the kept path and pops the next one).  The turn below holds no hop at all: a lane still hopping sits it out, and this loop gives
+        // every one of them a hop per turn at least.  Per lane the sequence of operations is that of one hop per general turn (profiles/r6_hop).
         if (__ballot(st == EL_JUMP)) {
             do {
                 if (st == EL_JUMP) {
@@ -544,27 +468,13 @@ __global__ __launch_bounds__(64, EC_LB) void k_ecfix(size_t n, uint8_t *__restri
                     bool ends = bh == 5;
                     if (!ends) {
                         const int qh = ec_qual(r, ih, QW);
-#if EC_HOP_WARM
-                        // most hops stand, and then the next look-up is the k-mer `step` bases further on: its line is asked for NOW, beside this hop's
-                        // (one word of it is loaded and never looked at: the line is in the caches by the time the next turn asks for it)
-                        if (ih > 0) {
-                            EcNode zs = z;
-                            zs.y = (int64_t)((uint64_t)z.y >> 16 << 16 | (uint64_t)(ih + 1));       // (as ec_hop_good leaves a hop that stands)
-                            (void)ec_hop(r, zs, step, shift);
-                            const uint32_t w_ = *(const volatile uint32_t *)(slots + (ec_hash(zs.x) & (mask >> 3)) * EC_LINE);
-                            (void)w_;
-                        }
-                        const int hh = ec_lookup(slots, mask, z.x, full, C);
-#else
-                        const int hh = ec_lookup(slots, mask, z.x, full, C);
-#endif
+                        const int hh = ec_lookup(slots, mask, z.x, full, C);   // (asking for the NEXT hop's line beside this one measured slower: profiles/r6_hop/ab_warm.txt)
                         ends = !ec_hop_good(hh, bh, ih, qh, z, keep, keep_i, keep_q, depth_last) || keep_i <= 0;
                     }
                     if (ends) st = EL_HOPEND;
                 }
             } while (__popcll(__ballot(st == EL_JUMP)) >= EC_HOP_MIN);
         }
-#endif
         // ---- what the lane wants from memory this turn
         bool want = false, pass_done = false, hop_end = false, overflow = false;
         int i = 0, b = 0;
@@ -585,41 +495,21 @@ __global__ __launch_bounds__(64, EC_LB) void k_ecfix(size_t n, uint8_t *__restri
                 else { i = (int)(zy & 0xffff) - 1; b = r.base(i); want = true; }
             }
         }
-#if !(EC_HOP_LOOP && EC_HOP_ONLY)
-        else if (st == EL_JUMP) {                                          // `step` bases on (correct.c:183-185)
-            i = ec_hop(r, z, step, shift);
-            b = r.base(i);
-            if (b == 5) hop_end = true; else want = true;
-        }
-#endif
         if (pass_done) {                                                   // correct.c:207-212
             score_diff = S.n_done == 1 ? EC_MAX_SC_DIFF : (int)((uint64_t)S.done_y1 >> 48) - (int)((uint64_t)S.done_y0 >> 48);
             if (score_diff >= EC_MAX_SC_DIFF) score_diff = EC_MAX_SC_DIFF;
             qsum = 0;
             ct = ((uint64_t)S.done_y0 >> 48) == 0 ? 0u : (uint32_t)((uint64_t)S.done_y0 >> 16);   // nothing to change: no walk back
             st = EL_CLOSE;
-#if EC_STAGE
             if (ct && S.tn) { trace.flush(S.tn - 1, C); trace.tag = (S.tn - 1) / EC_TR_LINE; }   // the open line leaves too (whole: what lies behind its last entry is never read); the LDS line still holds it
-#endif
         }
         // ---- the turn's one request per lane
         int hit = -1, qv = 0;
-        uint64_t te = 0;
         if (want) { qv = ec_qual(r, i, QW); hit = ec_lookup(slots, mask, z.x, full, C); }   // (the byte's load is in flight beside the line's)
-#if EC_STAGE
         uint4 tl[EC_TR_LINE / 2];
         const bool tload = st == EL_CLOSE && gate_cl && ct && ct / EC_TR_LINE != trace.tag;
-        if (tload) {
-            const uint4 *src = (const uint4 *)(trace.hbm + (ct & ~(uint32_t)(EC_TR_LINE - 1)));
-#pragma unroll
-            for (int e = 0; e < EC_TR_LINE / 2; ++e) tl[e] = src[e];
-            C.add(2, EC_TR_LINE);
-        }
-#else
-        if (st == EL_CLOSE && gate_cl && ct) { te = trace.hbm[ct]; C.add(2); }
-#endif
+        if (tload) trace.load(ct, tl, C);
         // ---- what came back
-#if EC_PUSH_AB
         // The paths a turn adds to the queue -- none, one (a miss; the kept path where a hop chain cannot start) or two (the read's base and the table's) -- are
         // described first and pushed by TWO shared calls: four inlined copies of the push (trace entry + sift loop) cost the wave four of them per turn
         // whenever its lanes disagree about which one they need.
@@ -644,73 +534,25 @@ __global__ __launch_bounds__(64, EC_LB) void k_ecfix(size_t n, uint8_t *__restri
                 }
             }
         }
-#if !(EC_HOP_LOOP && EC_HOP_ONLY)
-        else if (want) {                                                   // EL_JUMP: is the hop good?  (correct.c:186-195)
-            const bool good = ec_hop_good(hit, b, i, qv, z, keep, keep_i, keep_q, depth_last);
-            if (!good || keep_i <= 0) hop_end = true;
-        }
-#endif
         if (hop_end) { pa = true; a_keep = true; ac = r.base(keep_i) - 1; acost = 0; st = EL_POP; }   // the path goes on from where the last good hop left it (correct.c:198)
         if (pa) overflow = !ec_branch(H, S.hn, trace, S.tn, trace_cap, a_keep ? keep : z, ac, acost, shift, amatch, a_keep ? keep_q : qv, C);
         if (pb && !overflow) overflow = !ec_branch(H, S.hn, trace, S.tn, trace_cap, z, bc, bcost, shift, 1, qv, C);
-#else
-        if (want && st == EL_POP) {
-            int q = qv - 33;
-            q = q < EC_MAX_QUAL ? q : EC_MAX_QUAL;
-            q = q < 3 ? 3 : q;
-            bool ok = true;
-            if (hit < 0) ok = ec_branch(H, S.hn, trace, S.tn, trace_cap, z, b - 1, EC_MISS_PENALTY + (EC_MAX_QUAL - q), shift, 0, qv, C);
-            else {
-                const int best = (hit & 3) + 1, v = hit >> 2;
-                S.no_hits = 0;
-                if (b != best) {                                     // the table prefers another base: follow both, within the queue's budget
-                    const int pen = ec_swap_penalty(v);
-                    if (b != 5 && (S.hn + 2 <= EC_MAX_HEAP || pen < q)) ok = ec_branch(H, S.hn, trace, S.tn, trace_cap, z, b - 1, pen, shift, 1, qv, C);
-                    if (ok && (b == 5 || S.hn + 2 <= EC_MAX_HEAP || pen > q)) ok = ec_branch(H, S.hn, trace, S.tn, trace_cap, z, best - 1, q, shift, 1, qv, C);
-                } else {                                             // agreement: hop `step` bases at a time while the k-mers stay deep and unambiguous
-                    keep = z; keep_i = i; keep_q = qv; depth_last = ec_depth(v);
-                    if ((v & 7) <= 0 && step > 1 && keep_i > 0) st = EL_JUMP;
-                    else hop_end = true;
-                }
-            }
-            overflow = !ok;
-        }
-#if !(EC_HOP_LOOP && EC_HOP_ONLY)
-        else if (want) {                                                   // EL_JUMP: is the hop good?  (correct.c:186-195)
-            const bool good = ec_hop_good(hit, b, i, qv, z, keep, keep_i, keep_q, depth_last);
-            if (!good || keep_i <= 0) hop_end = true;
-        }
-#endif
-        if (hop_end) {                                                     // the path goes on from where the last good hop left it (correct.c:198)
-            overflow = !ec_branch(H, S.hn, trace, S.tn, trace_cap, keep, r.base(keep_i) - 1, 0, shift, 1, keep_q, C);
-            st = EL_POP;
-        }
-#endif
         if (overflow) { info[cur] = (int32_t)EC_INFO_TRACE_FULL; st = EL_IDLE; continue; }
         if (st != EL_CLOSE || !gate_cl) continue;
-#if EC_STAGE
         if (tload) {                                                       // the line of the chain's next entry into the lane's LDS line
 #pragma unroll
             for (int e = 0; e < EC_TR_LINE / 2; ++e) { trace.ln[2 * e * 64] = (uint64_t)tl[e].y << 32 | tl[e].x; trace.ln[(2 * e + 1) * 64] = (uint64_t)tl[e].w << 32 | tl[e].z; }
             trace.tag = ct / EC_TR_LINE;
         }
         while (ct && ct / EC_TR_LINE == trace.tag) {                       // every choice of the best path that this line holds (correct.c:213-218)
-            te = trace.ln[(ct & (EC_TR_LINE - 1)) * 64];
-#else
-        if (ct) {                                                          // one choice of the best path applied (correct.c:213-218)
-#endif
+            const uint64_t te = trace.ln[(ct & (EC_TR_LINE - 1)) * 64];
             const int pos = (int)((te >> 32) & 0xffffu), qq = (int)((te >> 48) & 0xffu);
             const uint32_t lo = (uint32_t)te, c = lo >> 29;
             if ((uint32_t)(r.base(pos) - 1) != c) { qsum += qq - 33; r.set_base(pos, (int)c + 1); }
             else if ((lo >> 28 & 1) && qq < 37) { r.set_qual(pos, 37); QW.tag = ~0ull; }
             ct = lo << 4 >> 4;
-#if !EC_STAGE
-            if (ct) continue;
-#endif
         }
-#if EC_STAGE
         if (ct) continue;
-#endif
         {                                                                  // the strand is done
             int ret = ((uint64_t)S.done_y0 >> 48) == 0 ? score_diff << 18 : (qsum | score_diff << 18 | S.no_hits << 17);
             if (r.rc) { ret0 = ret; r.rc = false; st = EL_SEED; continue; }   // the reverse-complement strand is done: now the read as given (seeded at the top, in company)
@@ -726,7 +568,7 @@ extern "C" void fmd_ectab_free(fmd_ectab_t *t)
     if (!t) return;
     hipSetDevice(t->device);
     hipFree(t->slots); hipFree(t->queue);
-    for (int i = 0; i < 5; ++i) if (t->buf[i]) hipFree(t->buf[i]);
+    for (int i = 0; i < EC_N_BUF; ++i) if (t->buf[i]) hipFree(t->buf[i]);
     free(t);
 }
 
@@ -833,7 +675,7 @@ extern "C" int fmd_ecfix_dev(fmd_ectab_t *t, void *stream_, size_t n, uint8_t *d
     FMD_HIP_TRY(hipSetDevice(t->device));
     hipStream_t st = (hipStream_t)stream_;
     const int grid = ec_grid(t->device, n);
-    if (EC_TR_LINE > 0) trace_cap &= ~(uint32_t)((EC_TR_LINE > 0 ? EC_TR_LINE : 1) - 1);               // slices of whole 64-byte lines (the work area was sized by the caller's number: no smaller)
+    trace_cap &= ~(uint32_t)(EC_TR_LINE - 1);               // slices of whole trace pieces (the work area was sized by the caller's number: no smaller)
     uint4 *heaps = (uint4 *)(((uintptr_t)d_work + 255) & ~(uintptr_t)255);
     uint64_t *traces = (uint64_t *)(heaps + (size_t)grid * 64 * EC_HEAP_SLOTS);
     FMD_HIP_TRY(hipMemsetAsync(t->queue, 0, 4, st));
@@ -845,13 +687,13 @@ extern "C" int fmd_ecfix_dev(fmd_ectab_t *t, void *stream_, size_t n, uint8_t *d
 // Device buffers of the host form, kept in the table handle between calls (`correct` calls it once per 10^6 reads: the work
 // area alone is 256 CUs x 16 waves x 64 lanes x ~12 KB).  One caller at a time owns them; a concurrent call allocates its own.
 struct EcBuf {
-    fmd_ectab *t; bool cached; FmdDevBuf b[5];
+    fmd_ectab *t; bool cached; FmdDevBuf b[EC_N_BUF];
     explicit EcBuf(fmd_ectab *t_) : t(t_), cached(false)
     {
         int expect = 0;
         if (__atomic_compare_exchange_n(&t->buf_busy, &expect, 1, false, __ATOMIC_ACQUIRE, __ATOMIC_RELAXED)) {
             cached = true;
-            for (int i = 0; i < 5; ++i) { b[i].p = t->buf[i]; b[i].bytes = t->buf_bytes[i]; }
+            for (int i = 0; i < EC_N_BUF; ++i) { b[i].p = t->buf[i]; b[i].bytes = t->buf_bytes[i]; }
         }
     }
     void *get(int i, size_t need)   // at least `need` bytes in buffer i (contents are not kept), nullptr when the device is out of memory
@@ -863,12 +705,47 @@ struct EcBuf {
     ~EcBuf()   // back to the handle; a concurrent call's own buffers go with it
     {
         if (!cached) return;
-        for (int i = 0; i < 5; ++i) { t->buf_bytes[i] = b[i].bytes; t->buf[i] = b[i].release(); }
+        for (int i = 0; i < EC_N_BUF; ++i) { t->buf_bytes[i] = b[i].bytes; t->buf[i] = b[i].release(); }
         __atomic_store_n(&t->buf_busy, 0, __ATOMIC_RELEASE);
     }
 };
 
-// Host form: reads whose trace overflows are run again, from their original bytes, with the trace four times as long.
+// The reads of a run whose trace overflowed, as the next run's input: which reads of the run they were, and their ORIGINAL bytes
+struct EcAgain { std::vector<size_t> idx; std::vector<uint64_t> off; std::vector<uint8_t> s, q; };
+
+// One step of the host form: n reads (bytes s and q, offsets off[0] = 0 .. off[n]) up, through fmd_ecfix_dev with traces of `cap` entries, and back into
+// the same arrays.  The reads to run again are copied to `again` as they came: when the info words are back, before the corrected bytes are copied over
+// them.  (The buffers of the arrays were sized for the first run by the caller; no later run is larger.)
+static int ec_run(EcBuf &B, fmd_ectab *t, size_t n, uint8_t *s, uint8_t *q, const uint64_t *off, int step, uint32_t cap, int32_t *info, EcAgain &again)
+{
+    uint8_t *ds = (uint8_t *)B.b[EC_BUF_SEQ].p, *dq = (uint8_t *)B.b[EC_BUF_QUAL].p;
+    uint64_t *doff = (uint64_t *)B.b[EC_BUF_OFF].p;
+    int32_t *dinfo = (int32_t *)B.b[EC_BUF_INFO].p;
+    const size_t wb = fmd_ecfix_work_bytes(t, n, cap);
+    void *dwork = B.get(EC_BUF_WORK, wb);
+    if (!dwork) return FMD_E_NOMEM;
+    FMD_HIP_TRY(hipMemcpy(ds, s, off[n], hipMemcpyHostToDevice));
+    FMD_HIP_TRY(hipMemcpy(dq, q, off[n], hipMemcpyHostToDevice));
+    FMD_HIP_TRY(hipMemcpy(doff, off, (n + 1) * 8, hipMemcpyHostToDevice));
+    FMD_TRY(fmd_ecfix_dev(t, nullptr, n, ds, dq, doff, step, cap, dinfo, dwork, wb));
+    FMD_HIP_TRY(hipMemcpy(info, dinfo, n * 4, hipMemcpyDeviceToHost));
+    again.idx.clear();
+    for (size_t i = 0; i < n; ++i) if ((uint32_t)info[i] == EC_INFO_TRACE_FULL) again.idx.push_back(i);
+    const size_t m = again.idx.size();
+    again.off.assign(m + 1, 0);
+    for (size_t k = 0; k < m; ++k) again.off[k + 1] = again.off[k] + (off[again.idx[k] + 1] - off[again.idx[k]]);
+    again.s.resize(again.off[m] + 16); again.q.resize(again.off[m] + 16);
+    for (size_t k = 0; k < m; ++k) {
+        memcpy(again.s.data() + again.off[k], s + off[again.idx[k]], again.off[k + 1] - again.off[k]);
+        memcpy(again.q.data() + again.off[k], q + off[again.idx[k]], again.off[k + 1] - again.off[k]);
+    }
+    FMD_HIP_TRY(hipMemcpy(s, ds, off[n], hipMemcpyDeviceToHost));
+    FMD_HIP_TRY(hipMemcpy(q, dq, off[n], hipMemcpyDeviceToHost));
+    return FMD_OK;
+}
+
+// Host form: reads whose trace overflows are run again, from their original bytes, with the trace four times as long (rare: a trace of 1024 entries is
+// enough for all but the most error-ridden reads).
 extern "C" int fmd_ecfix_batch(fmd_ectab_t *t, size_t n, uint8_t *seqs, uint8_t *quals, const uint64_t *off, int step, int32_t *info)
 {
     if (!t || (n && (!seqs || !quals || !off || !info))) return FMD_E_ARG;
@@ -879,69 +756,29 @@ extern "C" int fmd_ecfix_batch(fmd_ectab_t *t, size_t n, uint8_t *seqs, uint8_t 
     if (ec_test_hooks_on())
         if (const long hook = ec_test_value(getenv("FMD_ECFIX_TEST_TRACE"), 16)) cap = (uint32_t)hook;
     EcBuf B(t);
-    void *ds = B.get(0, total + 16), *dq = B.get(1, total + 16), *doff = B.get(2, (n + 1) * 8), *dinfo = B.get(3, n * 4);
-    if (!ds || !dq || !doff || !dinfo) return FMD_E_NOMEM;
+    if (!B.get(EC_BUF_SEQ, total + 16) || !B.get(EC_BUF_QUAL, total + 16) || !B.get(EC_BUF_OFF, (n + 1) * 8) || !B.get(EC_BUF_INFO, n * 4)) return FMD_E_NOMEM;
     std::vector<uint64_t> rel(n + 1);   // offsets relative to the first read
     for (size_t i = 0; i <= n; ++i) rel[i] = off[i] - off[0];
     uint8_t *s0 = seqs + off[0], *q0 = quals + off[0];
-    FMD_HIP_TRY(hipMemcpy(ds, s0, total, hipMemcpyHostToDevice));
-    FMD_HIP_TRY(hipMemcpy(dq, q0, total, hipMemcpyHostToDevice));
-    FMD_HIP_TRY(hipMemcpy(doff, rel.data(), (n + 1) * 8, hipMemcpyHostToDevice));
-    {
-        const size_t wb = fmd_ecfix_work_bytes(t, n, cap);
-        void *dwork = B.get(4, wb);
-        if (!dwork) return FMD_E_NOMEM;
-        const int rc = fmd_ecfix_dev(t, nullptr, n, (uint8_t *)ds, (uint8_t *)dq, (uint64_t *)doff, step, cap, (int32_t *)dinfo, dwork, wb);
-        if (rc != FMD_OK) return rc;
-    }
-    FMD_HIP_TRY(hipMemcpy(info, dinfo, n * 4, hipMemcpyDeviceToHost));
-    // the reads to run again (rare: a trace of 1024 entries is enough for all but the most error-ridden reads): their ORIGINAL bytes
-    // are taken from the caller's arrays now, before the corrected batch is copied over them
-    std::vector<size_t> again;
-    for (size_t i = 0; i < n; ++i) if ((uint32_t)info[i] == EC_INFO_TRACE_FULL) again.push_back(i);
-    std::vector<uint64_t> ko(again.size() + 1, 0);
-    for (size_t k = 0; k < again.size(); ++k) ko[k + 1] = ko[k] + (rel[again[k] + 1] - rel[again[k]]);
-    std::vector<uint8_t> keep_s(ko.back() + 16), keep_q(ko.back() + 16);
-    for (size_t k = 0; k < again.size(); ++k) {
-        memcpy(keep_s.data() + ko[k], s0 + rel[again[k]], ko[k + 1] - ko[k]);
-        memcpy(keep_q.data() + ko[k], q0 + rel[again[k]], ko[k + 1] - ko[k]);
-    }
-    FMD_HIP_TRY(hipMemcpy(s0, ds, total, hipMemcpyDeviceToHost));
-    FMD_HIP_TRY(hipMemcpy(q0, dq, total, hipMemcpyDeviceToHost));
-    // re-runs: `todo` indexes `again` (and so the kept originals)
-    std::vector<size_t> todo(again.size());
-    for (size_t k = 0; k < todo.size(); ++k) todo[k] = k;
-    for (int attempt = 0; attempt < 12 && !todo.empty(); ++attempt) {
+    EcAgain again;
+    FMD_TRY(ec_run(B, t, n, s0, q0, rel.data(), step, cap, info, again));   // straight from and to the caller's arrays
+    std::vector<size_t> who(again.idx);   // the caller's read behind each read of `again`
+    for (int attempt = 0; attempt < 12 && !who.empty(); ++attempt) {
         cap *= 4;
-        const size_t m = todo.size();
-        std::vector<uint64_t> o2(m + 1, 0);
-        for (size_t k = 0; k < m; ++k) o2[k + 1] = o2[k] + (ko[todo[k] + 1] - ko[todo[k]]);
-        std::vector<uint8_t> s2(o2[m] + 16), q2(o2[m] + 16);
-        for (size_t k = 0; k < m; ++k) {
-            memcpy(s2.data() + o2[k], keep_s.data() + ko[todo[k]], o2[k + 1] - o2[k]);
-            memcpy(q2.data() + o2[k], keep_q.data() + ko[todo[k]], o2[k + 1] - o2[k]);
-        }
+        EcAgain now;
+        std::swap(now, again);
+        const size_t m = who.size();
         std::vector<int32_t> i2(m);
-        const size_t wb = fmd_ecfix_work_bytes(t, m, cap);
-        void *dwork = B.get(4, wb);
-        if (!dwork) return FMD_E_NOMEM;
-        FMD_HIP_TRY(hipMemcpy(ds, s2.data(), o2[m], hipMemcpyHostToDevice));
-        FMD_HIP_TRY(hipMemcpy(dq, q2.data(), o2[m], hipMemcpyHostToDevice));
-        FMD_HIP_TRY(hipMemcpy(doff, o2.data(), (m + 1) * 8, hipMemcpyHostToDevice));
-        const int rc = fmd_ecfix_dev(t, nullptr, m, (uint8_t *)ds, (uint8_t *)dq, (uint64_t *)doff, step, cap, (int32_t *)dinfo, dwork, wb);
-        if (rc != FMD_OK) return rc;
-        FMD_HIP_TRY(hipMemcpy(s2.data(), ds, o2[m], hipMemcpyDeviceToHost));
-        FMD_HIP_TRY(hipMemcpy(q2.data(), dq, o2[m], hipMemcpyDeviceToHost));
-        FMD_HIP_TRY(hipMemcpy(i2.data(), dinfo, m * 4, hipMemcpyDeviceToHost));
+        FMD_TRY(ec_run(B, t, m, now.s.data(), now.q.data(), now.off.data(), step, cap, i2.data(), again));
         std::vector<size_t> left;
         for (size_t k = 0; k < m; ++k) {
-            const size_t i = again[todo[k]];
+            const size_t i = who[k];
             info[i] = i2[k];
-            if ((uint32_t)i2[k] == EC_INFO_TRACE_FULL) { left.push_back(todo[k]); continue; }
-            memcpy(s0 + rel[i], s2.data() + o2[k], o2[k + 1] - o2[k]);
-            memcpy(q0 + rel[i], q2.data() + o2[k], o2[k + 1] - o2[k]);
+            if ((uint32_t)i2[k] == EC_INFO_TRACE_FULL) { left.push_back(i); continue; }
+            memcpy(s0 + rel[i], now.s.data() + now.off[k], now.off[k + 1] - now.off[k]);
+            memcpy(q0 + rel[i], now.q.data() + now.off[k], now.off[k + 1] - now.off[k]);
         }
-        todo.swap(left);
+        who.swap(left);
     }
-    return todo.empty() ? FMD_OK : FMD_E_OVERFLOW;
+    return who.empty() ? FMD_OK : FMD_E_OVERFLOW;
 }

@@ -326,6 +326,13 @@ def test_trace_overflow_with_refill(gpu, gold, oracle_lib, monkeypatch, recipe):
     assert probed[1] > probed[0] > 0, probed
 
 
+def _tight_caps(want, n):
+    """the trace of n reads whose queue was full, spread over them, rounded up to whole pieces of four entries"""
+    full_q = np.flatnonzero(want[5] >= 255)
+    picks = full_q[np.linspace(0, len(full_q) - 1, n).astype(np.int64)]
+    return tuple(sorted({(int(want[4][i]) + 3) & ~3 for i in picks}))
+
+
 @pytest.mark.parametrize("recipe", RECIPES)
 def test_trace_full_word_of_the_device_form(gpu, gold, oracle_lib, monkeypatch, recipe):
     """fmd_ecfix_dev at trace_cap 16, 64, 1024: exactly the reads whose trace (root included) is longer than that, by the oracle's count, get
@@ -339,15 +346,39 @@ def test_trace_full_word_of_the_device_form(gpu, gold, oracle_lib, monkeypatch, 
         caps = (16, 64, 1024) + ((65536,) if long_reads else (8192,))  # (every 300-base read of the recipe needs more than 16 384 entries, none 65 536)
         # ... and capacities that this or that read whose queue was full just fits (its trace rounded up to whole pieces of four entries): a path
         # pushed or dropped against the budget rule of correct.c:173-175 moves the read's trace count, whether or not it changes the read's result
-        full_q = np.flatnonzero(want[5] >= 255)
-        picks = full_q[np.linspace(0, len(full_q) - 1, 2 if long_reads else 24).astype(np.int64)]
-        tight = tuple(sorted({(int(want[4][i]) + 3) & ~3 for i in picks}))
+        tight = _tight_caps(want, 2 if long_reads else 24)
         assert len(tight) >= (2 if long_reads else 12)
         for cap in caps + tight:
             got = t.dev(seqs, quals, 5, cap)
             over = want[4] > cap
             if cap in caps:
                 assert (~over).sum() >= 10 if cap == caps[-1] else over.sum() >= 10, (cap, over.sum())
+            assert np.array_equal(got[3] == TRACE_FULL, over), (cap, np.flatnonzero((got[3] == TRACE_FULL) != over)[:8])
+            _same_reads(got, want, ~over, "cap %d" % cap)
+
+
+def test_trace_capacity_is_rounded_down_to_whole_pieces(gpu, gold, oracle_lib, monkeypatch):
+    """fmd_ecfix_dev at capacities that are no multiple of four: c + 1, c + 2, c + 3 over four of the tight values c of the test above (the
+    first recipe, step 5; the work area sized by the number passed).  The kernel's capacity is that number rounded DOWN to whole trace pieces:
+    exactly the reads whose oracle trace is longer than cap & ~3 get FMD_ECFIX_TRACE_FULL, every other read is the oracle's (a piece is four entries,
+    EC_TR_LINE, in the build that ships: a variant built with another piece length rounds otherwise and fails here).  The values c are
+    chosen from the oracle's counts so that the rounding is observed: first those with a read whose trace is longer than c but no longer than
+    c + 3 -- a read that the unrounded capacity would have passed --, then others up to four."""
+    tab, seqs, quals = _hard(gold, "staged")
+    want = _hard_want(gold, "staged", 5)
+    _assert_hard_floors(want)
+    _hooks(monkeypatch)
+    tmax = want[4].astype(np.int64)
+    tight = _tight_caps(want, 24)
+    between = [c for c in tight if ((tmax > c) & (tmax <= c + 3)).any()]
+    cs = between + [c for c in tight if c not in between][: max(0, 4 - len(between))]
+    caps = [c + k for c in cs for k in (1, 2, 3)]
+    assert len(cs) >= 4 and all(c % 4 == 0 for c in cs)
+    assert sum(bool(((tmax > (cap & ~3)) & (tmax <= cap)).any()) for cap in caps) >= 2, "no capacity whose rounding decides about a read"
+    with _Tab(gpu, 17, *tab) as t:
+        for cap in caps:
+            got = t.dev(seqs, quals, 5, cap)
+            over = tmax > (cap & ~3)
             assert np.array_equal(got[3] == TRACE_FULL, over), (cap, np.flatnonzero((got[3] == TRACE_FULL) != over)[:8])
             _same_reads(got, want, ~over, "cap %d" % cap)
 
