@@ -25,6 +25,10 @@ __device__ __forceinline__ bool walk_lf_shares(uint64_t k, uint64_t x0, uint64_t
     return fmd_in_block(k, fmd_blk_of(x0 - 1), o) || fmd_in_block(k, fmd_blk_of(x0 - 1 + sz), o);
 }
 
+// cnt[c] for a lane's own c, by selects over the six values the kernel holds in SGPRs: ix.cnt[c] is a load from the argument segment, one more memory access that the
+// row and the interval of the next step wait for behind every gather, and whose s_waitcnt waits for every other load in flight (profiles/walk_narrow32)
+__device__ __forceinline__ uint64_t walk_cnt(const FmdIndexView &ix, int c) { return sel6(c, ix.cnt[0], ix.cnt[1], ix.cnt[2], ix.cnt[3], ix.cnt[4], ix.cnt[5]); }
+
 // every 4th base: the word moves into its place of the 16-byte group; every 16th: one store
 #define WALK_STASH_WORD()                                                                                  \
     do {                                                                                                   \
@@ -356,7 +360,7 @@ __device__ __forceinline__ void walk_run(const FmdIndexView &ix, size_t n, const
             wtk = fmd_block_rank1z(r.bk, r.t, r.nk, c, r.blk_k, wr0);              // rank_c(x0 - 1), rank_$(x0 - 1)
             wD = M0;
             const uint64_t Mc = sel6(c, M0, M1, M2, M3, M4, M5);
-            k = ix.cnt[c] + wtk + __popcll(Mc & bits_below((int)o + 1)) - 1;
+            k = walk_cnt(ix, c) + wtk + __popcll(Mc & bits_below((int)o + 1)) - 1;
         } else if (st == WK_LF || st == WK_BOTH) { // LF step at row k: base = BWT[k], k' = cnt[c] + rank_c(k) - 1
             uint32_t kb_ = r.blk_k, off;
             const bool in_k = fmd_in_block(k, r.blk_k, off);     // (WK_LF: the block asked for; WK_BOTH: one of the extension's two)
@@ -366,7 +370,7 @@ __device__ __forceinline__ void walk_run(const FmdIndexView &ix, size_t n, const
             const uint4 v = img[(int)(off >> 5) ^ tt];
             const uint32_t bit = off & 31;
             c = (int)(((v.x >> bit) & 1) | ((v.y >> bit) & 1) << 1 | ((v.z >> bit) & 1) << 2);
-            k = ix.cnt[c] + fmd_block_rank1(img, tt, off + 1, c, kb_) - 1;
+            k = walk_cnt(ix, c) + fmd_block_rank1(img, tt, off + 1, c, kb_) - 1;
             if (st == WK_LF && depth > 0 && tab) { // still inside the prefix table: no extension, just collect the base
                 if (c < 1 || c > 4) { // the sequence ends, or an ambiguous base: start over on the ordinary path
                     k = ids[gs]; depth = 0; pack = 0; pk0 = pk1 = pk2 = 0; tab = false;
@@ -428,7 +432,7 @@ __device__ __forceinline__ void walk_run(const FmdIndexView &ix, size_t n, const
                     } else flags |= FMD_OVLP_F_OVERFLOW;
                     ++npush;
                 }
-                x0 = sel6(c, ix.cnt[0], ix.cnt[1], ix.cnt[2], ix.cnt[3], ix.cnt[4], ix.cnt[5]) + sel6(c, tk[0], tk[1], tk[2], tk[3], tk[4], tk[5]);
+                x0 = walk_cnt(ix, c) + sel6(c, tk[0], tk[1], tk[2], tk[3], tk[4], tk[5]);
                 uint64_t before = 0;             // sizes ordered before c: 0 <4 <3 <2 <1 <5
                 if (c != 0) before += s[0];
                 if (c == 3 || c == 2 || c == 1 || c == 5) before += s[4];
