@@ -98,6 +98,14 @@ __device__ __forceinline__ uint64_t win64(uint32_t w0, uint32_t w1, uint32_t w2,
     const uint32_t lo = __builtin_amdgcn_alignbit(w1, w0, sh), hi = __builtin_amdgcn_alignbit(w2, w1, sh);
     return (uint64_t)hi << 32 | lo;
 }
+// The positions of a window (planes X, Y, Z) whose symbol sorts before c in the order of fm6_extend's x[1] sums, 0 < 4 < 3 < 2 < 1 < 5 (exact.c:81-86);
+// cx, cy, cz = all ones where c has the plane's bit.  '$' sorts before every base; T (z alone) before c = 3, 2, 1, 5: c has x or y; G (x and y) before
+// 2, 1, 5: exactly one of them; C (y alone) before 1, 5: x without y; A (x alone) before 5: x and z.  Without a branch on c: the lanes of a wave differ in it.
+template <class T>
+__device__ __forceinline__ T win_before(T X, T Y, T Z, T cx, T cy, T cz)
+{
+    return ~(X | Y | Z) | (Z & ~X & (cx | cy)) | (X & Y & (cx ^ cy)) | (Y & ~X & cx & ~cy) | (X & ~Y & ~Z & cx & cz);
+}
 __device__ __forceinline__ uint64_t range64(uint32_t a, uint32_t b) // bits [a, b), b <= 64
 {
     return bits_below((int)b) & ~bits_below((int)a);

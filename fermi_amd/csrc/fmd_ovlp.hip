@@ -28,6 +28,7 @@ struct OvlBatch {
     // a batch taken from the sorted order of a larger job (fmd_ovlp_sorted_dev): slot t of the batch is row gidx[t] of rec, nei, seq and of
     // park, where WALK_HEAD left it; nullptr: slot = row, the walk starts at the sentinel of ids[t]
     const uint32_t *gidx; FmdWalkPark *park;
+    const uint32_t *keys;   // ... and, where the caller has them, the sort key of every slot (k_ovl_park_keys); nullptr otherwise
 };
 
 // The second pass of a sorted job through k_ovl_walk<WALK_TAIL2> (rows written by the walk, FMD_WALK_TAIL2=0: the A/B switch), and with the work
@@ -44,6 +45,7 @@ static bool ovl_tail2_cls(const OvlBatch &o)
 }
 static int ovl_use_fast(void) { const char *ef = getenv("FMD_OVLP_FAST"); return fmd_nei_fast_available() && !(ef && atoi(ef) == 0); }   // FMD_OVLP_FAST=0: A/B switch, every strand through the general group kernels
 static int ovl_grp_down(void) { const char *e = getenv("FMD_GRP_DOWN"); return !(e && atoi(e) == 0); }
+static int ovl_walk_phase(void) { const char *e = getenv("FMD_WALK_PHASE"); return !(e && atoi(e) == 0); }
 static int ovl_min_cls(void) { const char *e = getenv("FMD_GRP4"); return e && atoi(e) == 0 ? 1 : 0; }                                  // FMD_GRP4=0: no groups of 4 (as fmd_launch_classify)
 
 // phase A: LF-walk + overlap_intv + fm6_is_contained, then the read-order copy.  per_cu > 0 bounds the
@@ -72,6 +74,8 @@ static void ovl_phase_a(const OvlBatch &o, hipStream_t st, size_t b, size_t np, 
     if (ovl_tail2_cls(o)) {   // the work lists of phase B made here (part 0 of the batch: a sorted job's batches are not pipelined)
         a.cls = o.cls + b * FMD_CLS_WORDS_PER_STRAND; a.use_fast = ovl_use_fast(); a.min_cls = ovl_min_cls();
     }
+    // the strands of one minimizer in phase on the genome (k_ovl_walk<WALK_TAIL2>; FMD_WALK_PHASE=0: the A/B switch, free-running admission)
+    if (o.keys && ovl_walk_phase()) a.keys = o.keys + b;
     fmd_launch_walk_tail2(o.h, st, a, per_cu);
 }
 
@@ -214,7 +218,7 @@ extern "C" int fmd_ovlp_dev(fmd_dev_t *h, void *stream_, size_t n, const uint64_
     o.listA = (fmd_intv_t *)((uint8_t *)d_work + align_up(n * (size_t)o.stride_r, 256));
     o.listB = (fmd_intv_t *)((uint8_t *)o.listA + align_up(n * (size_t)o.cap * sizeof(fmd_intv_t), 256));
     o.cls = (uint32_t *)((uint8_t *)o.listB + align_up(n * (size_t)o.cap * sizeof(fmd_intv_t), 256));
-    o.rec = d_rec; o.nei = d_nei; o.seq = d_seq; o.gidx = nullptr; o.park = nullptr;
+    o.rec = d_rec; o.nei = d_nei; o.seq = d_seq; o.gidx = nullptr; o.park = nullptr; o.keys = nullptr;
 
     int parts, walk_cu, grp_cu, fast_cu;
     ovl_pipe_config(n, parts, walk_cu, grp_cu, fast_cu);
@@ -323,7 +327,7 @@ extern "C" int fmd_ovlp_head_dev(fmd_dev_t *h, void *stream_, size_t n, const ui
 }
 
 // pass 2 + fm6_get_nei for np parked strands: slot t of the call = row d_rows[t] of d_park, d_rec, d_nei and d_seq
-static int ovl_tail(fmd_dev *h, hipStream_t st, size_t np, const uint32_t *rows, FmdWalkPark *park, const uint64_t *d_ids, int min_match, uint32_t max_len, uint32_t max_nei,
+static int ovl_tail(fmd_dev *h, hipStream_t st, size_t np, const uint32_t *rows, const uint32_t *keys, FmdWalkPark *park, const uint64_t *d_ids, int min_match, uint32_t max_len, uint32_t max_nei,
                     fmd_ovlp_rec_t *d_rec, fmd_intv_t *d_nei, uint8_t *d_seq, uint32_t seq_stride, uint8_t *area, size_t area_strands)
 {
     OvlBatch o;
@@ -335,7 +339,7 @@ static int ovl_tail(fmd_dev *h, hipStream_t st, size_t np, const uint32_t *rows,
     o.listB = (fmd_intv_t *)((uint8_t *)o.listA + align_up(area_strands * (size_t)o.cap * sizeof(fmd_intv_t), 256));
     o.cls = (uint32_t *)((uint8_t *)o.listB + align_up(area_strands * (size_t)o.cap * sizeof(fmd_intv_t), 256));
     o.rec = d_rec; o.nei = d_nei; o.seq = d_seq; o.park = park;
-    o.gidx = rows;
+    o.gidx = rows; o.keys = keys;
     ovl_phase_a(o, st, 0, np, 0);
     return ovl_phase_b(o, st, 0, np, 0, 0, 0);
 }
@@ -347,7 +351,7 @@ extern "C" int fmd_ovlp_tail_dev(fmd_dev_t *h, void *stream_, size_t np, const u
     if (np == 0) return FMD_OK;
     if (np >= 0xffffff00ull || !fmd_ovlp_two_pass_ok(h, np, min_match, max_len) || work_bytes < fmd_ovlp_work_bytes(np, max_len, min_match)) return FMD_E_ARG;
     FMD_HIP_TRY(hipSetDevice(h->device));
-    const int rc = ovl_tail(h, (hipStream_t)stream_, np, d_rows, (FmdWalkPark *)d_park, nullptr, min_match, max_len, max_nei, d_rec, d_nei, d_seq, seq_stride, (uint8_t *)d_work, np);
+    const int rc = ovl_tail(h, (hipStream_t)stream_, np, d_rows, nullptr, (FmdWalkPark *)d_park, nullptr, min_match, max_len, max_nei, d_rec, d_nei, d_seq, seq_stride, (uint8_t *)d_work, np);
     if (rc != FMD_OK) return rc;
     FMD_CHECK_LAUNCH("sorted overlap job: tail");
     return FMD_OK;
@@ -387,7 +391,7 @@ extern "C" int fmd_ovlp_sorted_dev(fmd_dev_t *h, void *stream_, size_t n, const 
     // pass 2 + fm6_get_nei, batch by batch in that order
     for (size_t b = 0; b < n; b += batch) {
         const size_t np = n - b < batch ? n - b : batch;
-        const int rc = ovl_tail(h, st, np, sorted + b, park, d_ids, min_match, max_len, max_nei, d_rec, d_nei, d_seq, seq_stride, w + L.batch_area, batch);
+        const int rc = ovl_tail(h, st, np, sorted + b, (const uint32_t *)(w + L.keys_b) + b, park, d_ids, min_match, max_len, max_nei, d_rec, d_nei, d_seq, seq_stride, w + L.batch_area, batch);
         if (rc != FMD_OK) return rc;
     }
     FMD_CHECK_LAUNCH("sorted overlap job");

@@ -22,6 +22,7 @@ struct WalkArgs {
     const uint4 *adm = nullptr;         // WALK_HEAD: two words per item (k_ovl_head_adm)
     int pair_from = 0;                  // WALK_HEAD: the depth below FMD_WALK_SPLIT at which a narrow strand is handed to k_ovl_pair; 0 = none is
     const uint32_t *gidx = nullptr;     // the two tails: slot of the batch -> row of park, rec (and seq_out)
+    const uint32_t *keys = nullptr;     // WALK_TAIL2: the sort key of every slot (k_ovl_park_keys), strands of one key in phase on the genome; null = free-running admission
     uint8_t *seq_out = nullptr;         // WALK_TAIL2: the caller's rows in read order
     uint32_t seq_stride = 0;
     uint32_t *redo = nullptr;           // WALK_TAIL2: [0] number, [1 ..] slots of the strands with an N (k_ovl_seq_redo)

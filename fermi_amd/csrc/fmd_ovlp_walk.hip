@@ -14,7 +14,10 @@
 #ifndef FMD_HEAD_AUX
 #define FMD_HEAD_AUX 0
 #endif
-enum { WK_IDLE = 0, WK_LF, WK_EXT, WK_BOTH, WK_RIGHT, WK_ADM1, WK_ADM2, WK_DONE };   // (WK_DONE: WALK_TAIL2 only)
+enum { WK_IDLE = 0, WK_LF, WK_EXT, WK_BOTH, WK_RIGHT, WK_ADM1, WK_ADM2, WK_WAIT, WK_DONE };   // (WK_WAIT, WK_DONE: WALK_TAIL2 only)
+// WALK_TAIL2 in phase: a lane in WK_ADM2 carries six bits of its sort key above the state (the minimizer's offset, and 32 = the key has a minimizer)
+#define WK_KEY_SHIFT 4
+#define WK_STATE_MASK ((1 << WK_KEY_SHIFT) - 1)
 // can the LF step at row k be read from a block the backward extension of [x0, x0 + sz) brings in anyway (the block of x0 - 1, or
 // the block of its other end when that one does not reach it)?
 __device__ __forceinline__ bool walk_lf_shares(uint64_t k, uint64_t x0, uint64_t sz)
@@ -76,10 +79,20 @@ enum { WALK_WHOLE = 0, WALK_HEAD = 1, WALK_TAIL = 2, WALK_TAIL2 = 3 };   // (FMD
 // is through its sequence writes the caller's row itself, in read order, from those words at the strand's close (walk_emit_row: ~250 instructions for
 // the wave whoever takes part, where the separate kernel read 112 + wrote 100 bytes per strand and cost the step 14 ms of its 272).  A sequence that
 // holds an N (2 bits do not) is put on a list and k_ovl_seq_redo writes its row afterwards from what WALK_HEAD parked.
-// A strand closes in the step after its last (WK_DONE, top of the loop): the record in one piece, the row, its work list.  Reads of one length finish a wave
-// together, so the close has company by itself.  (Starting every strand 16 - o steps late, o = the low five bits of its sort key, so that the strands of one
-// minimizer stand at the same genome position in every step and share their rank blocks' lines: measured, 30 % fewer lines across L2 were expected, the step
-// gained 2.6 ms of 215, and it was not kept -- profiles/walk_phase)
+// Two admissions.  Free-running (WalkArgs::keys == nullptr; FMD_WALK_PHASE=0: the A/B switch): a lane takes the next strand as soon as it is idle and closes
+// its strand in the step after its last; reads of one length finish a wave together, so the close has company by itself.  In phase on the genome (keys
+// given: the batches of fmd_ovlp_sorted_dev): the sorted order puts the strands of one minimizer into neighbouring lanes, but admitted together they
+// advance in step in DEPTH, so two of them whose ends lie d positions apart ask for the same rank block d wave steps apart, and a block survives one or
+// two steps of an XCD's resident waves in its L2.  A strand whose minimizer lies o bases from its end therefore starts omax - o steps late (o = the low
+// five bits of its key, omax the largest of the wave's generation).  The strands of a key then stand at the same genome position in every step:
+// their nested intervals ask for the same block in the same wave instruction and share its line: half the bytes fetched and a third fewer requests per
+// launch.  The price: up to 16 idle steps per lane and generation, a wave takes new strands only when all its lanes are idle (a generation
+// lasts as long as its longest strand: reads of one length, which is what a job of at most WALK_LS_BASES bases holds), and the lanes of a generation
+// finish in up to 17 different steps and wait in WK_DONE for a close in company (top of the loop).  On the parent's narrow turn those idle steps took back
+// what the shared lines gave (profiles/walk_phase: the kernel left the L2 bound and met the issue bound); with the turn in 32-bit words (below) it has the
+// instructions to spare, and the two together are what ships: the launch 25 -> 21 ms, the step 202 -> 184.5 ms (profiles/walk_phase32).
+// The phase start costs no register: the six bits it needs of a strand's key (offset, has a minimizer) come in through `pack`, idle between the ticket and
+// WK_ADM1, ride in the spare bits of `st` for the one step to WK_ADM2 (WK_KEY_SHIFT), and the countdown of a waiting lane is `npush`.
 #define WALK_LS_WORDS 7
 #define WALK_LS_BASES (16 * WALK_LS_WORDS)
 #define WALK_F_HASN 0x80000000u       // (in the walk's `flags` register only: never stored)
@@ -87,7 +100,12 @@ enum { WALK_WHOLE = 0, WALK_HEAD = 1, WALK_TAIL = 2, WALK_TAIL2 = 3 };   // (FMD
 #define WALK_F_W63 0x40000000u
 #define WALK_F_WNARROW 0x20000000u
 #define WALK_F_W32 0x10000000u
-#define WALK_F_INTERNAL 0xf0000000u
+// two small fields of the walk itself, kept in `flags` and not in registers of their own: the strand is left-contained or its right extension found another
+// size (the record's status -3), and the base an LF step found for the extension that follows it in a gather of its own (WK_LF -> WK_EXT)
+#define WALK_F_CONTAINED 0x08000000u
+#define WALK_F_CPEND_SHIFT 24
+#define WALK_F_CPEND (7u << WALK_F_CPEND_SHIFT)
+#define WALK_F_INTERNAL 0xff000000u
 struct __attribute__((packed, aligned(4))) WalkU4 { uint32_t x, y, z, w; };   // a 16-byte store at a 4-byte aligned address
 // four bases, 2 bits each, first found (= LAST in read order) in the low bits -> their nt6 codes as the four bytes of a word in read order
 __device__ __forceinline__ uint32_t walk_expand4(uint32_t win8)
@@ -143,7 +161,8 @@ __device__ __forceinline__ void walk_run(const FmdIndexView &ix, size_t n, const
                                          fmd_intv_t *__restrict__ listA, uint32_t cap, uint32_t *__restrict__ queue, uint32_t tickets,
                                          FmdWalkPark *__restrict__ park, const uint4 *__restrict__ adm, int pair_from,
                                          const uint32_t *__restrict__ gidx, uint8_t *__restrict__ seq_out, uint32_t seq_stride,
-                                         uint32_t *__restrict__ redo, uint32_t *__restrict__ cls, int use_fast, int min_cls)
+                                         uint32_t *__restrict__ redo, uint32_t *__restrict__ cls, int use_fast, int min_cls,
+                                         const uint32_t *__restrict__ keys)
 {
     FMD_DECLARE_COMPACT_LDS();
     __shared__ uint32_t walk_ls[MODE == WALK_TAIL2 ? 64 * WALK_LS_WORDS : 1];   // WALK_TAIL2: the lane's bases, word w of lane l at [w * 64 + l]
@@ -151,8 +170,7 @@ __device__ __forceinline__ void walk_run(const FmdIndexView &ix, size_t n, const
     constexpr int WAUX = MODE == WALK_HEAD ? FMD_HEAD_AUX : FMD_GLDS_AUX;   // pass 1 never asks for a line twice (strands in id order: every gather is a DRAM miss)
     size_t sid = 0;
     size_t gs = 0;                        // the strand's row in rec[] (WALK_TAIL: gidx[sid], otherwise sid)
-    int st = WK_IDLE, c_pend = 0, ret = 0;
-    int fin_cls = -1;                     // WALK_TAIL2 with the work lists of get_nei made here (cls != nullptr): the list of the strand this lane has just finished
+    int st = WK_IDLE;
     uint32_t depth = 0, npush = 0, pack = 0, flags = 0;
     uint32_t pk0 = 0, pk1 = 0, pk2 = 0;   // the stash is written 16 bases at a time (one 16-byte store per lane instead of four words)
     uint64_t k = 0, x0 = 0, x1 = 0, sz = 0;
@@ -166,31 +184,43 @@ __device__ __forceinline__ void walk_run(const FmdIndexView &ix, size_t n, const
     uint4 adm_a = make_uint4(0, 0, 0, 0), adm_b = make_uint4(0, 0, 0, 0);   // WALK_HEAD: the admission record of a strand on its way in (WK_ADM1)
     FmdTickets tk_;
     constexpr bool GUIDED = MODE != WALK_WHOLE;   // guided ticket chunks (fmd_wave.h) in the two passes of a sorted job, fixed ones in the one-pass walk
-    fmd_tickets_init(tk_, queue, tickets, GUIDED ? n : 0);
+    // WALK_TAIL2 with the sorted keys at hand: the strands of one minimizer in phase on the genome (see WALK_TAIL2 above).  A generation is 64 consecutive
+    // strands of the sorted order: fixed chunks of 64 tickets (fmd_launch_walk_tail2), since a guided chunk ends anywhere and the rest of the generation would
+    // come from the chunk reserved ahead, somewhere else in the order
+    const bool phase = MODE == WALK_TAIL2 && keys != nullptr;
+    const size_t n_guided = GUIDED && !phase ? n : 0;
+    fmd_tickets_init(tk_, queue, tickets, n_guided);
     for (;;) {
-        // The close of a strand that is through its right extension (WK_DONE), in the step after its last: the record in one piece, the row in read order,
-        // the work list the strand belongs on.  Here and not where the right extension ends, so that the wave meets walk_emit_row's ~250 instructions in
-        // one place, with every lane that finished in the last step (reads of one length: the whole wave).
-        if (MODE == WALK_TAIL2 && st == WK_DONE) {   // k = fm_retrieve's row, x0 = k[0], x1 and sz = the two '$' ranks of the right extension (k[1], k[2])
-            uint4 *o = (uint4 *)(rec + gs);
-            o[0] = make_uint4((uint32_t)k, (uint32_t)(k >> 32), (uint32_t)x0, (uint32_t)(x0 >> 32));
-            o[1] = make_uint4((uint32_t)x1, (uint32_t)(x1 >> 32), (uint32_t)sz, (uint32_t)(sz >> 32));
-            o[2] = make_uint4(depth, ret < 0 ? (uint32_t)-3 : 0u, npush, (uint32_t)-1);           // len, status, n_ovlp, rbeg
-            o[3] = make_uint4(0u, 0u, flags & ~WALK_F_INTERNAL, 2u);                               // ext_len, n_nei, flags, reserved = 2 | lfork = 0
-            // (the caller's copy in read order: from LDS a lane writes it without holding up the others; every sequence with a complete record
-            // gets its row -- k_ovl_seq_out's conditions)
-            if (flags & WALK_F_HASN) redo[1 + atomicAdd(redo, 1u)] = (uint32_t)sid;
-            else walk_emit_row(walk_ls + fmd_lane(), depth, seq_out + gs * (size_t)seq_stride);
-            if (cls != nullptr && ret >= 0 && npush > 0 && !(flags & FMD_OVLP_F_OVERFLOW)) {   // k_ovl_classify's rule (fmd_ovlp_grp.hip)
-                int c = FMD_GRP_CLASSES;
-                if ((flags & WALK_F_W63) && depth < 65535u) {
+        int fin_cls = -1;                 // WALK_TAIL2 with the work lists of get_nei made here (cls != nullptr): the list of the strand this lane closes in this step
+        if (MODE == WALK_TAIL2) {
+            // The close of the strands that are through their right extension (WK_DONE): the record in one piece, the row in read order, the work list the
+            // strand belongs on.  Free-running, a strand closes in the step after its last; in phase, the strands of a generation finish in up to 17
+            // different steps, and walk_emit_row costs the wave its ~250 instructions whoever takes part: they close in company -- when half the wave
+            // waits (the rule of k_ovl_nei_lane's full round) or nobody is walking any more.
+            const uint64_t dn = __ballot(st == WK_DONE);
+            if (dn && ((uint32_t)__popcll(dn) >= (phase ? 32u : 1u) || __ballot(st != WK_IDLE && st != WK_DONE) == 0)) {
+                if (st == WK_DONE) {   // k = fm_retrieve's row, x0 = k[0], x1 and sz = the two '$' ranks of the right extension (k[1], k[2])
+                    uint4 *o = (uint4 *)(rec + gs);
+                    o[0] = make_uint4((uint32_t)k, (uint32_t)(k >> 32), (uint32_t)x0, (uint32_t)(x0 >> 32));
+                    o[1] = make_uint4((uint32_t)x1, (uint32_t)(x1 >> 32), (uint32_t)sz, (uint32_t)(sz >> 32));
+                    o[2] = make_uint4(depth, (flags & WALK_F_CONTAINED) ? (uint32_t)-3 : 0u, npush, (uint32_t)-1);           // len, status, n_ovlp, rbeg
+                    o[3] = make_uint4(0u, 0u, flags & ~WALK_F_INTERNAL, 2u);                               // ext_len, n_nei, flags, reserved = 2 | lfork = 0
+                    // (the caller's copy in read order: from LDS a lane writes it without holding up the others; every sequence with a complete record
+                    // gets its row -- k_ovl_seq_out's conditions)
+                    if (flags & WALK_F_HASN) redo[1 + atomicAdd(redo, 1u)] = (uint32_t)sid;
+                    else walk_emit_row(walk_ls + fmd_lane(), depth, seq_out + gs * (size_t)seq_stride);
+                    if (cls != nullptr && !(flags & WALK_F_CONTAINED) && npush > 0 && !(flags & FMD_OVLP_F_OVERFLOW)) {   // k_ovl_classify's rule (fmd_ovlp_grp.hip)
+                        int c = FMD_GRP_CLASSES;
+                        if ((flags & WALK_F_W63) && depth < 65535u) {
 #pragma unroll
-                    for (int kk = FMD_GRP_CLASSES - 1; kk >= 0; --kk) if (kk >= min_cls && npush <= (uint32_t)fmd_grp_size(kk)) c = kk;
-                    if (c < FMD_GRP_CLASSES && (flags & WALK_F_WNARROW) && use_fast) c += FMD_GRP_CLASSES + 1 + ((flags & WALK_F_W32) ? FMD_GRP_CLASSES : 0);
+                            for (int kk = FMD_GRP_CLASSES - 1; kk >= 0; --kk) if (kk >= min_cls && npush <= (uint32_t)fmd_grp_size(kk)) c = kk;
+                            if (c < FMD_GRP_CLASSES && (flags & WALK_F_WNARROW) && use_fast) c += FMD_GRP_CLASSES + 1 + ((flags & WALK_F_W32) ? FMD_GRP_CLASSES : 0);
+                        }
+                        fin_cls = c;
+                    }
+                    st = WK_IDLE;
                 }
-                fin_cls = c;
             }
-            st = WK_IDLE;
         }
         if (MODE == WALK_TAIL2 && cls != nullptr) {
             // k_ovl_classify's work, by the lanes that have just closed a strand: one returning atomic per
@@ -223,21 +253,23 @@ __device__ __forceinline__ void walk_run(const FmdIndexView &ix, size_t n, const
                 }
             }
         }
-        const size_t my = fmd_tickets_take(tk_, queue, st == WK_IDLE && !exhausted, GUIDED ? n : 0);
-        if (st == WK_IDLE && !exhausted) {
+        // in phase, a wave takes strands by generation: only when all its lanes are idle, one whole chunk of 64 tickets (lanes that find the queue drained stay idle)
+        const bool gen_open = !phase || __ballot(st != WK_IDLE) == 0;
+        const size_t my = fmd_tickets_take(tk_, queue, st == WK_IDLE && !exhausted && gen_open, n_guided);
+        if (st == WK_IDLE && !exhausted && gen_open) {
             // The two passes of a sorted job take a strand in over one (WALK_HEAD) or two (WALK_TAIL) wave steps: the loads are issued
             // here and complete under the gather of the other lanes (WK_ADM1 / WK_ADM2 below).  A chain of dependent loads in front of
             // the gather -- id, tail-table entry, two prefix-table entries, as the one-pass walk does it -- stalls all 64 lanes of a wave
             // whose strands live 20 steps: k_ovl_head_adm resolves that chain for every strand beforehand, streaming.
             if (TAILM) {
-                if (my < n) { sid = my; gs = gidx[my]; st = WK_ADM1; }
+                if (my < n) { sid = my; gs = gidx[my]; if (phase) pack = keys[my]; st = WK_ADM1; }   // (pack: nobody's until WK_ADM1 reads the parked line into it)
                 else exhausted = true;
             } else if (MODE == WALK_HEAD) {
                 if (my < n) { sid = my; adm_a = adm[2 * my]; adm_b = adm[2 * my + 1]; st = WK_ADM1; }
                 else exhausted = true;
             } else
             if (my < n) {
-                sid = my; gs = my; k = ids[gs]; depth = 0; npush = 0; pack = 0; pk0 = pk1 = pk2 = 0; flags = 0; ret = 0; st = WK_LF; tab = tab_ok;
+                sid = my; gs = my; k = ids[gs]; depth = 0; npush = 0; pack = 0; pk0 = pk1 = pk2 = 0; flags = 0; st = WK_LF; tab = tab_ok;
                 // the first ptab_d LF steps were taken when the index was loaded (FmdIndexView::tail): pick the walk up behind them
                 const unsigned long long te = (tab_ok && ix.tail && k < ix.n_seq) ? ix.tail[k] : ~0ull;
                 if (te != ~0ull) {
@@ -284,9 +316,13 @@ __device__ __forceinline__ void walk_run(const FmdIndexView &ix, size_t n, const
         const bool was_two_phase = r.two_phase;
         fmd_wave_l_ready<WAUX>(ix, fmd_lds, r);
         if (st == WK_IDLE || skip || (MODE == WALK_TAIL2 && st == WK_DONE)) continue;
+        if (MODE == WALK_TAIL2 && st == WK_WAIT) {   // a waiting lane posts no request and is not idle
+            if (--npush == 0) st = walk_lf_shares(k, x0, sz) ? WK_BOTH : WK_LF;   // (npush: the countdown, 0 again when the walk starts)
+            continue;
+        }
         if (MODE == WALK_HEAD && st == WK_ADM1) {   // the admission record has arrived (FmdHeadAdm, k_ovl_head_adm)
             gs = adm_a.x;
-            depth = 0; npush = 0; pack = 0; pk0 = pk1 = pk2 = 0; flags = 0; ret = 0;
+            depth = 0; npush = 0; pack = 0; pk0 = pk1 = pk2 = 0; flags = 0;
             if (adm_b.w & 1u) {   // no tail-table entry: from the sentinel, on the ordinary path
                 k = (uint64_t)(adm_b.y & 0xffu) << 32 | adm_a.y; st = WK_LF; tab = tab_ok;
             } else {
@@ -310,18 +346,40 @@ __device__ __forceinline__ void walk_run(const FmdIndexView &ix, size_t n, const
             const uint4 *pp = (const uint4 *)(park + gs);   // registers the state will live in (the loads land under the next gather)
             const uint4 a = pp[0], b = pp[1], cb = pp[2];
             k = (uint64_t)a.y << 32 | a.x; x0 = (uint64_t)a.w << 32 | a.z; x1 = (uint64_t)b.y << 32 | b.x; sz = (uint64_t)b.w << 32 | b.z;
-            pk0 = cb.x; pk1 = cb.y; pk2 = cb.z; pack = cb.w;
+            // (WALK_TAIL2 has no stash registers of its own: the parked bases wait one step in npush, depth and flags, which belong to nobody until WK_ADM2 sets
+            // all three.  NOTHING may read depth, npush or flags of a lane in WK_ADM2.  It buys three VGPRs: 125 with it, 128 -- the limit, nothing spilled --
+            // with pk0..2 carried instead (tools/kernel_resources.py), so it can be undone as long as nothing else wants those three.)
+            // In phase, pack holds the strand's sort key since the ticket: what WK_ADM2 needs of it moves into the spare bits of st before the line takes pack.
             st = WK_ADM2;
+            if (MODE == WALK_TAIL2 && phase) st |= (int)((pack & 31u) | (pack < 0xfffffffeu ? 32u : 0u)) << WK_KEY_SHIFT;
+            if (MODE == WALK_TAIL2) { npush = cb.x; depth = cb.y; flags = cb.z; pack = cb.w; }
+            else { pk0 = cb.x; pk1 = cb.y; pk2 = cb.z; pack = cb.w; }
             continue;
         }
-        if (MODE == WALK_TAIL2 && st == WK_ADM2) {
+        if (MODE == WALK_TAIL2 && (st & WK_STATE_MASK) == WK_ADM2) {
+            // The lanes of a generation arrive here together.  A strand whose minimizer lies o bases from its end waits omax - o steps, omax the largest
+            // offset of the generation: from then on every strand of a key stands at the same genome position in every step.  A key without a
+            // minimizer (k_ovl_park_keys) waits for nobody.
+            uint32_t wait = 0;
+            if (phase) {
+                const uint32_t kb = (uint32_t)st >> WK_KEY_SHIFT, o = kb & 31u;
+                const bool has = (kb & 32u) != 0;
+                uint64_t top = __ballot(has);
+                uint32_t omax = 0;
+#pragma unroll
+                for (int b = 4; b >= 0; --b) {
+                    const uint64_t m = __ballot(has && ((o >> b) & 1u)) & top;
+                    if (m) { top = m; omax |= 1u << b; }
+                }
+                wait = has ? omax - o : 0u;
+            }
             st = WK_IDLE;
             if (k != ~0ull) {   // (~0: the sequence ended inside the head)
-                const uint32_t c0 = walk_nib_to_2bit(pk0), c1 = walk_nib_to_2bit(pk1), c2 = walk_nib_to_2bit(pk2), c3 = walk_nib_to_2bit(pack);
+                const uint32_t c0 = walk_nib_to_2bit(npush), c1 = walk_nib_to_2bit(depth), c2 = walk_nib_to_2bit(flags), c3 = walk_nib_to_2bit(pack);
                 walk_ls[fmd_lane()] = (c0 & 0xffffu) | c1 << 16; walk_ls[64 + fmd_lane()] = (c2 & 0xffffu) | c3 << 16;
-                depth = FMD_WALK_SPLIT; npush = 0; pack = 0; pk0 = pk1 = pk2 = 0; ret = 0; tab = false;
+                depth = FMD_WALK_SPLIT; npush = wait; pack = 0; tab = false;
                 flags = ((c0 | c1 | c2 | c3) & 0x10000u) ? WALK_F_HASN : 0u;
-                st = walk_lf_shares(k, x0, sz) ? WK_BOTH : WK_LF;
+                st = wait ? WK_WAIT : walk_lf_shares(k, x0, sz) ? WK_BOTH : WK_LF;
             }
             continue;
         }
@@ -333,34 +391,62 @@ __device__ __forceinline__ void walk_run(const FmdIndexView &ix, size_t n, const
                 sr[0] = make_uint4(WALK_NIB4(pk0), WALK_NIB4(pk0 >> 16), WALK_NIB4(pk1), WALK_NIB4(pk1 >> 16));
                 sr[1] = make_uint4(WALK_NIB4(pk2), WALK_NIB4(pk2 >> 16), WALK_NIB4(pack), WALK_NIB4(pack >> 16));
 #undef WALK_NIB4
-                depth = FMD_WALK_SPLIT; npush = 0; pack = 0; pk0 = pk1 = pk2 = 0; flags = 0; ret = 0; tab = false;
+                depth = FMD_WALK_SPLIT; npush = 0; pack = 0; pk0 = pk1 = pk2 = 0; flags = 0; tab = false;
                 st = walk_lf_shares(k, x0, sz) ? WK_BOTH : WK_LF;
             }
             continue;
         }
 
-        int c = c_pend;
+        int c = (int)((flags & WALK_F_CPEND) >> WALK_F_CPEND_SHIFT);
         // Narrow interval (size <= 63, i.e. all but the first ~log4(n) bases): everything comes from ONE
         // 64-position window of BWT[x0, x0+size) read out of the lane's block image -- the six child
         // sizes, the base at row k (k lies inside the window) and rank_c(k) -- plus ONE absolute rank
         // of ONE symbol, rank_c(x0-1).  ~150 VALU instead of two full six-symbol block ranks (~600).
         const bool narrow = st == WK_BOTH && sz <= 63;
-        uint64_t ws[6] = {0, 0, 0, 0, 0, 0}, wtk = 0, wD = 0, wr0 = 0;  // wD, wr0: the narrow form of cand_store (fmd_kernel_common.h)
+        // What the rest of the turn needs of it: the sizes of child 0 and of child c = BWT[k], the sizes ordered before c (0 < 4 < 3 < 2 < 1 < 5) and where
+        // child c starts (cnt[c] + rank_c(x0 - 1); cnt[0] = 0) -- all of them popcounts of masks over the window.
+        // Two widths, ONE of them per wave step: while no narrow lane of the wave is wider than 31 (pass 2 of 30-fold reads: nearly every step) the window
+        // BWT[x0, x0 + size) starts at offset 1 .. 64 of the block of x0 - 1 and ends inside its 96 positions: two chunks of that one image, 32-bit masks, and
+        // the rank from the chunks already in registers.  Otherwise the 64-position window over both images.
+        uint32_t ns0 = 0, nsc = 0, nbef = 0;
+        uint64_t nx0 = 0, wD = 0, wr0 = 0;  // wD, wr0: the narrow form of cand_store (fmd_kernel_common.h)
         if (narrow) {
-            const uint32_t sh = (uint32_t)x0 & 31;
-            uint4 a, b, cc;
-            grp_window(r.bk, r.t, r.bl, r.tl, r.blk_k, r.blk_l, r.hk, r.l_sep, r.blk_k, r.nk - 1, a, b, cc); // window at x0 = (x0 - 1) + 1
-            const uint64_t m = bits_below((int)sz);
-            const uint64_t X = win64(a.x, b.x, cc.x, sh), Y = win64(a.y, b.y, cc.y, sh), Z = win64(a.z, b.z, cc.z, sh);
-            const uint64_t lo = ~Z & m, hi = Z & ~Y & m;
-            const uint64_t M0 = lo & ~Y & ~X, M1 = lo & ~Y & X, M2 = lo & Y & ~X, M3 = lo & Y & X, M4 = hi & ~X, M5 = hi & X;
-            ws[0] = __popcll(M0); ws[1] = __popcll(M1); ws[2] = __popcll(M2); ws[3] = __popcll(M3); ws[4] = __popcll(M4); ws[5] = __popcll(M5);
-            const uint32_t o = (uint32_t)(k - x0);                       // row k inside the window
-            c = (int)(((X >> o) & 1) | ((Y >> o) & 1) << 1 | ((Z >> o) & 1) << 2);
-            wtk = fmd_block_rank1z(r.bk, r.t, r.nk, c, r.blk_k, wr0);              // rank_c(x0 - 1), rank_$(x0 - 1)
-            wD = M0;
-            const uint64_t Mc = sel6(c, M0, M1, M2, M3, M4, M5);
-            k = walk_cnt(ix, c) + wtk + __popcll(Mc & bits_below((int)o + 1)) - 1;
+            if (__ballot(sz > 31) == 0) {
+                const uint32_t ch = r.nk >> 5, sh = r.nk & 31;               // r.nk = offset of x0 in the block of x0 - 1: 1 .. 64
+                const uint4 v0 = r.bk[0 ^ r.t], v1 = r.bk[1 ^ r.t], v2 = r.bk[2 ^ r.t], mv = r.bk[3 ^ r.t];   // the image, once
+                // the window's chunks ch and min(ch + 1, 2) out of the registers (ch = 2: offset 64, shift 0 -- the second word is not looked at)
+                uint4 a = v0, b = v1;
+                a.x = ch == 1 ? v1.x : a.x; a.y = ch == 1 ? v1.y : a.y; a.z = ch == 1 ? v1.z : a.z;
+                a.x = ch == 2 ? v2.x : a.x; a.y = ch == 2 ? v2.y : a.y; a.z = ch == 2 ? v2.z : a.z;
+                b.x = ch != 0 ? v2.x : b.x; b.y = ch != 0 ? v2.y : b.y; b.z = ch != 0 ? v2.z : b.z;
+                const uint32_t m2 = v2.w;
+                const uint32_t X = __builtin_amdgcn_alignbit(b.x, a.x, sh), Y = __builtin_amdgcn_alignbit(b.y, a.y, sh), Z = __builtin_amdgcn_alignbit(b.z, a.z, sh);
+                const uint32_t m = (1u << (uint32_t)sz) - 1u;
+                const uint32_t o = (uint32_t)k - (uint32_t)x0;               // row k inside the window
+                const uint32_t ex = ((X >> o) & 1u) - 1u, ey = ((Y >> o) & 1u) - 1u, ez = ((Z >> o) & 1u) - 1u;   // all ones where the bit of c is clear
+                c = (int)((~ex & 1u) | (~ey & 2u) | (~ez & 4u));
+                const uint32_t M0 = ~(X | Y | Z) & m, Mc = (X ^ ex) & (Y ^ ey) & (Z ^ ez) & m;
+                const uint32_t Mb = win_before(X, Y, Z, ~ex, ~ey, ~ez) & m;
+                ns0 = (uint32_t)__builtin_popcount(M0); nsc = (uint32_t)__builtin_popcount(Mc); nbef = (uint32_t)__builtin_popcount(Mb);
+                nx0 = walk_cnt(ix, c) + fmd_block_rank1z_regs(v0, v1, m2, mv, r.nk, c, ex, ey, ez, r.blk_k, wr0);   // rank_c(x0 - 1), rank_$(x0 - 1)
+                wD = M0;
+                k = nx0 + (uint32_t)__builtin_popcount(Mc & ((2u << o) - 1u)) - 1;
+            } else {
+                const uint32_t sh = (uint32_t)x0 & 31;
+                uint4 a, b, cc;
+                grp_window(r.bk, r.t, r.bl, r.tl, r.blk_k, r.blk_l, r.hk, r.l_sep, r.blk_k, r.nk - 1, a, b, cc); // window at x0 = (x0 - 1) + 1
+                const uint64_t m = bits_below((int)sz);
+                const uint64_t X = win64(a.x, b.x, cc.x, sh), Y = win64(a.y, b.y, cc.y, sh), Z = win64(a.z, b.z, cc.z, sh);
+                const uint32_t o = (uint32_t)(k - x0);                       // row k inside the window
+                const uint64_t ex = ((X >> o) & 1) - 1, ey = ((Y >> o) & 1) - 1, ez = ((Z >> o) & 1) - 1;   // all ones where the bit of c is clear
+                c = (int)(((uint32_t)~ex & 1u) | ((uint32_t)~ey & 2u) | ((uint32_t)~ez & 4u));
+                const uint64_t M0 = ~(X | Y | Z) & m, Mc = (X ^ ex) & (Y ^ ey) & (Z ^ ez) & m;
+                const uint64_t Mb = win_before(X, Y, Z, ~ex, ~ey, ~ez) & m;
+                ns0 = (uint32_t)__popcll(M0); nsc = (uint32_t)__popcll(Mc); nbef = (uint32_t)__popcll(Mb);
+                nx0 = walk_cnt(ix, c) + fmd_block_rank1z(r.bk, r.t, r.nk, c, r.blk_k, wr0);          // rank_c(x0 - 1), rank_$(x0 - 1)
+                wD = M0;
+                k = nx0 + __popcll(Mc & bits_below((int)o + 1)) - 1;
+            }
         } else if (st == WK_LF || st == WK_BOTH) { // LF step at row k: base = BWT[k], k' = cnt[c] + rank_c(k) - 1
             uint32_t kb_ = r.blk_k, off;
             const bool in_k = fmd_in_block(k, r.blk_k, off);     // (WK_LF: the block asked for; WK_BOTH: one of the extension's two)
@@ -389,7 +475,7 @@ __device__ __forceinline__ void walk_run(const FmdIndexView &ix, size_t n, const
                 }
                 continue;
             }
-            if (st == WK_LF && depth > 0) { c_pend = c; st = WK_EXT; continue; } // the extension needs its own gather
+            if (st == WK_LF && depth > 0) { flags = (flags & ~WALK_F_CPEND) | (uint32_t)c << WALK_F_CPEND_SHIFT; st = WK_EXT; continue; } // the extension needs its own gather
         }
         if (depth == 0) { // first LF step: the last base of the sequence, or an empty sequence
             if (c == 0) {
@@ -405,11 +491,10 @@ __device__ __forceinline__ void walk_run(const FmdIndexView &ix, size_t n, const
             if (c > 4) tab = false;
             tfw = (uint32_t)(c - 1) & 3; trv = (uint32_t)(4 - c) & 3;
         } else if (st == WK_EXT || st == WK_BOTH) {
-            uint64_t tk[6] = {0, 0, 0, 0, 0, 0}, s[6];
-            if (narrow) { // only tk[c] is ever read below
-#pragma unroll
-                for (int a = 0; a < 6; ++a) { s[a] = ws[a]; tk[a] = wtk; }
-            } else {
+            // s0, sc: the sizes of child 0 and child c; before: the sizes ordered before c (0 < 4 < 3 < 2 < 1 < 5); nx: where child c starts
+            uint64_t s0 = ns0, sc = nsc, before = nbef, nx = nx0;
+            if (!narrow) {
+                uint64_t tk[6] = {0, 0, 0, 0, 0, 0}, s[6];
                 uint64_t tl[6] = {0, 0, 0, 0, 0, 0};
                 if (was_two_phase) {
 #pragma unroll
@@ -418,11 +503,17 @@ __device__ __forceinline__ void walk_run(const FmdIndexView &ix, size_t n, const
                 if (r.hl) fmd_block_rank6<false>(r.bl, r.tl, r.nl, tl, r.blk_l);
 #pragma unroll
                 for (int a = 0; a < 6; ++a) s[a] = tl[a] - tk[a];
+                s0 = s[0]; sc = sel6(c, s[0], s[1], s[2], s[3], s[4], s[5]);
+                nx = walk_cnt(ix, c) + sel6(c, tk[0], tk[1], tk[2], tk[3], tk[4], tk[5]);
+                before = s[0];
+                if (c == 3 || c == 2 || c == 1 || c == 5) before += s[4];
+                if (c == 2 || c == 1 || c == 5) before += s[3];
+                if (c == 1 || c == 5) before += s[2];
+                if (c == 5) before += s[1];
             }
             if (c != 0) { // one more base: overlap_intv's loop body (unitig.c:47-59)
-                const uint64_t sc = sel6(c, s[0], s[1], s[2], s[3], s[4], s[5]);
                 // (sc == 0 cannot happen: the sequence itself is in the index)
-                if (MODE != WALK_HEAD && !info_only && (int)depth >= min_match && s[0]) {
+                if (MODE != WALK_HEAD && !info_only && (int)depth >= min_match && s0) {
                     if (npush < cap) {
                         fmd_intv_t *e = listA + sid * (size_t)cap + (cap - 1 - npush);
                         const bool nf = narrow && depth < 65536u;
@@ -432,14 +523,7 @@ __device__ __forceinline__ void walk_run(const FmdIndexView &ix, size_t n, const
                     } else flags |= FMD_OVLP_F_OVERFLOW;
                     ++npush;
                 }
-                x0 = walk_cnt(ix, c) + sel6(c, tk[0], tk[1], tk[2], tk[3], tk[4], tk[5]);
-                uint64_t before = 0;             // sizes ordered before c: 0 <4 <3 <2 <1 <5
-                if (c != 0) before += s[0];
-                if (c == 3 || c == 2 || c == 1 || c == 5) before += s[4];
-                if (c == 2 || c == 1 || c == 5) before += s[3];
-                if (c == 1 || c == 5) before += s[2];
-                if (c == 5) before += s[1];
-                x1 += before; sz = sc;
+                x0 = nx; x1 += before; sz = sc;
                 WALK_PUT_BASE(c);
             } else { // '$': the sequence is complete (len = depth); these ranks are the left test of fm6_is_contained
                 if (MODE == WALK_TAIL2) {
@@ -461,19 +545,19 @@ __device__ __forceinline__ void walk_run(const FmdIndexView &ix, size_t n, const
                 if (!info_only && (int)depth <= min_match) { o->status = -1; o->flags = 0; st = WK_IDLE; continue; } // too short (unitig.c:288)
                 // (the caller's copy in read order is made by k_ovl_seq_out: a lane doing it here, from a stash in HBM, holds up the other 63;
                 // WALK_TAIL2 writes it from LDS at the strand's close)
-                if (sz != s[0]) ret = -1;          // left-contained
-                x0 = tk[0]; sz = s[0];             // ok[0]: x[0] = cnt[0] + tk[0], x[1] unchanged
+                if (sz != s0) flags |= WALK_F_CONTAINED;           // left-contained
+                x0 = nx; sz = s0;                  // ok[0]: x[0] = cnt[0] + tk[0] (cnt[0] = 0), x[1] unchanged
                 st = WK_RIGHT;
                 continue;
             }
         } else if (st == WK_RIGHT) { // extend by '$' on the right (unitig.c:86-89)
             const uint64_t t0k = was_two_phase ? tk2[0] : (r.hk ? fmd_block_rank1(r.bk, r.t, r.nk, 0, r.blk_k) : 0);
             const uint64_t t0l = r.hl ? fmd_block_rank1(r.bl, r.tl, r.nl, 0, r.blk_l) : 0;
-            if (sz != t0l - t0k) ret = -1;
+            if (sz != t0l - t0k) flags |= WALK_F_CONTAINED;
             if (MODE == WALK_TAIL2) { x1 = t0k; sz = t0l - t0k; st = WK_DONE; continue; }   // everything else at the close (top of the loop)
             fmd_ovlp_rec_t *o = rec + gs;
             o->k[0] = x0; o->k[1] = t0k; o->k[2] = t0l - t0k;
-            o->status = ret < 0 ? -3 : 0;
+            o->status = (flags & WALK_F_CONTAINED) ? -3 : 0;
             o->n_ovlp = (int32_t)npush;
             o->flags = flags & ~WALK_F_INTERNAL;
             st = WK_IDLE;
@@ -503,7 +587,7 @@ template <int MODE>
 __global__ __launch_bounds__(64, 4) void k_ovl_walk(const WalkArgs a)
 {
     walk_run<MODE>(a.ix, a.n, a.ids, a.min_match, a.info_only, a.rec, a.srev, a.stride_r, a.listA, a.cap, a.queue, a.tickets, a.park, a.adm, a.pair_from,
-                   a.gidx, a.seq_out, a.seq_stride, a.redo, a.cls, a.use_fast, a.min_cls);
+                   a.gidx, a.seq_out, a.seq_stride, a.redo, a.cls, a.use_fast, a.min_cls, a.keys);
 }
 
 #undef WALK_STASH_WORD
@@ -779,7 +863,7 @@ bool fmd_walk_tail2_fits(uint32_t stride_r, uint32_t seq_stride) { return stride
 void fmd_launch_walk_tail2(fmd_dev *h, hipStream_t st, WalkArgs a, int per_cu)
 {
     const int grid = walk_grid(h, a.n, FMD_COMPACT_LDS_U4 * 16 + 64 * WALK_LS_WORDS * 4, per_cu);
-    a.queue = fmd_next_queue(h, st); a.tickets = walk_ticket_chunk(64, a.n, grid);
+    a.queue = fmd_next_queue(h, st); a.tickets = a.keys ? 64u : walk_ticket_chunk(64, a.n, grid);   // (in phase: one chunk = one generation of a wave)
     (void)hipMemsetAsync(a.redo, 0, 4, st);
     if (a.cls) (void)hipMemsetAsync(a.cls, 0, 4 * FMD_CLS_HEADER_U32, st);
     k_ovl_walk<WALK_TAIL2><<<grid, 64, 0, st>>>(a);

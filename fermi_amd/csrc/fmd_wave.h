@@ -336,6 +336,28 @@ __device__ __forceinline__ uint64_t fmd_block_rank1z(const uint4 *blk, int t, ui
     return (uint64_t)blk_no * FMD_BLK_STRIDE - five + n;
 }
 
+// fmd_block_rank1z for npos <= 64 from chunks the caller holds in registers: v0, v1 = chunks 0 and 1 (planes and the counts of '$' and A), m2 = the
+// fourth word of chunk 2 (the count of C), mv = the metadata chunk.  ex, ey, ez = the planes' complement masks of symbol c (all ones where the bit of c
+// is clear).  The look-ahead chunk never counts: it starts at position 64.
+__device__ __forceinline__ uint64_t fmd_block_rank1z_regs(const uint4 v0, const uint4 v1, uint32_t m2, const uint4 mv, uint32_t npos, int c, uint32_t ex, uint32_t ey,
+                                                          uint32_t ez, uint32_t blk_no, uint64_t &rz)
+{
+    const uint32_t k0 = fmd_mask32((int)npos), k1 = fmd_mask32((int)npos - 32);
+    const uint32_t n = __builtin_popcount((v0.x ^ ex) & (v0.y ^ ey) & (v0.z ^ ez) & k0) + __builtin_popcount((v1.x ^ ex) & (v1.y ^ ey) & (v1.z ^ ez) & k1);
+    const uint32_t nz = __builtin_popcount(~(v0.x | v0.y | v0.z) & k0) + __builtin_popcount(~(v1.x | v1.y | v1.z) & k1);
+    const uint32_t m0 = v0.w, m1 = v1.w;
+    rz = ((uint64_t)(mv.z & 0xff) << 32 | m0) + nz;
+    if (c < 5) {
+        uint32_t lo = m0;   // (selects, not a chain of ?: the compiler turns into branches: the lanes of a wave differ in c)
+        lo = c == 1 ? m1 : lo; lo = c == 2 ? m2 : lo; lo = c == 3 ? mv.x : lo; lo = c == 4 ? mv.y : lo;
+        const uint32_t hi = ((c == 4 ? mv.w : mv.z >> (8 * c))) & 0xff;
+        return ((uint64_t)hi << 32 | lo) + n;
+    }
+    const uint64_t five = ((uint64_t)(mv.z & 0xff) << 32 | m0) + ((uint64_t)((mv.z >> 8) & 0xff) << 32 | m1) +
+                          ((uint64_t)((mv.z >> 16) & 0xff) << 32 | m2) + ((uint64_t)(mv.z >> 24) << 32 | mv.x) + ((uint64_t)(mv.w & 0xff) << 32 | mv.y);
+    return (uint64_t)blk_no * FMD_BLK_STRIDE - five + n;
+}
+
 // ---- work queue of the persistent kernels --------------------------------------------------------
 // Items are handed out by ONE device-wide counter.  A wave does not pay an atomic round trip (which
 // crosses the fabric: the counter is shared by all XCDs) every time a lane finishes: it holds a
