@@ -119,13 +119,10 @@ __device__ __forceinline__ uint64_t range64(uint32_t a, uint32_t b) // bits [a, 
 // (error-free: 0.1 %) -- in groups of 8 half of their lanes never hold anything.
 #define FMD_GRP_CLASSES 6
 __device__ __host__ __forceinline__ constexpr int fmd_grp_size(int k) { return k == 0 ? 4 : k == 1 ? 8 : k == 2 ? 12 : k == 3 ? 16 : k == 4 ? 21 : 32; }
-#define FMD_CLS_CNT_STRIDE 32              // counters sit on separate 128-byte lines
-#define FMD_CLS_HEADER_U32 640             // the counter area in front of the lists (3 * FMD_GRP_CLASSES + 1 lines)
 // hand-over from k_ovl_nei_fast to k_ovl_nei_grp: list slots reserved FMD_FAST_CHUNK at a time, unused ones stay holes
 #define FMD_FAST_CHUNK 16
 #define FMD_FAST_MAX_WAVES 8192
 #define FMD_LIST_HOLE 0xffffffffu
-#define FMD_DOWN_WORD 4                    // word of a fast list's counter line that counts the SECOND-PASS list of that class (strands k_ovl_nei_grp moved to a smaller group); its deal counter: + FMD_DEAL_WORD
 // A strand k_ovl_nei_fast hands on in the middle (a fork, an N: rounds only k_ovl_nei_grp does) travels with its state: bit 15 of the
 // list entry's second word, the number of live candidates in the bits below, and in the strand's row of listB (scratch of
 // k_ovl_nei, which these strands never reach without being started over from listA) one 32-byte entry per live candidate, in list
@@ -148,25 +145,106 @@ __device__ __forceinline__ void fmd_resume_decode(const uint4 a, const uint4 b, 
     r0 = (uint64_t)(b.y & 0xffu) << 32 | b.x; nei0 = b.y >> 8; sz = b.z & 0xffffu; pos = b.z >> 16; lf = b.w & 0x1ffffu; cat = (b.w >> 17) & 31u; flags8 = (b.w >> 22) & 0xffu;
 }
 #define FMD_LANE_CHUNK 64                  // the same for k_ovl_nei_lane (fmd_ovlp_lane.hip): every lane of a wave may hand its strand on in one step
-#define FMD_DEAL_WORD_LANE 16              // word of a fast list's counter line that is k_ovl_nei_lane's ticket counter (the group form deals from the same word)
 #define FMD_FAST_RESERVE (2 * FMD_FAST_MAX_WAVES * FMD_LANE_CHUNK)   // entries a general list may lose to holes (two fast kernels feed it; a wave's last chunk keeps at most FMD_LANE_CHUNK - 1)
-#define FMD_CLS_PART_U32 (FMD_CLS_HEADER_U32 + 2 * FMD_GRP_CLASSES * FMD_FAST_RESERVE)   // per part of a pipelined batch: counters + that room
-static_assert((3 * FMD_GRP_CLASSES + 1) * FMD_CLS_CNT_STRIDE <= FMD_CLS_HEADER_U32, "one counter line per list");
-#define FMD_CLS_LISTS (3 * FMD_GRP_CLASSES + 1)                 // general lists, the slow list, fast lists (32-bit masks, 64-bit masks)
-#define FMD_CLS_WORDS_PER_STRAND (6 * FMD_GRP_CLASSES + 3)      // two words per entry of a group list, one each for the slow list, the late slow list, the fix-up list
-// Counters on the slow list's 128-byte line: [0] strands k_ovl_classify sets aside (k_ovl_nei takes them at once, beside the group
-// kernels), [FMD_CLS_LATE_CNT] strands the fast / group kernels hand back later (a second k_ovl_nei launch behind them; this is the
-// counter those kernels get as `slow_n`), and FMD_CLS_FIX_CNT words behind THAT the fix-up list's.
-#define FMD_CLS_LATE_CNT 4
-#define FMD_CLS_FIX_CNT 16
-struct FmdOvlClasses {
-    // counters: [k * STRIDE] = strands of general class k, [CLASSES * STRIDE] = the slow list, [(CLASSES + 1 + k) * STRIDE] = fast class k,
-    // k >= CLASSES: the 64-bit variant of class k - CLASSES (+8 on that line: strands the fast kernel handed on to the general class)
-    uint32_t *cnt;
-    uint32_t *lst[FMD_GRP_CLASSES];   // two words per strand: index, candidates | length << 16
-    uint32_t *lslow;                  // everything else, plus strands the group kernels hand back
-    uint32_t *fast[2 * FMD_GRP_CLASSES];  // strands whose candidates are in the narrow form: k_ovl_nei_fast first (same two words)
+
+// ---- The work lists of ONE PART of a batch (np strands), laid over a uint32_t area: FMD_CLS_HEADER_U32 words of counters -- one 128-byte line per list --, then
+// the lists.  This is the only place that knows where they lie: the host fills FmdOvlClasses through fmd_cls_list (fmd_nei_lists_at, fmd_ovlp_internal.h), the
+// walk's close finds its list through it.  List numbers: general class k = k, the slow list = FMD_CLS_SLOW, fast class k = fmd_cls_fast(k) with 32-bit masks
+// and fmd_cls_fast(k + FMD_GRP_CLASSES) with 64-bit masks.
+//   general list k   2 words per entry (slot of the batch, candidates | length << 16); room for every strand of the part + FMD_FAST_RESERVE holes
+//   the slow list    1 word per entry, np entries: what classification sets aside (k_ovl_nei takes them at once, beside the group kernels)
+//   fast list k      2 words per entry, np entries; when the fast kernels are through, the storage of the SECOND-PASS list of class k (k_ovl_nei_grp)
+//   the late list    1 word per entry, np entries: strands the fast / group kernels hand back (a second k_ovl_nei launch behind them)
+//   the fix-up list  1 word per entry, np entries: strands a group kernel closed with one neighbour after a fork (k_ovl_fix)
+#define FMD_CLS_CNT_STRIDE 32                                   // counters sit on separate 128-byte lines
+#define FMD_CLS_HEADER_U32 640                                  // the counter area in front of the lists
+#define FMD_CLS_LISTS (3 * FMD_GRP_CLASSES + 1)                 // general lists, the slow list, fast lists (32-bit masks, 64-bit masks): the lists that have a counter line
+#define FMD_CLS_SLOW FMD_GRP_CLASSES
+static_assert(FMD_CLS_LISTS * FMD_CLS_CNT_STRIDE <= FMD_CLS_HEADER_U32, "one counter line per list");
+__host__ __device__ __forceinline__ constexpr int fmd_cls_fast(int k) { return FMD_GRP_CLASSES + 1 + k; }     // k in [0, 2 * FMD_GRP_CLASSES)
+__host__ __device__ __forceinline__ constexpr int fmd_cls_cnt_off(int c) { return c * FMD_CLS_CNT_STRIDE; }    // word offset of the counter line of list c
+// List c of a part of np strands, c in [0, FMD_CLS_LISTS]: as a pointer (P = uint32_t *, area = the part's), or as a word offset (P = size_t, area = 0).
+// In this shape -- the slow list first, then a select between two pointers -- it folds into k_ovl_walk<WALK_TAIL2> without a register (that kernel has none
+// to give: 125 of 128); as `area + offset(c)` it cost two.
+template <class P>
+__host__ __device__ __forceinline__ constexpr P fmd_cls_list(P area, int c, size_t np)
+{
+    const size_t gl = 2 * np + 2 * (size_t)FMD_FAST_RESERVE;          // words of a general list
+    const P slow = area + FMD_CLS_HEADER_U32 + gl * FMD_GRP_CLASSES;
+    if (c == FMD_CLS_SLOW) return slow;
+    return c < FMD_CLS_SLOW ? area + FMD_CLS_HEADER_U32 + gl * c : slow + np + 2 * np * (size_t)(c - FMD_CLS_SLOW - 1);
+}
+template <class P> __host__ __device__ __forceinline__ constexpr P fmd_cls_late(P area, size_t np) { return fmd_cls_list(area, FMD_CLS_LISTS, np); }   // behind the last fast list
+template <class P> __host__ __device__ __forceinline__ constexpr P fmd_cls_fix(P area, size_t np) { return fmd_cls_late(area, np) + np; }
+// A batch cut into parts (FMD_OVLP_PIPE) keeps one such area per part, one behind the other: per part a header and the general lists' reserve, per strand
+// the words that grow with the part.  The area of part `part`, whose first strand is strand b of the batch, starts at word
+#define FMD_CLS_WORDS_PER_STRAND (6 * FMD_GRP_CLASSES + 3)      // two words per entry of a general and of a fast list, one each for the slow, the late and the fix-up list
+#define FMD_CLS_PART_U32 (FMD_CLS_HEADER_U32 + 2 * FMD_GRP_CLASSES * FMD_FAST_RESERVE)
+__host__ __device__ __forceinline__ constexpr size_t fmd_cls_part_off(int part, size_t b) { return (size_t)part * FMD_CLS_PART_U32 + b * FMD_CLS_WORDS_PER_STRAND; }
+static_assert(fmd_cls_fix<size_t>(0, 1000) + 1000 == fmd_cls_part_off(1, 1000) && fmd_cls_fix<size_t>(0, 1) + 1 == fmd_cls_part_off(1, 1), "a part's lists end where the next part begins");
+
+// The words of a counter line (zeroed with the header before every batch).  Kernels get a pointer to ONE word of a line -- the count of the list they read,
+// the count they append to -- and reach its neighbours by the difference of two names.
+enum FmdClsWord {
+    // every line
+    FMD_CW_COUNT = 0,            // entries of the list (a general list: slots, the holes of the chunked hand-over included)
+    // a general and a fast list's line
+    FMD_CW_DEAL = 16,            // the next position to deal out: fmd_deal_next of the group kernels, the ticket counter of k_ovl_nei_lane
+    // a fast list's line
+    FMD_CW_DOWN = 4,             // entries of the second-pass list of the class (strands k_ovl_nei_grp moved to a smaller group), in chunks of FMD_FAST_CHUNK
+    FMD_CW_DOWN_DEAL = FMD_CW_DOWN + FMD_CW_DEAL,   // ... and the deal counter of that list: the second pass is launched with FMD_CW_DOWN as its count
+    FMD_CW_HANDED = 8,           // strands the fast kernel handed on to the general list of the class (`bail_n`; FMD_OVLP_STATS)
+    FMD_CW_HANDED_AT0 = 9,       // (printed by the GRP_STATS block; nothing counts here since strands are handed on where they stand)
+    FMD_CW_FAST_ROUNDS = 10,     // GRP_STATS, the fast kernels: wave rounds,
+    FMD_CW_FAST_LIVE = 11,       // ... live lanes in them,
+    FMD_CW_FAST_HELD = 12,       // ... lanes of groups that hold a strand,
+    FMD_CW_FAST_ROUNDS2 = 13,    // ... rounds in which some strand saw a second base
+    // the slow list's line
+    FMD_CW_LATE = 4,             // entries of the late list (`slow_n` of the fast / group kernels)
+    FMD_CW_GRP_ROUNDS = 12,      // GRP_STATS, the group kernels: wave rounds,
+    FMD_CW_GRP_LIVE = 13,        // ... live lanes in them,
+    FMD_CW_GRP_HELD = 14,        // ... lanes of groups that hold a strand
+    FMD_CW_FIX = 20,             // entries of the fix-up list
 };
+template <int... W> constexpr bool fmd_cw_distinct()
+{
+    const int w[] = {W...};
+    for (size_t i = 0; i < sizeof...(W); ++i) {
+        if (w[i] < 0 || w[i] >= FMD_CLS_CNT_STRIDE) return false;
+        for (size_t j = 0; j < i; ++j) if (w[j] == w[i]) return false;
+    }
+    return true;
+}
+static_assert(fmd_cw_distinct<FMD_CW_COUNT, FMD_CW_DEAL>(), "a general list's counter line");
+static_assert(fmd_cw_distinct<FMD_CW_COUNT, FMD_CW_DEAL, FMD_CW_DOWN, FMD_CW_DOWN_DEAL, FMD_CW_HANDED, FMD_CW_HANDED_AT0, FMD_CW_FAST_ROUNDS, FMD_CW_FAST_LIVE, FMD_CW_FAST_HELD,
+                              FMD_CW_FAST_ROUNDS2>(), "a fast list's counter line");
+static_assert(fmd_cw_distinct<FMD_CW_COUNT, FMD_CW_LATE, FMD_CW_GRP_ROUNDS, FMD_CW_GRP_LIVE, FMD_CW_GRP_HELD, FMD_CW_FIX>(), "the slow list's counter line");
+
+// The lists of one part as pointers (the kernels' form; filled through the functions above).  The late and the fix-up list travel beside it (NeiArgs,
+// fmd_ovlp_internal.h): the kernels that append to them get them as `slow_list` and `fix_off`.
+struct FmdOvlClasses {
+    uint32_t *cnt;                        // the header: line fmd_cls_cnt_off(c) belongs to list c, words FmdClsWord
+    uint32_t *lst[FMD_GRP_CLASSES];       // the general lists
+    uint32_t *lslow;                      // the slow list
+    uint32_t *fast[2 * FMD_GRP_CLASSES];  // strands whose candidates are in the narrow form: k_ovl_nei_fast / k_ovl_nei_lane first; [FMD_GRP_CLASSES ..]: the 64-bit lists
+};
+
+// The list a strand belongs on, from what is known of it at the walk's close (k_ovl_walk<WALK_TAIL2>) or from its record and its row of listA (k_ovl_classify):
+// m candidates, len bases, and three facts about the WIDEST candidate -- the first one pushed, the last of the list (shortest overlap): its size is at most
+// 63 (the group kernels count symbols of BWT[x, x + size) through a 64-position window), it is in the narrow form (the fast kernels check the others when
+// they load them), its size is more than 31 (the fast kernels' 64-bit masks).  A strand goes to the smallest group class >= min_cls that holds its m
+// candidates, to that class's fast list where use_fast; everything else to the slow list.  Who is eligible at all (status 0, candidates, no overflow, not
+// contained) is the caller's test: the two read it from different places.
+__device__ __forceinline__ int fmd_ovl_list_of(uint32_t m, uint32_t len, bool w63, bool wnarrow, bool w32, int use_fast, int min_cls)
+{
+    int c = FMD_CLS_SLOW;
+    if (w63 && len < 65535u) {
+#pragma unroll
+        for (int k = FMD_GRP_CLASSES - 1; k >= 0; --k) if (k >= min_cls && m <= (uint32_t)fmd_grp_size(k)) c = k;
+        if (c < FMD_CLS_SLOW && wnarrow && use_fast) c += fmd_cls_fast(w32 ? FMD_GRP_CLASSES : 0);   // fast list c, or c + FMD_GRP_CLASSES
+    }
+    return c;
+}
 
 // Two-pass walk of a sorted job (k_ovl_walk<WALK_HEAD / WALK_TAIL>, fmd_ovlp_walk.hip): where a strand stands FMD_WALK_SPLIT bases in.
 #define FMD_WALK_SPLIT 32u            // a multiple of 16: the stash of a parked strand is two whole 16-byte groups

@@ -10,14 +10,24 @@
 #include <string.h>
 #include "fmd_ovlp_internal.h"
 
-// (gidx: slot of a sorted batch -> row of rec / nei_out / seq_out, fmd_ovlp_sorted_dev; nullptr = the slot is the row)
-extern "C" size_t fmd_ovlp_work_bytes(size_t n, uint32_t max_len, int min_match)
+// Work area of one batch of n strands (fmd_ovlp_dev and everything that shares its area): the stash (stride_r bytes per strand, the sequence's last base
+// first), two candidate lists of cap entries per strand (listA: the walk's candidates; listB: scratch of get_nei), and the work lists of get_nei -- per strand
+// the words of fmd_cls_part_off, and a header + reserve for each of the FMD_OVLP_MAX_PARTS parts a batch may be cut into.
+struct BatchLayout { size_t srev, listA, listB, cls, total; uint32_t stride_r, cap; };
+static BatchLayout batch_layout(size_t n, uint32_t max_len, int min_match)
 {
-    const size_t stride_r = align_up((size_t)max_len, 16);
-    const size_t cap = fmd_ovlp_list_cap(max_len, min_match);
-    return align_up(n * stride_r, 256) + 2 * align_up(n * cap * sizeof(fmd_intv_t), 256) +
-           align_up(n * (4 * FMD_CLS_WORDS_PER_STRAND) + 4 * (size_t)FMD_CLS_PART_U32 * FMD_OVLP_MAX_PARTS, 256) + 256;
+    BatchLayout L;
+    const size_t stride_r = align_up((size_t)max_len, 16), cap = fmd_ovlp_list_cap(max_len, min_match);
+    L.stride_r = (uint32_t)stride_r; L.cap = (uint32_t)cap;
+    size_t o = 0;
+    L.srev = o; o += align_up(n * stride_r, 256);
+    L.listA = o; o += align_up(n * cap * sizeof(fmd_intv_t), 256);
+    L.listB = o; o += align_up(n * cap * sizeof(fmd_intv_t), 256);
+    L.cls = o; o += align_up(4 * fmd_cls_part_off(FMD_OVLP_MAX_PARTS, n), 256) + 256;
+    L.total = o;
+    return L;
 }
+extern "C" size_t fmd_ovlp_work_bytes(size_t n, uint32_t max_len, int min_match) { return batch_layout(n, max_len, min_match).total; }
 
 // The buffers of one fmd_ovlp_dev call; the two phases below work on the strands [b, b + np) of it.
 struct OvlBatch {
@@ -29,6 +39,13 @@ struct OvlBatch {
     // park, where WALK_HEAD left it; nullptr: slot = row, the walk starts at the sentinel of ids[t]
     const uint32_t *gidx; FmdWalkPark *park;
     const uint32_t *keys;   // ... and, where the caller has them, the sort key of every slot (k_ovl_park_keys); nullptr otherwise
+    // the work area of the batch: `area` laid out for `n_area` strands (the batch itself, or the largest batch of a sorted job)
+    void carve(uint8_t *area, size_t n_area)
+    {
+        const BatchLayout L = batch_layout(n_area, max_len, min_match);
+        stride_r = L.stride_r; cap = L.cap;
+        srev = area + L.srev; listA = (fmd_intv_t *)(area + L.listA); listB = (fmd_intv_t *)(area + L.listB); cls = (uint32_t *)(area + L.cls);
+    }
 };
 
 // The second pass of a sorted job through k_ovl_walk<WALK_TAIL2> (rows written by the walk, FMD_WALK_TAIL2=0: the A/B switch), and with the work
@@ -46,7 +63,7 @@ static bool ovl_tail2_cls(const OvlBatch &o)
 static int ovl_use_fast(void) { const char *ef = getenv("FMD_OVLP_FAST"); return fmd_nei_fast_available() && !(ef && atoi(ef) == 0); }   // FMD_OVLP_FAST=0: A/B switch, every strand through the general group kernels
 static int ovl_grp_down(void) { const char *e = getenv("FMD_GRP_DOWN"); return !(e && atoi(e) == 0); }
 static int ovl_walk_phase(void) { const char *e = getenv("FMD_WALK_PHASE"); return !(e && atoi(e) == 0); }
-static int ovl_min_cls(void) { const char *e = getenv("FMD_GRP4"); return e && atoi(e) == 0 ? 1 : 0; }                                  // FMD_GRP4=0: no groups of 4 (as fmd_launch_classify)
+static int ovl_min_cls(void) { const char *e = getenv("FMD_GRP4"); return e && atoi(e) == 0 ? 1 : 0; }                                  // the smallest group class in use; FMD_GRP4=0: A/B knob, no groups of 4 (round 3's classes)
 
 // phase A: LF-walk + overlap_intv + fm6_is_contained, then the read-order copy.  per_cu > 0 bounds the
 // resident waves per CU (pipelined batches leave room for phase B of the previous part).
@@ -72,39 +89,31 @@ static void ovl_phase_a(const OvlBatch &o, hipStream_t st, size_t b, size_t np, 
     // The stash area, idle then, holds the list of the strands with an N.
     a.seq_out = o.seq; a.seq_stride = o.seq_stride; a.redo = (uint32_t *)srev;
     if (ovl_tail2_cls(o)) {   // the work lists of phase B made here (part 0 of the batch: a sorted job's batches are not pipelined)
-        a.cls = o.cls + b * FMD_CLS_WORDS_PER_STRAND; a.use_fast = ovl_use_fast(); a.min_cls = ovl_min_cls();
+        a.cls = o.cls + fmd_cls_part_off(0, b); a.use_fast = ovl_use_fast(); a.min_cls = ovl_min_cls();
     }
     // the strands of one minimizer in phase on the genome (k_ovl_walk<WALK_TAIL2>; FMD_WALK_PHASE=0: the A/B switch, free-running admission)
     if (o.keys && ovl_walk_phase()) a.keys = o.keys + b;
     fmd_launch_walk_tail2(o.h, st, a, per_cu);
 }
 
-// phase B: fm6_get_nei.  `part` selects the counter header of this part's work lists.
+// phase B: fm6_get_nei.  `part` selects the area of this part's work lists.
 static int ovl_phase_b(const OvlBatch &o, hipStream_t st, size_t b, size_t np, int part, int per_cu, int fast_cu)
 {
-    uint8_t *srev = o.srev + b * (size_t)o.stride_r;
-    fmd_intv_t *listA = o.listA + b * (size_t)o.cap, *listB = o.listB + b * (size_t)o.cap;
-    const uint32_t *gidx = o.gidx ? o.gidx + b : nullptr;
-    fmd_ovlp_rec_t *rec = gidx ? o.rec : o.rec + b;
-    fmd_intv_t *nei = gidx ? o.nei : o.nei + b * (size_t)o.max_nei;
-    uint8_t *seq = gidx ? o.seq : o.seq + b * (size_t)o.seq_stride;
-    const int grid = fmd_grid_for(o.h, np);
+    NeiArgs a;
+    a.ix = o.ix; a.n_cu = o.h->n_cu; a.grid = fmd_grid_for(o.h, np); a.np = np; a.min_match = o.min_match;
+    a.srev = o.srev + b * (size_t)o.stride_r; a.stride_r = o.stride_r;
+    a.listA = o.listA + b * (size_t)o.cap; a.listB = o.listB + b * (size_t)o.cap; a.cap = o.cap;
+    a.gidx = o.gidx ? o.gidx + b : nullptr;
+    a.rec = a.gidx ? o.rec : o.rec + b;
+    a.nei = a.gidx ? o.nei : o.nei + b * (size_t)o.max_nei; a.max_nei = o.max_nei;
+    a.seq = a.gidx ? o.seq : o.seq + b * (size_t)o.seq_stride; a.seq_stride = o.seq_stride;
     uint32_t *q2 = fmd_next_queue(o.h, st);
-    // work lists: the counter header, then one list per group class (2 words per strand), the slow list (1), one list per fast class (2)
-    // (a general list has room for every strand of the part + the holes the fast kernels' chunked hand-over may leave)
-    uint32_t *cls = o.cls + (size_t)part * FMD_CLS_PART_U32 + b * FMD_CLS_WORDS_PER_STRAND;
-    FmdOvlClasses cl;
-    cl.cnt = cls;
-    for (int k = 0; k < FMD_GRP_CLASSES; ++k) cl.lst[k] = cls + FMD_CLS_HEADER_U32 + (2 * np + 2 * (size_t)FMD_FAST_RESERVE) * k;
-    cl.lslow = cls + FMD_CLS_HEADER_U32 + (2 * np + 2 * (size_t)FMD_FAST_RESERVE) * FMD_GRP_CLASSES;
-    for (int k = 0; k < 2 * FMD_GRP_CLASSES; ++k) cl.fast[k] = cl.lslow + np + 2 * np * k;
-    uint32_t *lslow_late = cl.lslow + np + 2 * np * (size_t)(2 * FMD_GRP_CLASSES);   // strands the fast / group kernels hand back (behind the fast lists)
-    const size_t fix_off = np;                                                        // the fix-up list (fake forks the group kernels closed), behind that one
-    uint32_t *n_slow = cl.cnt + FMD_GRP_CLASSES * FMD_CLS_CNT_STRIDE, *n_late = n_slow + FMD_CLS_LATE_CNT;
+    uint32_t *cls = o.cls + fmd_cls_part_off(part, b);
+    fmd_nei_lists_at(a, cls, np);
     const int use_fast = ovl_use_fast();
     if (!(part == 0 && ovl_tail2_cls(o))) {   // (else: k_ovl_walk<WALK_TAIL2> has zeroed the header and filled the lists)
         FMD_HIP_TRY(hipMemsetAsync(cls, 0, 4 * FMD_CLS_HEADER_U32, st));
-        fmd_launch_classify(st, np, rec, listA, o.cap, cl, use_fast, gidx);
+        fmd_launch_classify(a, st, use_fast, ovl_min_cls());
     }
     // what classification sets aside (more than 32 candidates, a candidate wider than 63) goes through the lane-per-strand kernel NOW, on a
     // side stream beside the group kernels: it is a handful of long dependent chains (10 ms per 2*10^7 strands of raw reads for 1 % of
@@ -117,36 +126,28 @@ static int ovl_phase_b(const OvlBatch &o, hipStream_t st, size_t b, size_t np, i
     }
     {
         hipStream_t ss = side ? slow.stream : st;
-        fmd_launch_nei_slow(grid, ss, fmd_next_queue(o.h, ss), o.ix, np, o.min_match, srev, o.stride_r, o.cap, listA, listB, rec, nei, o.max_nei, seq, o.seq_stride, cl.lslow, n_slow, gidx);
+        fmd_launch_nei_slow(a, ss, fmd_next_queue(o.h, ss), 0);
     }
     // strands whose candidates the walk left in the narrow form: the unforked path (one lane per candidate, no x[0]-side fetch,
     // one shared window per strand and round); whatever turns out not to be that simple moves on to the general list of its class
     if (use_fast)
         for (int k = 0; k < 2 * FMD_GRP_CLASSES; ++k) {
-            uint32_t *nk = cl.cnt + (FMD_GRP_CLASSES + 1 + k) * FMD_CLS_CNT_STRIDE;
-            const int kg = k % FMD_GRP_CLASSES;
+            const int kg = k % FMD_GRP_CLASSES, wide = k >= FMD_GRP_CLASSES;
             // one lane per STRAND where its candidates fit a lane's registers (fmd_ovlp_lane.hip), one lane per candidate otherwise (FMD_NEI_LANE=0: always)
-            if (fmd_nei_lane_enabled() && fmd_nei_lane_class_ok(kg, k >= FMD_GRP_CLASSES))
-                fmd_launch_nei_lane(kg, k >= FMD_GRP_CLASSES, o.h->n_cu, fast_cu, st, o.ix, cl.fast[k], nk, o.cap, listA, listB, rec, nei, o.max_nei, seq,
-                                    o.seq_stride, cl.lst[kg], cl.cnt + kg * FMD_CLS_CNT_STRIDE, nk + 8, gidx);
-            else
-            fmd_launch_nei_fast(kg, k >= FMD_GRP_CLASSES, o.h->n_cu, fast_cu, st, o.ix, cl.fast[k], nk, o.cap, listA, listB, rec, nei, o.max_nei, seq,
-                                o.seq_stride, cl.lst[kg], cl.cnt + kg * FMD_CLS_CNT_STRIDE, nk + 8, lslow_late, n_late, gidx);
+            if (fmd_nei_lane_enabled() && fmd_nei_lane_class_ok(kg, wide)) fmd_launch_nei_lane(a, kg, wide, fast_cu, st);
+            else fmd_launch_nei_fast(a, kg, wide, fast_cu, st);
         }
     // one lane per candidate interval, 64 / G strands per wave
     // (second pass: the strands a group kernel moved to a smaller group when their candidates had died down to single reads -- reads with errors --, largest class first:
     // a strand may move again; their lists live where the fast lists were.  FMD_GRP_DOWN=0: the A/B switch, every strand stays in the group it was admitted to)
     const uint32_t down_cap = ovl_grp_down() && np > 2 * (size_t)FMD_FAST_CHUNK ? (uint32_t)np : 0u;
-    for (int k = 0; k < FMD_GRP_CLASSES; ++k)
-        fmd_launch_nei_grp(k, o.h->n_cu, per_cu, st, o.ix, cl.lst[k], cl.cnt + k * FMD_CLS_CNT_STRIDE, o.cap, listA, listB, cl, rec, nei, o.max_nei, seq, o.seq_stride, lslow_late, n_late, gidx, fix_off, down_cap, 0);
+    for (int k = 0; k < FMD_GRP_CLASSES; ++k) fmd_launch_nei_grp(a, k, per_cu, st, down_cap, 0);
     if (down_cap)
-        for (int k = FMD_GRP_CLASSES - 2; k >= 0; --k)
-            fmd_launch_nei_grp(k, o.h->n_cu, per_cu, st, o.ix, cl.fast[k], cl.cnt + (FMD_GRP_CLASSES + 1 + k) * FMD_CLS_CNT_STRIDE + FMD_DOWN_WORD, o.cap, listA, listB, cl, rec, nei, o.max_nei, seq, o.seq_stride,
-                               lslow_late, n_late, gidx, fix_off, down_cap, 1);
+        for (int k = FMD_GRP_CLASSES - 2; k >= 0; --k) fmd_launch_nei_grp(a, k, per_cu, st, down_cap, 1);
     // the rest (too many candidates, wide intervals, fake forks, neighbour overflow): lane per strand
-    fmd_launch_nei_slow(grid, st, q2, o.ix, np, o.min_match, srev, o.stride_r, o.cap, listA, listB, rec, nei, o.max_nei, seq, o.seq_stride, lslow_late, n_late, gidx);
+    fmd_launch_nei_slow(a, st, q2, 1);
     // fake forks among the strands the group kernels finished: the fix-up alone
-    fmd_launch_nei_fix(grid, st, fmd_next_queue(o.h, st), o.ix, lslow_late + fix_off, n_late + FMD_CLS_FIX_CNT, srev, o.stride_r, rec, nei, o.max_nei, seq, o.seq_stride, gidx);
+    fmd_launch_nei_fix(a, st, fmd_next_queue(o.h, st));
     if (side) {   // the caller's stream owns every row again (and the work area, which the next batch reuses)
         if (hipEventRecord(slow.ev[1], slow.stream) != hipSuccess || hipStreamWaitEvent(st, slow.ev[1], 0) != hipSuccess) { (void)hipGetLastError(); hipStreamSynchronize(slow.stream); }
         slow.release();
@@ -155,24 +156,43 @@ static int ovl_phase_b(const OvlBatch &o, hipStream_t st, size_t b, size_t np, i
         uint32_t hs[FMD_CLS_HEADER_U32];
         hipStreamSynchronize(st);
         hipMemcpy(hs, cls, sizeof(hs), hipMemcpyDeviceToHost);
+        const auto word = [&hs](int c, int w) { return hs[fmd_cls_cnt_off(c) + w]; };
         uint32_t nf = 0, nb = 0, ng = 0;
-        for (int k = 0; k < 2 * FMD_GRP_CLASSES; ++k) { nf += hs[(FMD_GRP_CLASSES + 1 + k) * FMD_CLS_CNT_STRIDE]; nb += hs[(FMD_GRP_CLASSES + 1 + k) * FMD_CLS_CNT_STRIDE + 8]; }
-        for (int k = 0; k < FMD_GRP_CLASSES; ++k) ng += hs[k * FMD_CLS_CNT_STRIDE];
+        for (int k = 0; k < 2 * FMD_GRP_CLASSES; ++k) { nf += word(fmd_cls_fast(k), FMD_CW_COUNT); nb += word(fmd_cls_fast(k), FMD_CW_HANDED); }
+        for (int k = 0; k < FMD_GRP_CLASSES; ++k) ng += word(k, FMD_CW_COUNT);
         fprintf(stderr, "[M::fmd_ovlp] part of %zu strands: %u to the unforked path (%u of them handed on), %u slots of the general group kernels' lists (holes of the hand-over included), %u through the lane-per-strand kernel at once + %u handed back to it, %u fake forks fixed up\n",
-                np, nf, nb, ng, hs[FMD_GRP_CLASSES * FMD_CLS_CNT_STRIDE], hs[FMD_GRP_CLASSES * FMD_CLS_CNT_STRIDE + FMD_CLS_LATE_CNT], hs[FMD_GRP_CLASSES * FMD_CLS_CNT_STRIDE + FMD_CLS_LATE_CNT + FMD_CLS_FIX_CNT]);
+                np, nf, nb, ng, word(FMD_CLS_SLOW, FMD_CW_COUNT), word(FMD_CLS_SLOW, FMD_CW_LATE), word(FMD_CLS_SLOW, FMD_CW_FIX));
+        // The slots above depend on which waves handed strands on (a wave's last chunk keeps its unused slots as holes); what the general lists
+        // CONTAIN does not: the entries that are no hole, per group class
+        uint32_t ne[FMD_GRP_CLASSES];
+        for (int k = 0; k < FMD_GRP_CLASSES; ++k) {
+            const size_t slots = word(k, FMD_CW_COUNT);
+            uint32_t *e = (uint32_t *)malloc(8 * slots + 8);
+            ne[k] = 0;
+            if (e && hipMemcpy(e, a.cl.lst[k], 8 * slots, hipMemcpyDeviceToHost) == hipSuccess)
+                for (size_t i = 0; i < slots; ++i) ne[k] += e[2 * i] != FMD_LIST_HOLE;
+            free(e);
+        }
+        static_assert(FMD_GRP_CLASSES == 6, "one %u per general class");
+        fprintf(stderr, "[M::fmd_ovlp] ... of those slots %u %u %u %u %u %u hold a strand (general lists of the group classes, smallest first)\n", ne[0], ne[1], ne[2], ne[3], ne[4], ne[5]);
     }
 #ifdef GRP_STATS
     {
         uint32_t hs[FMD_CLS_HEADER_U32];
         hipStreamSynchronize(st);
         hipMemcpy(hs, cls, sizeof(hs), hipMemcpyDeviceToHost);
-        const uint32_t *g = hs + FMD_GRP_CLASSES * FMD_CLS_CNT_STRIDE + FMD_CLS_LATE_CNT + 8;
+        const auto word = [&hs](int c, int w) { return hs[fmd_cls_cnt_off(c) + w]; };
+        const uint32_t gr = word(FMD_CLS_SLOW, FMD_CW_GRP_ROUNDS), gl = word(FMD_CLS_SLOW, FMD_CW_GRP_LIVE), gh = word(FMD_CLS_SLOW, FMD_CW_GRP_HELD);
+        static_assert(FMD_GRP_CLASSES == 6, "one %u per general class");
         fprintf(stderr, "[grp stats] classes %u %u %u %u %u %u slow %u | wave rounds %u, live lanes %u (%.1f %%), lanes of groups holding a strand %u (%.1f %%)\n",
-                hs[0], hs[32], hs[64], hs[96], hs[128], hs[160], hs[192], g[0], g[1], 100.0 * g[1] / (64.0 * g[0]), g[2], 100.0 * g[2] / (64.0 * g[0]));
+                word(0, FMD_CW_COUNT), word(1, FMD_CW_COUNT), word(2, FMD_CW_COUNT), word(3, FMD_CW_COUNT), word(4, FMD_CW_COUNT), word(5, FMD_CW_COUNT), word(FMD_CLS_SLOW, FMD_CW_COUNT),
+                gr, gl, 100.0 * gl / (64.0 * gr), gh, 100.0 * gh / (64.0 * gr));
         for (int k = 0; k < 2 * FMD_GRP_CLASSES; ++k) {
-            const uint32_t *f = hs + (FMD_GRP_CLASSES + 1 + k) * FMD_CLS_CNT_STRIDE;
-            if (f[0]) fprintf(stderr, "[fast stats] G=%d %s: %u strands, %u handed on (%u) | wave rounds %u (%u with a second base), live lanes %.1f %%, lanes of groups holding a strand %.1f %%\n",
-                              fmd_grp_size(k % FMD_GRP_CLASSES), k >= FMD_GRP_CLASSES ? "64-bit" : "32-bit", f[0], f[8], f[9], f[10], f[13], 100.0 * f[11] / (64.0 * f[10]), 100.0 * f[12] / (64.0 * f[10]));
+            const int f = fmd_cls_fast(k);
+            const uint32_t fr = word(f, FMD_CW_FAST_ROUNDS);
+            if (word(f, FMD_CW_COUNT)) fprintf(stderr, "[fast stats] G=%d %s: %u strands, %u handed on (%u) | wave rounds %u (%u with a second base), live lanes %.1f %%, lanes of groups holding a strand %.1f %%\n",
+                              fmd_grp_size(k % FMD_GRP_CLASSES), k >= FMD_GRP_CLASSES ? "64-bit" : "32-bit", word(f, FMD_CW_COUNT), word(f, FMD_CW_HANDED), word(f, FMD_CW_HANDED_AT0), fr,
+                              word(f, FMD_CW_FAST_ROUNDS2), 100.0 * word(f, FMD_CW_FAST_LIVE) / (64.0 * fr), 100.0 * word(f, FMD_CW_FAST_HELD) / (64.0 * fr));
         }
     }
 #endif
@@ -212,12 +232,7 @@ extern "C" int fmd_ovlp_dev(fmd_dev_t *h, void *stream_, size_t n, const uint64_
     OvlBatch o;
     o.h = h; o.ix = fmd_view(h);
     o.ids = d_ids; o.min_match = min_match; o.max_len = max_len; o.max_nei = max_nei; o.seq_stride = seq_stride;
-    o.stride_r = (uint32_t)align_up(max_len, 16);
-    o.cap = fmd_ovlp_list_cap(max_len, min_match);
-    o.srev = (uint8_t *)d_work;
-    o.listA = (fmd_intv_t *)((uint8_t *)d_work + align_up(n * (size_t)o.stride_r, 256));
-    o.listB = (fmd_intv_t *)((uint8_t *)o.listA + align_up(n * (size_t)o.cap * sizeof(fmd_intv_t), 256));
-    o.cls = (uint32_t *)((uint8_t *)o.listB + align_up(n * (size_t)o.cap * sizeof(fmd_intv_t), 256));
+    o.carve((uint8_t *)d_work, n);
     o.rec = d_rec; o.nei = d_nei; o.seq = d_seq; o.gidx = nullptr; o.park = nullptr; o.keys = nullptr;
 
     int parts, walk_cu, grp_cu, fast_cu;
@@ -332,12 +347,7 @@ static int ovl_tail(fmd_dev *h, hipStream_t st, size_t np, const uint32_t *rows,
 {
     OvlBatch o;
     o.h = h; o.ix = fmd_view(h); o.ids = d_ids; o.min_match = min_match; o.max_len = max_len; o.max_nei = max_nei; o.seq_stride = seq_stride;
-    o.stride_r = (uint32_t)align_up(max_len, 16);
-    o.cap = fmd_ovlp_list_cap(max_len, min_match);
-    o.srev = area;
-    o.listA = (fmd_intv_t *)(o.srev + align_up(area_strands * (size_t)o.stride_r, 256));
-    o.listB = (fmd_intv_t *)((uint8_t *)o.listA + align_up(area_strands * (size_t)o.cap * sizeof(fmd_intv_t), 256));
-    o.cls = (uint32_t *)((uint8_t *)o.listB + align_up(area_strands * (size_t)o.cap * sizeof(fmd_intv_t), 256));
+    o.carve(area, area_strands);
     o.rec = d_rec; o.nei = d_nei; o.seq = d_seq; o.park = park;
     o.gidx = rows; o.keys = keys;
     ovl_phase_a(o, st, 0, np, 0);
@@ -475,11 +485,12 @@ extern "C" int fmd_ovlp_check_left_dev(fmd_dev_t *h, void *stream_, size_t n, in
     if (work_bytes < fmd_ovlp_work_bytes(n, max_len, min_match)) return FMD_E_ARG;
     FMD_HIP_TRY(hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)stream_;
-    const uint32_t stride_r = (uint32_t)align_up(max_len, 16);
-    const uint32_t cap = fmd_ovlp_list_cap(max_len, min_match);
-    fmd_intv_t *listA = (fmd_intv_t *)((uint8_t *)d_work + align_up(n * (size_t)stride_r, 256));
-    fmd_intv_t *listB = (fmd_intv_t *)((uint8_t *)listA + align_up(n * (size_t)cap * sizeof(fmd_intv_t), 256));
-    fmd_launch_check_left(fmd_grid_for(h, n), st, fmd_next_queue(h, st), fmd_view(h), n, min_match, cap, listA, listB, d_rec, d_seq, seq_stride);
+    const BatchLayout L = batch_layout(n, max_len, min_match);
+    NeiArgs a;   // (the two candidate lists of the batch's area are its scratch; rows in batch order)
+    a.ix = fmd_view(h); a.grid = fmd_grid_for(h, n); a.np = n; a.min_match = min_match; a.cap = L.cap;
+    a.listA = (fmd_intv_t *)((uint8_t *)d_work + L.listA); a.listB = (fmd_intv_t *)((uint8_t *)d_work + L.listB);
+    a.rec = d_rec; a.seq = const_cast<uint8_t *>(d_seq); a.seq_stride = seq_stride;
+    fmd_launch_check_left(a, st, fmd_next_queue(h, st));
     FMD_CHECK_LAUNCH("k_ovl_cls");
     return FMD_OK;
 }
@@ -495,11 +506,10 @@ extern "C" int fmd_seqinfo_dev(fmd_dev_t *h, void *stream_, size_t n, const uint
     if (n >= 0xffffff00ull || work_bytes < fmd_ovlp_work_bytes(n, max_len, (int)max_len - 1)) return FMD_E_ARG;
     FMD_HIP_TRY(hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)stream_;
-    const uint32_t stride_r = (uint32_t)align_up(max_len, 16);
-    const uint32_t cap = fmd_ovlp_list_cap(max_len, (int)max_len - 1);
+    const BatchLayout L = batch_layout(n, max_len, (int)max_len - 1);
     WalkArgs a;   // the one-pass walk with no threshold: records and the stash, no candidates
-    a.ix = fmd_view(h); a.n = n; a.ids = d_ids; a.info_only = 1; a.rec = d_rec; a.srev = (uint8_t *)d_work; a.stride_r = stride_r;
-    a.listA = (fmd_intv_t *)((uint8_t *)d_work + align_up(n * (size_t)stride_r, 256)); a.cap = cap;
+    a.ix = fmd_view(h); a.n = n; a.ids = d_ids; a.info_only = 1; a.rec = d_rec; a.srev = (uint8_t *)d_work + L.srev; a.stride_r = L.stride_r;
+    a.listA = (fmd_intv_t *)((uint8_t *)d_work + L.listA); a.cap = L.cap;
     fmd_launch_walk_whole(h, st, a, max_len, d_seq, seq_stride, 0, FMD_TICKET_CHUNK);
     FMD_CHECK_LAUNCH("k_ovl_walk");
     return FMD_OK;

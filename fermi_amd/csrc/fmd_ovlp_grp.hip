@@ -40,7 +40,7 @@ static_assert(GRP_POOL <= 32, "the region ends with 32 block numbers");
 // (ballots per wave, LDS across the 16 waves) and ONE atomic per block and class, each counter on
 // its own 128-byte line: per-wave atomics on adjacent words cost 7-15 ms per 2*10^7 strands.
 #define CLS_THREADS 1024
-#define CLS_LISTS FMD_CLS_LISTS            // general class k = k, slow = FMD_GRP_CLASSES, fast class k = FMD_GRP_CLASSES + 1 + k (+ FMD_GRP_CLASSES: 64-bit masks)
+#define CLS_LISTS FMD_CLS_LISTS            // (the list numbers: fmd_kernel_common.h)
 __global__ __launch_bounds__(CLS_THREADS) void k_ovl_classify(size_t n, const fmd_ovlp_rec_t *__restrict__ rec, const fmd_intv_t *__restrict__ listA,
                                                               uint32_t cap, FmdOvlClasses cl, int use_fast, const uint32_t *__restrict__ gidx, int min_cls)
 {
@@ -52,17 +52,10 @@ __global__ __launch_bounds__(CLS_THREADS) void k_ovl_classify(size_t n, const fm
         const fmd_ovlp_rec_t *o = rec + (gidx ? (size_t)gidx[i] : i);   // (sorted batches: the record's row is not the slot, fmd_ovlp_sorted_dev)
         if (o->status == 0 && o->n_ovlp > 0 && !(o->flags & FMD_OVLP_F_OVERFLOW)) {
             m = (uint32_t)o->n_ovlp; len = (uint32_t)o->len;
-            // the widest candidate is the last one (shortest overlap): the group kernels count
-            // symbols of BWT[x, x+size) through a 64-position window
+            // the widest candidate is the last one of the list (shortest overlap, pushed first)
             const uint4 *q = (const uint4 *)(listA + i * (size_t)cap + (cap - 1));
             const FmdCand w = cand_decode(q[0], q[1]);
-            cls = FMD_GRP_CLASSES;
-            if (w.sz <= 63 && len < 65535) {
-#pragma unroll
-                for (int k = FMD_GRP_CLASSES - 1; k >= 0; --k) if (k >= min_cls && m <= (uint32_t)fmd_grp_size(k)) cls = k;
-                // the widest candidate was pushed first; the fast kernel checks the others when it loads them
-                if (cls < FMD_GRP_CLASSES && w.narrow && use_fast) cls += FMD_GRP_CLASSES + 1 + (w.sz > 31 ? FMD_GRP_CLASSES : 0);
-            }
+            cls = fmd_ovl_list_of(m, len, w.sz <= 63, w.narrow, w.sz > 31, use_fast, min_cls);
         }
     }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -77,13 +70,13 @@ __global__ __launch_bounds__(CLS_THREADS) void k_ovl_classify(size_t n, const fm
     if (threadIdx.x < CLS_LISTS) {             // exclusive scan over the waves, then the block's slice of the list
         uint32_t tot = 0;
         for (int w = 0; w < CLS_THREADS / 64; ++w) { const uint32_t v = wcnt[w][threadIdx.x]; wcnt[w][threadIdx.x] = tot; tot += v; }
-        base[threadIdx.x] = tot ? atomicAdd(cl.cnt + threadIdx.x * FMD_CLS_CNT_STRIDE, tot) : 0;
+        base[threadIdx.x] = tot ? atomicAdd(cl.cnt + fmd_cls_cnt_off((int)threadIdx.x) + FMD_CW_COUNT, tot) : 0;
     }
     __syncthreads();
     if (cls >= 0) {
         const uint32_t k = base[cls] + wcnt[wave][cls] + in_wave;
-        if (cls == FMD_GRP_CLASSES) cl.lslow[k] = (uint32_t)i;
-        else { uint32_t *lst = cls < FMD_GRP_CLASSES ? cl.lst[cls] : cl.fast[cls - FMD_GRP_CLASSES - 1]; lst[2 * k] = (uint32_t)i; lst[2 * k + 1] = m | len << 16; }   // fast[5..9]: the 64-bit lists
+        if (cls == FMD_CLS_SLOW) cl.lslow[k] = (uint32_t)i;
+        else { uint32_t *lst = cls < FMD_CLS_SLOW ? cl.lst[cls] : cl.fast[cls - fmd_cls_fast(0)]; lst[2 * k] = (uint32_t)i; lst[2 * k + 1] = m | len << 16; }
     }
 }
 
@@ -93,13 +86,12 @@ __global__ __launch_bounds__(CLS_THREADS) void k_ovl_classify(size_t n, const fm
 // 11 % of all group rounds of k_ovl_nei_grp and 10-17 % of k_ovl_nei_fast's were groups with nothing left (GRP_STATS, 10^7 reads with 1 % errors).
 // DYN: a wave reserves CHUNKS of consecutive positions from one counter (one atomic per chunk: atomics on one address serialise at ~14 ns; guided
 // sizes 16 .. FMD_DEAL_CHUNK, the first chunk of every wave without an atomic), a group asks when its prefetch slot is empty.  Consecutive positions still go to groups that run
-// at the same time, which is what the order of the list is for.  The counter is word 16 of the list counter's own 128-byte line (zeroed
+// at the same time, which is what the order of the list is for.  The counter is word FMD_CW_DEAL of the list counter's own 128-byte line (zeroed
 // with the header of the batch).  Returns the position for every lane of a group that asked (`want`: group-uniform), 0xffffffff otherwise and once
 // the list is dealt out (`dry`).
 #ifndef FMD_DEAL_CHUNK
 #define FMD_DEAL_CHUNK 64
 #endif
-#define FMD_DEAL_WORD 16
 static int nei_dyn(void)   // FMD_NEI_DYN=0: A/B switch, the work lists dealt round-robin as before
 {
     const char *e = getenv("FMD_NEI_DYN");
@@ -197,7 +189,7 @@ __global__ __launch_bounds__(64, 4) void k_ovl_nei_grp(FmdIndexView ix, const ui
     // of the live candidates' interval sizes bounds the lanes the strand can EVER need again (every child takes at least one occurrence of its
     // parent's with it), so a strand whose live candidates are all single occurrences and fit a smaller group moves there for good -- as it stands
     // after the round (FMD_LIST_RESUME), to the second-pass list of that class (the storage of its fast list, idle by now; counter in word
-    // FMD_DOWN_WORD of that list's line), which the launcher runs after the first pass, largest class first.  Slots are reserved FMD_FAST_CHUNK at a
+    // FMD_CW_DOWN of that list's line), which the launcher runs after the first pass, largest class first.  Slots are reserved FMD_FAST_CHUNK at a
     // time per wave and target class (one atomic per strand on one address serialises), unused ones stay holes.  down_cap = entries a second-pass
     // list holds (0: strands stay where they are, the A/B switch FMD_GRP_DOWN=0).
     constexpr int MYK = G == 4 ? 0 : G == 8 ? 1 : G == 12 ? 2 : G == 16 ? 3 : G == 21 ? 4 : 5;
@@ -223,7 +215,7 @@ __global__ __launch_bounds__(64, 4) void k_ovl_nei_grp(FmdIndexView ix, const ui
                     const uint64_t hm = __ballot(mv == (uint32_t)(tt + 1) && j == 0 && g < S);
                     if (hm == 0) continue;
                     const int k2 = MYK - 1 - tt;
-                    uint32_t *lst2 = cl.fast[k2], *cnt2 = cl.cnt + (FMD_GRP_CLASSES + 1 + k2) * FMD_CLS_CNT_STRIDE + FMD_DOWN_WORD;
+                    uint32_t *lst2 = cl.fast[k2], *cnt2 = cl.cnt + fmd_cls_cnt_off(fmd_cls_fast(k2)) + FMD_CW_DOWN;
                     const uint32_t n = (uint32_t)__popcll(hm), room = res_end[tt] - res_cur[tt];   // n <= S <= FMD_FAST_CHUNK
                     uint32_t base = 0;
                     bool got = true;
@@ -297,7 +289,7 @@ __global__ __launch_bounds__(64, 4) void k_ovl_nei_grp(FmdIndexView ix, const ui
         // ---- one round: forward extension (symbols of BWT[x1, x1 + size)) from one gather
         const bool live = active && alive;
 #ifdef GRP_STATS
-        { const uint32_t nl = (uint32_t)__popcll(__ballot(live)); if (lane == 0) { atomicAdd(slow_n + 8, 1u); atomicAdd(slow_n + 9, nl); atomicAdd(slow_n + 10, (uint32_t)__popcll(act_m)); } }
+        { const uint32_t nl = (uint32_t)__popcll(__ballot(live)); if (lane == 0) { atomicAdd(slow_n + (FMD_CW_GRP_ROUNDS - FMD_CW_LATE), 1u); atomicAdd(slow_n + (FMD_CW_GRP_LIVE - FMD_CW_LATE), nl); atomicAdd(slow_n + (FMD_CW_GRP_HELD - FMD_CW_LATE), (uint32_t)__popcll(act_m)); } }
 #endif
         const uint64_t ke = live ? x1 - 1 : NONE64;
         // the l side lies at most 63 positions after the k side: same block or the next one
@@ -505,7 +497,7 @@ __global__ __launch_bounds__(64, 4) void k_ovl_nei_grp(FmdIndexView ix, const ui
                 if (k2 < FMD_GRP_CLASSES && fmd_resume_fits((uint32_t)round, n_nei, nei0_info, 0u) && (uint32_t)ncur <= cap) {
                     if (alive) fmd_resume_encode((uint4 *)(listB + sid * (size_t)cap + j), x1, sz, D, r0, pos, (uint32_t)round, n_nei, nei0_info, LF_GET(flags), (uint32_t)cat, flags & 0xffu);
                     if (j == 0) {
-                        const uint32_t k = atomicAdd(cl.cnt + k2 * FMD_CLS_CNT_STRIDE, 1u);
+                        const uint32_t k = atomicAdd(cl.cnt + fmd_cls_cnt_off(k2) + FMD_CW_COUNT, 1u);
                         cl.lst[k2][2 * (size_t)k] = sid; cl.lst[k2][2 * (size_t)k + 1] = (uint32_t)ncur | FMD_LIST_RESUME | (uint32_t)ori_l << 16;
                     }
                 } else if (j == 0) { const uint32_t k = atomicAdd(slow_n, 1u); slow_list[k] = sid; }   // the lane-per-strand kernel starts it over
@@ -530,7 +522,7 @@ __global__ __launch_bounds__(64, 4) void k_ovl_nei_grp(FmdIndexView ix, const ui
                     o->flags |= flags & 0xffu;
                     // a fake fork (contained reads, unitig.c:158-176): the record stands as fm6_get_nei leaves it BEFORE the fix-up; k_ovl_fix
                     // re-derives the appended bases from it (a lane walking ~60 dependent steps has no place in a group kernel)
-                    if (n_nei == 1 && (flags & FMD_OVLP_F_FORKED)) { const uint32_t k = atomicAdd(slow_n + FMD_CLS_FIX_CNT, 1u); slow_list[fix_off + k] = sid; }
+                    if (n_nei == 1 && (flags & FMD_OVLP_F_FORKED)) { const uint32_t k = atomicAdd(slow_n + (FMD_CW_FIX - FMD_CW_LATE), 1u); slow_list[fix_off + k] = sid; }
                 }
                 active = false; alive = false;
             }
@@ -708,7 +700,7 @@ __global__ __launch_bounds__(64, FMD_FAST_LB) void k_ovl_nei_fast(FmdIndexView i
         }
 
 #ifdef GRP_STATS
-        { const uint32_t nl = (uint32_t)__popcll(__ballot(active && alive)); if (lane == 0) { atomicAdd(bail_n + 2, 1u); atomicAdd(bail_n + 3, nl); atomicAdd(bail_n + 4, (uint32_t)__popcll(act_m)); } }
+        { const uint32_t nl = (uint32_t)__popcll(__ballot(active && alive)); if (lane == 0) { atomicAdd(bail_n + (FMD_CW_FAST_ROUNDS - FMD_CW_HANDED), 1u); atomicAdd(bail_n + (FMD_CW_FAST_LIVE - FMD_CW_HANDED), nl); atomicAdd(bail_n + (FMD_CW_FAST_HELD - FMD_CW_HANDED), (uint32_t)__popcll(act_m)); } }
 #endif
         // ---- the window of every resident strand: BWT[X1, X1 + szw), its block(s) into pool slots 2g (2g + 1)
         uint32_t bke, oke;
@@ -743,7 +735,7 @@ __global__ __launch_bounds__(64, FMD_FAST_LB) void k_ovl_nei_fast(FmdIndexView i
         bool bail = false;
         if (__ballot(active && ((xa && xa != any) || (ya && ya != any) || (za && za != any) || cs > 4))) {
 #ifdef GRP_STATS
-            if (lane == 0) atomicAdd(bail_n + 5, 1u);
+            if (lane == 0) atomicAdd(bail_n + (FMD_CW_FAST_ROUNDS2 - FMD_CW_HANDED), 1u);
 #endif
             // per base: how many reads of my range show it (order of the x[0] side: $ T G C A N), and does one start with it?
             const M m1 = X & ~Y & ~Z & mw, m2 = ~X & Y & ~Z & mw, m3 = X & Y & ~Z & mw, m4 = ~X & ~Y & Z & mw, m5 = X & ~Y & Z & mw;
@@ -830,15 +822,15 @@ static int fast_blocks_per_cu(void)
 }
 int fmd_nei_fast_available(void) { return 1; }
 static inline int fast_grid(int waves) { return waves < FMD_FAST_MAX_WAVES ? waves : FMD_FAST_MAX_WAVES; }   // (the hand-over lists have room for this many waves' holes)
-void fmd_launch_nei_fast(int cls, int wide, int n_cu, int per_cu_cap, hipStream_t st, const FmdIndexView &ix, const uint32_t *list, const uint32_t *list_n, uint32_t cap,
-                         const fmd_intv_t *listA, fmd_intv_t *listB, fmd_ovlp_rec_t *rec, fmd_intv_t *nei_out, uint32_t max_nei, uint8_t *seq_out,
-                         uint32_t seq_stride, uint32_t *gen_list, uint32_t *gen_n, uint32_t *bail_n, uint32_t *slow_list, uint32_t *slow_n, const uint32_t *gidx)
+void fmd_launch_nei_fast(const NeiArgs &a, int cls, int wide, int per_cu_cap, hipStream_t st)
 {
     const char *e = getenv("FMD_FAST_WAVES"); // A/B knob: resident waves per CU
     if (e && atoi(e) > 0 && (per_cu_cap <= 0 || atoi(e) < per_cu_cap)) per_cu_cap = atoi(e);
     const bool dyn = nei_dyn() != 0;
-    uint32_t *deal = (uint32_t *)list_n + FMD_DEAL_WORD;
-#define FAST_LAUNCH_(K, M, DY) k_ovl_nei_fast<fmd_grp_size(K), M, DY><<<fast_grid(n_cu * grp_cap(fast_blocks_per_cu<fmd_grp_size(K), M, DY>(), per_cu_cap)), 64, 0, st>>>(ix, list, list_n, cap, listA, listB, rec, nei_out, max_nei, seq_out, seq_stride, gen_list, gen_n, bail_n, slow_list, slow_n, gidx, deal)
+    const int fk = cls + (wide ? FMD_GRP_CLASSES : 0), fl = fmd_cls_fast(fk);   // the fast list it reads; what it hands on goes to general list cls, what it hands back to the late list
+#define FAST_LAUNCH_(K, M, DY) k_ovl_nei_fast<fmd_grp_size(K), M, DY><<<fast_grid(a.n_cu * grp_cap(fast_blocks_per_cu<fmd_grp_size(K), M, DY>(), per_cu_cap)), 64, 0, st>>>( \
+        a.ix, a.cl.fast[fk], a.cnt(fl), a.cap, a.listA, a.listB, a.rec, a.nei, a.max_nei, a.seq, a.seq_stride, a.cl.lst[cls], a.cnt(cls), a.cnt(fl, FMD_CW_HANDED), \
+        a.late, a.cnt(FMD_CLS_SLOW, FMD_CW_LATE), a.gidx, a.cnt(fl, FMD_CW_DEAL))
 #define FAST_LAUNCH(K, M) do { if (dyn) FAST_LAUNCH_(K, M, true); else FAST_LAUNCH_(K, M, false); } while (0)
 #define FAST_LAUNCH2(K) do { if (wide) FAST_LAUNCH(K, uint64_t); else FAST_LAUNCH(K, uint32_t); } while (0)
     switch (cls) {
@@ -870,16 +862,19 @@ static int grp_blocks_per_cu(void)
     }
     return cached;
 }
-void fmd_launch_nei_grp(int cls, int n_cu, int per_cu_cap, hipStream_t st, const FmdIndexView &ix, const uint32_t *list, const uint32_t *list_n, uint32_t cap,
-                        const fmd_intv_t *listA, fmd_intv_t *listB, const FmdOvlClasses &cl, fmd_ovlp_rec_t *rec, fmd_intv_t *nei_out, uint32_t max_nei, uint8_t *seq_out,
-                        uint32_t seq_stride, uint32_t *slow_list, uint32_t *slow_n, const uint32_t *gidx, size_t fix_off, uint32_t down_cap, int second_pass)
+void fmd_launch_nei_grp(const NeiArgs &a, int cls, int per_cu_cap, hipStream_t st, uint32_t down_cap, int second_pass)
 {
     const uint32_t n_max = second_pass ? down_cap / FMD_FAST_CHUNK * FMD_FAST_CHUNK : 0u;
     const char *eq = getenv("FMD_GRP_QUIET");
     const int quiet_on = !(eq && atoi(eq) == 0);
     const bool dyn = nei_dyn() != 0;
-    uint32_t *deal = (uint32_t *)list_n + FMD_DEAL_WORD;
-#define GRP_LAUNCH_(K, DY) k_ovl_nei_grp<fmd_grp_size(K), DY><<<n_cu * grp_cap(grp_blocks_per_cu<fmd_grp_size(K), DY>(), per_cu_cap), 64, 0, st>>>(ix, list, list_n, cap, listA, listB, cl, rec, nei_out, max_nei, seq_out, seq_stride, slow_list, slow_n, gidx, fix_off, deal, down_cap, n_max, quiet_on)
+    // first pass: general list cls; second pass: the strands that moved down to class cls, where fast list cls was (count and deal counter: words of that list's line)
+    const int l = second_pass ? fmd_cls_fast(cls) : cls;
+    const uint32_t *list = second_pass ? a.cl.fast[cls] : a.cl.lst[cls];
+    const size_t fix_off = (size_t)(a.fix - a.late);   // the kernel appends to both through the late list
+#define GRP_LAUNCH_(K, DY) k_ovl_nei_grp<fmd_grp_size(K), DY><<<a.n_cu * grp_cap(grp_blocks_per_cu<fmd_grp_size(K), DY>(), per_cu_cap), 64, 0, st>>>( \
+        a.ix, list, a.cnt(l, second_pass ? FMD_CW_DOWN : FMD_CW_COUNT), a.cap, a.listA, a.listB, a.cl, a.rec, a.nei, a.max_nei, a.seq, a.seq_stride, \
+        a.late, a.cnt(FMD_CLS_SLOW, FMD_CW_LATE), a.gidx, fix_off, a.cnt(l, second_pass ? FMD_CW_DOWN_DEAL : FMD_CW_DEAL), down_cap, n_max, quiet_on)
 #define GRP_LAUNCH(K) do { if (dyn) GRP_LAUNCH_(K, true); else GRP_LAUNCH_(K, false); } while (0)
     switch (cls) {
     case 0: GRP_LAUNCH(0); break;
@@ -892,8 +887,7 @@ void fmd_launch_nei_grp(int cls, int n_cu, int per_cu_cap, hipStream_t st, const
 #undef GRP_LAUNCH
 #undef GRP_LAUNCH_
 }
-void fmd_launch_classify(hipStream_t st, size_t n, const fmd_ovlp_rec_t *rec, const fmd_intv_t *listA, uint32_t cap, FmdOvlClasses cl, int use_fast, const uint32_t *gidx)
+void fmd_launch_classify(const NeiArgs &a, hipStream_t st, int use_fast, int min_cls)
 {
-    const char *e = getenv("FMD_GRP4");   // A/B knob: FMD_GRP4=0 = no groups of 4 (round 3's classes)
-    k_ovl_classify<<<(unsigned)((n + CLS_THREADS - 1) / CLS_THREADS), CLS_THREADS, 0, st>>>(n, rec, listA, cap, cl, use_fast, gidx, e && atoi(e) == 0 ? 1 : 0);
+    k_ovl_classify<<<(unsigned)((a.np + CLS_THREADS - 1) / CLS_THREADS), CLS_THREADS, 0, st>>>(a.np, a.rec, a.listA, a.cap, a.cl, use_fast, a.gidx, min_cls);
 }

@@ -376,11 +376,10 @@ int fmd_nei_lane_enabled(void)
 // classes whose candidates fit the registers of a lane: up to 21 (the larger group size is the group kernels' business)
 int fmd_nei_lane_class_ok(int cls, int wide) { (void)wide; return cls >= 0 && cls <= 4; }   // up to 21 candidates (32: the group form)
 
-void fmd_launch_nei_lane(int cls, int wide, int n_cu, int per_cu_cap, hipStream_t st, const FmdIndexView &ix, const uint32_t *list, const uint32_t *list_n, uint32_t cap,
-                         const fmd_intv_t *listA, fmd_intv_t *listB, fmd_ovlp_rec_t *rec, fmd_intv_t *nei_out, uint32_t max_nei, uint8_t *seq_out,
-                         uint32_t seq_stride, uint32_t *gen_list, uint32_t *gen_n, uint32_t *bail_n, const uint32_t *gidx)
+void fmd_launch_nei_lane(const NeiArgs &a, int cls, int wide, int per_cu_cap, hipStream_t st)
 {
-    uint32_t *queue = (uint32_t *)list_n + FMD_DEAL_WORD_LANE;      // the ticket counter: a word of the list counter's own line (zeroed with the header of the batch)
+    const int fk = cls + (wide ? FMD_GRP_CLASSES : 0), fl = fmd_cls_fast(fk);   // the fast list it reads; what it hands on goes to general list cls
+    uint32_t *queue = a.cnt(fl, FMD_CW_DEAL);                       // the ticket counter: a word of the list counter's own line (zeroed with the header of the batch)
     const char *e = getenv("FMD_LANE_WAVES");                       // A/B knob: resident waves per CU
     const char *et = getenv("FMD_LANE_TICKETS");                    // largest ticket chunk (guided sizes below it)
     const uint32_t tk_chunk = et && atoi(et) >= 16 ? (uint32_t)atoi(et) : 256u;
@@ -394,9 +393,10 @@ void fmd_launch_nei_lane(int cls, int wide, int n_cu, int per_cu_cap, hipStream_
         int per = cached; \
         if (per_cu_cap > 0 && per_cu_cap < per) per = per_cu_cap; \
         if (e && atoi(e) > 0 && atoi(e) < per) per = atoi(e); \
-        int grid = n_cu * per; \
+        int grid = a.n_cu * per; \
         if (grid > FMD_FAST_MAX_WAVES) grid = FMD_FAST_MAX_WAVES; \
-        k_ovl_nei_lane<fmd_grp_size(K), MM><<<grid, 64, 0, st>>>(ix, list, list_n, cap, listA, listB, rec, nei_out, max_nei, seq_out, seq_stride, gen_list, gen_n, bail_n, gidx, queue, tk_chunk, slow_min, adm_min); \
+        k_ovl_nei_lane<fmd_grp_size(K), MM><<<grid, 64, 0, st>>>(a.ix, a.cl.fast[fk], a.cnt(fl), a.cap, a.listA, a.listB, a.rec, a.nei, a.max_nei, a.seq, a.seq_stride, \
+                                                                 a.cl.lst[cls], a.cnt(cls), a.cnt(fl, FMD_CW_HANDED), a.gidx, queue, tk_chunk, slow_min, adm_min); \
     } while (0)
 #define LANE_LAUNCH2(K) do { if (wide) LANE_LAUNCH_(K, uint64_t); else LANE_LAUNCH_(K, uint32_t); } while (0)
     switch (cls) {

@@ -450,19 +450,16 @@ __global__ __launch_bounds__(64) void k_ovl_cls(FmdIndexView ix, size_t n, int m
 }
 
 // ------------------------------------------------------------------------------- launchers
-void fmd_launch_nei_slow(int grid, hipStream_t st, uint32_t *queue, const FmdIndexView &ix, size_t n, int min_match, const uint8_t *srev, uint32_t stride_r, uint32_t cap,
-                         fmd_intv_t *listA, fmd_intv_t *listB, fmd_ovlp_rec_t *rec, fmd_intv_t *nei_out, uint32_t max_nei, uint8_t *seq_out, uint32_t seq_stride,
-                         const uint32_t *work_list, const uint32_t *work_n, const uint32_t *gidx)
+void fmd_launch_nei_slow(const NeiArgs &a, hipStream_t st, uint32_t *queue, int late)
 {
-    k_ovl_nei<<<grid, 64, 0, st>>>(ix, n, min_match, srev, stride_r, cap, listA, listB, rec, nei_out, max_nei, seq_out, seq_stride, queue, work_list, work_n, gidx);
+    const uint32_t *list = late ? a.late : a.cl.lslow, *list_n = a.cnt(FMD_CLS_SLOW, late ? FMD_CW_LATE : FMD_CW_COUNT);
+    k_ovl_nei<<<a.grid, 64, 0, st>>>(a.ix, a.np, a.min_match, a.srev, a.stride_r, a.cap, a.listA, a.listB, a.rec, a.nei, a.max_nei, a.seq, a.seq_stride, queue, list, list_n, a.gidx);
 }
-void fmd_launch_nei_fix(int grid, hipStream_t st, uint32_t *queue, const FmdIndexView &ix, const uint32_t *list, const uint32_t *list_n, const uint8_t *srev, uint32_t stride_r,
-                        fmd_ovlp_rec_t *rec, const fmd_intv_t *nei_out, uint32_t max_nei, uint8_t *seq_out, uint32_t seq_stride, const uint32_t *gidx)
+void fmd_launch_nei_fix(const NeiArgs &a, hipStream_t st, uint32_t *queue)
 {
-    k_ovl_fix<<<grid, 64, 0, st>>>(ix, list, list_n, srev, stride_r, rec, nei_out, max_nei, seq_out, seq_stride, queue, gidx);
+    k_ovl_fix<<<a.grid, 64, 0, st>>>(a.ix, a.fix, a.cnt(FMD_CLS_SLOW, FMD_CW_FIX), a.srev, a.stride_r, a.rec, a.nei, a.max_nei, a.seq, a.seq_stride, queue, a.gidx);
 }
-void fmd_launch_check_left(int grid, hipStream_t st, uint32_t *queue, const FmdIndexView &ix, size_t n, int min_match, uint32_t cap, fmd_intv_t *listA, fmd_intv_t *listB,
-                           fmd_ovlp_rec_t *rec, const uint8_t *seq, uint32_t seq_stride)
+void fmd_launch_check_left(const NeiArgs &a, hipStream_t st, uint32_t *queue)
 {
-    k_ovl_cls<<<grid, 64, 0, st>>>(ix, n, min_match, cap, listA, listB, rec, seq, seq_stride, queue);
+    k_ovl_cls<<<a.grid, 64, 0, st>>>(a.ix, a.np, a.min_match, a.cap, a.listA, a.listB, a.rec, a.seq, a.seq_stride, queue);
 }

@@ -209,15 +209,8 @@ __device__ __forceinline__ void walk_run(const FmdIndexView &ix, size_t n, const
                     // gets its row -- k_ovl_seq_out's conditions)
                     if (flags & WALK_F_HASN) redo[1 + atomicAdd(redo, 1u)] = (uint32_t)sid;
                     else walk_emit_row(walk_ls + fmd_lane(), depth, seq_out + gs * (size_t)seq_stride);
-                    if (cls != nullptr && !(flags & WALK_F_CONTAINED) && npush > 0 && !(flags & FMD_OVLP_F_OVERFLOW)) {   // k_ovl_classify's rule (fmd_ovlp_grp.hip)
-                        int c = FMD_GRP_CLASSES;
-                        if ((flags & WALK_F_W63) && depth < 65535u) {
-#pragma unroll
-                            for (int kk = FMD_GRP_CLASSES - 1; kk >= 0; --kk) if (kk >= min_cls && npush <= (uint32_t)fmd_grp_size(kk)) c = kk;
-                            if (c < FMD_GRP_CLASSES && (flags & WALK_F_WNARROW) && use_fast) c += FMD_GRP_CLASSES + 1 + ((flags & WALK_F_W32) ? FMD_GRP_CLASSES : 0);
-                        }
-                        fin_cls = c;
-                    }
+                    if (cls != nullptr && !(flags & WALK_F_CONTAINED) && npush > 0 && !(flags & FMD_OVLP_F_OVERFLOW))   // (the strands k_ovl_classify takes from the records)
+                        fin_cls = fmd_ovl_list_of(npush, depth, (flags & WALK_F_W63) != 0, (flags & WALK_F_WNARROW) != 0, (flags & WALK_F_W32) != 0, use_fast, min_cls);
                     st = WK_IDLE;
                 }
             }
@@ -225,7 +218,8 @@ __device__ __forceinline__ void walk_run(const FmdIndexView &ix, size_t n, const
         if (MODE == WALK_TAIL2 && cls != nullptr) {
             // k_ovl_classify's work, by the lanes that have just closed a strand: one returning atomic per
             // list that gets entries, all of them issued at once (lane j reserves for the j-th distinct list), then every lane writes its entry.  The lists
-            // and counters are where ovl_phase_b expects them (FmdOvlClasses over `cls`); depth, npush and sid are still the finished strand's.
+            // and counters are where ovl_phase_b expects them (`cls` = the area of the part: fmd_cls_list, fmd_cls_cnt_off); depth, npush and sid are still
+            // the finished strand's.
             uint64_t rem = __ballot(fin_cls >= 0);
             if (rem) {
                 const int lane = fmd_lane();
@@ -239,16 +233,12 @@ __device__ __forceinline__ void walk_run(const FmdIndexView &ix, size_t n, const
                     rem &= ~mk; ++nc;
                 }
                 uint32_t base = 0;
-                if (lane < nc) base = atomicAdd(cls + my_c * FMD_CLS_CNT_STRIDE, my_cnt);
+                if (lane < nc) base = atomicAdd(cls + fmd_cls_cnt_off(my_c) + FMD_CW_COUNT, my_cnt);
                 base = (uint32_t)__shfl((int)base, (int)my_slot) + my_rank;
                 if (fin_cls >= 0) {
-                    const size_t gl = 2 * n + 2 * (size_t)FMD_FAST_RESERVE;           // words of a general list
-                    uint32_t *lslow = cls + FMD_CLS_HEADER_U32 + gl * FMD_GRP_CLASSES;
-                    if (fin_cls == FMD_GRP_CLASSES) lslow[base] = (uint32_t)sid;
-                    else {
-                        uint32_t *lst = fin_cls < FMD_GRP_CLASSES ? cls + FMD_CLS_HEADER_U32 + gl * fin_cls : lslow + n + 2 * n * (size_t)(fin_cls - FMD_GRP_CLASSES - 1);
-                        lst[2 * base] = (uint32_t)sid; lst[2 * base + 1] = npush | depth << 16;
-                    }
+                    uint32_t *lslow = fmd_cls_list(cls, FMD_CLS_SLOW, n);   // (n: the strands of this launch, i.e. of the part)
+                    if (fin_cls == FMD_CLS_SLOW) lslow[base] = (uint32_t)sid;
+                    else { uint32_t *lst = fmd_cls_list(cls, fin_cls, n); lst[2 * base] = (uint32_t)sid; lst[2 * base + 1] = npush | depth << 16; }
                     fin_cls = -1;
                 }
             }

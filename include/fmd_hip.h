@@ -139,7 +139,7 @@ int fmd_retrieve_batch(fmd_dev_t *h, size_t n, const uint64_t *x, uint8_t *seqs,
  * at the last position, not the marginal counts); first_bad = the smallest of them. */
 int fmd_dev_export_bwt(fmd_dev_t *h, uint64_t first, uint64_t n, uint8_t *bwt);
 int fmd_dev_check_rank(fmd_dev_t *h, uint64_t *n_bad, uint64_t *first_bad);
-/* The two-base blocks (16 bits per symbol beside the index; fmd_pair.hip): what the sorted overlap job reads below min_match, two bases per
+/* The two-base blocks (32 bits per symbol beside the 8 of the rank blocks; fmd_pair.hip): what the sorted overlap job reads below min_match, two bases per
  * 128-byte line where the rank blocks give one per 64-byte line -- same results, fewer requests.  The job builds them on first use where they fit
  * (FMD_PAIR=0: never, FMD_PAIR=1: whenever the allocation succeeds); this call builds them now (*built = 1 when the handle has them).  The
  * reference has nothing like it: rld_rank2a (rld.c:457) is asked once per base (unitig.c:47-59, exact.c:59-70).
@@ -432,7 +432,7 @@ typedef struct {
     /* host_table = 2 (the same on every rank): the root keeps NO table.  Every piece of every peer, once it has landed in pinned host memory, is handed to
      * row_sink -- n_rows packed rows as fmd_ovlp_pack_rows_dev writes them: ids[n_rows], prec[n_rows], off[n_rows + 1] into var -- on the thread that runs the
      * step, while the GPUs compute and pack the next piece; the buffers are reused two pieces later.  What unitig.c:394-404 does by joining its workers into
-     * one graph: here the consumer (fermi_amd/host/dist_root.c folds the rows into the 44.5-byte rows `unitig` walks) takes them as they arrive, and the
+     * one graph: here the consumer (fmdh_dist_root_sink, fermi_amd/host/ovlp_table.c, folds the rows into the 44.5-byte rows `unitig` walks) takes them as they arrive, and the
      * root's memory is what the consumer keeps.  A non-zero return fails the step on every rank (FMD_E_IO).  Only the root's row_sink / sink_ctx are read.
      * A step that fails (any rank, any reason) has handed the sink SOME of its pieces: what the consumer holds then is incomplete -- it starts over. */
     int (*row_sink)(void *ctx, uint64_t n_rows, const uint32_t *ids, const fmd_ovlp_rec_t *prec, const uint64_t *off, const uint8_t *var, uint32_t max_nei);
