@@ -17,6 +17,8 @@ NONE64 = np.uint64(0xFFFFFFFFFFFFFFFF)
 OVLP_DT = np.dtype([("rank", "<u8"), ("k", "<u8", 3), ("len", "<i4"), ("status", "<i4"), ("n_ovlp", "<i4"),
                     ("rbeg", "<i4"), ("ext_len", "<i4"), ("n_nei", "<i4"), ("flags", "<u4"), ("reserved", "<u2"), ("lfork", "<u2")])
 OVLP_F_FORKED, OVLP_F_OVERFLOW, OVLP_F_FIXED = 1, 2, 4
+LOCATE_RUN_DT = np.dtype([("rank", "<u8"), ("n", "<u4"), ("off", "<u4"), ("query", "<u4"), ("reserved", "<u4")])  # fmd_locate_run_t
+LOCATE_STAT_DT = np.dtype([(f, "<u8") for f in ("n_runs", "n_rows", "n_skipped", "n_unfinished", "overflow", "n_ext")])  # fmd_locate_stat_t
 
 # every symbol include/fmd_hip.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
@@ -45,6 +47,7 @@ ABI_SYMBOLS = [
     "fmd_fltuniq_batch_limits",
     "fmd_scaf_links_work_bytes", "fmd_scaf_links_dev", "fmd_scaf_links",
     "fmd_multi_bsearch_work_bytes", "fmd_multi_bsearch_dev", "fmd_multi_bsearch_batch",
+    "fmd_locate_work_bytes", "fmd_locate_dev", "fmd_locate_batch",
 ]
 
 
@@ -124,6 +127,9 @@ def _configure(L):
     L.fmd_multi_bsearch_dev.argtypes = [C.c_int, vp, vp, sz, vp, u64p, u64p, u64p, u64p, vp, sz]
     L.fmd_multi_bsearch_batch.argtypes = [C.c_int, vp, sz, vp, u64p, u64p, u64p, u64p]
     L.fmd_retrieve_dev.argtypes = [vp, vp, sz, u64p, vp, C.c_uint32, vp, u64p]
+    L.fmd_locate_work_bytes.restype = sz; L.fmd_locate_work_bytes.argtypes = [sz, C.c_uint64]
+    L.fmd_locate_dev.argtypes = [vp, vp, sz, u64p, u64p, C.c_uint32, C.c_uint32, vp, C.c_uint64, vp, vp, sz]
+    L.fmd_locate_batch.argtypes = [vp, sz, u64p, u64p, C.c_uint32, C.c_uint32, C.POINTER(vp), C.POINTER(C.c_uint64), vp]
     L.fmd_retrieve_batch.argtypes = [vp, sz, u64p, vp, C.c_uint32, vp, u64p]
     L.fmd_build_bwt.argtypes = [C.c_int, sz, vp, u64p, vp, C.POINTER(C.c_uint64)]
     L.fmd_build_bwt_dev.argtypes = [C.c_int, vp, sz, vp, u64p, C.c_uint64, C.c_uint32, C.c_int, C.POINTER(vp), C.POINTER(C.c_uint64)]
@@ -404,6 +410,42 @@ class DevIndex:
             l = min(int(ln[i]), stride)
             out[i, :l] = seqs[i, :l][::-1]
         return out, ln.astype(np.int32), rank
+
+    def locate_rows(self, beg, cnt, max_occ=1000, max_len=0):
+        """fmd_locate_batch: the sequences that hold the rows [beg[i], beg[i] + cnt[i]) and the offsets of those rows in them, as runs
+        (LOCATE_RUN_DT: sentinel ranks rank .. rank + n - 1 of query `query`, all at offset `off`), sorted by (query, off, rank), and the
+        statistics as a dict.  Intervals above max_occ are left out whole (n_skipped); max_len = 0: walk until every row has ended."""
+        beg = np.ascontiguousarray(beg, dtype=np.uint64); cnt = np.ascontiguousarray(cnt, dtype=np.uint64)
+        if len(beg) != len(cnt):
+            raise FmdError("locate_rows: %d starts, %d counts" % (len(beg), len(cnt)))
+        p, m = C.c_void_p(), C.c_uint64()
+        stat = np.zeros(1, dtype=LOCATE_STAT_DT)
+        check(lib().fmd_locate_batch(self.h, len(beg), _ptr(beg), _ptr(cnt), int(max_occ), int(max_len), C.byref(p), C.byref(m), _ptr(stat)))
+        runs = np.zeros(m.value, dtype=LOCATE_RUN_DT)
+        if m.value:
+            C.memmove(_ptr(runs), p.value, m.value * LOCATE_RUN_DT.itemsize)
+        lib().fmd_host_free(p)
+        return runs, {f: int(stat[0][f]) for f in LOCATE_STAT_DT.names}
+
+    def locate(self, seqs, max_occ=1000, sorted_map=None):
+        """Backward search of every query, then locate: (cnt, located, hit_off, hit_id, hit_pos).  cnt[i] = occurrences; located[i] = its hits
+        are listed (cnt[i] <= max_occ; trivially so for a miss); the hits of query i are hit_id / hit_pos[hit_off[i] : hit_off[i + 1]], sorted
+        by (id, pos): id = the sequence's sentinel rank, or sorted_map[rank] >> 2 with seqsort's map (read = id >> 1, strand = id & 1), pos =
+        the 0-based offset of the match in that strand's sequence as indexed."""
+        cnt, beg, _ = self.backward_search(seqs)
+        runs, _ = self.locate_rows(beg, cnt, max_occ=max_occ)
+        n = len(cnt)
+        located = cnt <= np.uint64(max_occ)
+        q = np.repeat(runs["query"].astype(np.int64), runs["n"])
+        pos = np.repeat(runs["off"].astype(np.int64), runs["n"])
+        first = np.cumsum(runs["n"].astype(np.int64)) - runs["n"].astype(np.int64)
+        ids = np.repeat(runs["rank"].astype(np.int64) - first, runs["n"]) + np.arange(len(q), dtype=np.int64)
+        if sorted_map is not None:
+            ids = (np.asarray(sorted_map, dtype=np.uint64)[ids] >> np.uint64(2)).astype(np.int64)
+        order = np.lexsort((pos, ids, q))
+        hit_off = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum(np.bincount(q, minlength=n), out=hit_off[1:])
+        return cnt, located, hit_off, ids[order], pos[order]
 
 
 FMD_MULTI_MAX = 16   # include/fmd_hip.h

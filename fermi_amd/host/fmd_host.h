@@ -373,6 +373,13 @@ int fmdh_main_ropebwt(int argc, char *argv[]);
 /* msearch_cmd.c: `fermi-amd msearch [-g dev] <query.fa> <a.fmd> [<b.fmd> ...]`: count and SA interval of every query in the merged index of the files, from
  * the files as they are (fmd_multi_bsearch_batch; fm_multi_backward_search exact.c:25-57); usage and unreadable-file errors return 1 before the device is looked for */
 int fmdh_main_msearch(int argc, char *argv[]);
+/* locate_cmd.c: `fermi-amd locate [-g GPU] [-m INT] [-r reads.rank] <reads.fmd> <query.fa>`: the reads that hold every query, strand and offset (fmd_bsearch_batch,
+ * then fmd_locate_batch); usage and unreadable-file errors return 1 before the device is looked for.  fmdh_locate_hits (no GPU): the runs of fmd_locate_* expanded
+ * into hits sorted by (query, id, off), id = sorted[rank] >> 2 with seqsort's map and the rank itself with sorted = NULL; *hits is malloc'ed; 1 when a run
+ * reaches a rank >= n_seq (the map is not read past its end) or memory runs out */
+typedef struct { uint64_t id; uint32_t query, off; } fmdh_locate_hit_t;
+int fmdh_locate_hits(const fmd_locate_run_t *runs, uint64_t n_runs, const uint64_t *sorted, uint64_t n_seq, fmdh_locate_hit_t **hits, uint64_t *n_hits);
+int fmdh_main_locate(int argc, char *argv[]);
 int fmdh_fltuniq_auto_k(long long file_bytes);   /* the k `fltuniq` takes for an input file of that many bytes on disk (seq.c:147-150) */
 
 /* `fermi correct` (cmd.c:253-291, correct.c:305-456); defaults = cmd.c:258 */

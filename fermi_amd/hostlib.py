@@ -81,6 +81,7 @@ def lib():
         L.fmdh_scaf_print_links.restype = None; L.fmdh_scaf_print_links.argtypes = [vp, vp]
         L.fmdh_scaf_free.restype = None; L.fmdh_scaf_free.argtypes = [vp]
         L.fmdh_scaf_cal_rdist.restype = C.c_double; L.fmdh_scaf_cal_rdist.argtypes = [vp]
+        L.fmdh_locate_hits.argtypes = [vp, C.c_uint64, vp, C.c_uint64, C.POINTER(vp), C.POINTER(C.c_uint64)]
         _lib = L
     return _lib
 
@@ -112,6 +113,27 @@ def write_rld_from_bwt(bwt, path):
 def trim_palindrome(seq):
     seq = np.ascontiguousarray(seq, dtype=np.uint8)
     return int(lib().fmdh_trim_palindrome(seq.ctypes.data, len(seq)))
+
+
+LOCATE_RUN_DT = np.dtype([("rank", "<u8"), ("n", "<u4"), ("off", "<u4"), ("query", "<u4"), ("reserved", "<u4")])   # fmd_locate_run_t (include/fmd_hip.h)
+LOCATE_HIT_DT = np.dtype([("id", "<u8"), ("query", "<u4"), ("off", "<u4")])                                       # fmdh_locate_hit_t (fmd_host.h)
+
+
+def locate_hits(runs, n_seq, sorted_map=None):
+    """fmdh_locate_hits: the runs of a locate expanded into hits (LOCATE_HIT_DT) sorted by (query, id, off); id = sorted_map[rank] >> 2 with seqsort's
+    map, the sentinel rank itself without one.  ValueError when a run reaches a rank >= n_seq."""
+    runs = np.ascontiguousarray(runs, dtype=LOCATE_RUN_DT)
+    m = None if sorted_map is None else np.ascontiguousarray(sorted_map, dtype=np.uint64)
+    if m is not None and len(m) < n_seq:
+        raise ValueError("locate_hits: a map of %d entries for %d sequences" % (len(m), n_seq))
+    p, n = C.c_void_p(), C.c_uint64()
+    if lib().fmdh_locate_hits(runs.ctypes.data, len(runs), None if m is None else m.ctypes.data, n_seq, C.byref(p), C.byref(n)) != 0:
+        raise ValueError("locate_hits: a run reaches beyond the %d sequences" % n_seq)
+    hits = np.zeros(n.value, dtype=LOCATE_HIT_DT)
+    if n.value:
+        C.memmove(hits.ctypes.data, p.value, n.value * LOCATE_HIT_DT.itemsize)
+    _libc.free(p)
+    return hits
 
 
 _libc = C.CDLL(None)

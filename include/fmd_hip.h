@@ -132,6 +132,28 @@ int fmd_retrieve_dev(fmd_dev_t *h, void *stream, size_t n, const uint64_t *d_x, 
 int fmd_retrieve_batch(fmd_dev_t *h, size_t n, const uint64_t *x, uint8_t *seqs, uint32_t stride,
                        uint32_t *len, uint64_t *rank);
 
+/* ---- locate (no reference counterpart: the FMD-index keeps no suffix-array samples) ------------------
+ * Which sequences hold the rows [beg[i], beg[i] + cnt[i]) -- the SA interval of a search -- and at which offset: the LF-walk of a row ends at
+ * its sequence's '$' after `off` steps, on the sentinel rank fm_retrieve returns (the index into seqsort's map), and the rows of an interval are
+ * walked TOGETHER, as intervals that split by the preceding symbol, one level per base.  A run = the sentinel ranks
+ * rank .. rank + n - 1 of query `query`, all at offset `off` (0-based, in the strand's sequence as indexed); runs come in no particular order from
+ * the _dev form and sorted by (query, off, rank) from the _batch form.  cnt[i] = 0 gives nothing; an interval with cnt[i] > max_occ, or one that does
+ * not lie inside the index, is left out whole and counted in n_skipped.
+ * stat: n_runs = runs stored, n_rows = the rows in them, n_unfinished = rows still walking after the last level, n_ext = backward extensions done,
+ * overflow = 1 when a run did not fit run_cap or an item did not fit the work area (nothing is written past either; the result is incomplete).
+ * The _dev form enqueues exactly `levels` levels on `stream` and returns: it neither allocates nor synchronises.  total_rows = the sum of the
+ * cnt[i] <= max_occ; that many runs always suffice for run_cap; the work area is 16-byte aligned.  FMD_E_ARG: a null pointer with n > 0, a work
+ * area smaller than fmd_locate_work_bytes(n, 0) -- one sized for fewer rows than there are sets `overflow` --, n >= 2^32.  n = 0 is a no-op.
+ * The _batch form sizes everything from the counts, runs levels in groups of at most 64 until the frontier is empty (max_len = 0) or max_len levels
+ * are done, and returns FMD_E_OVERFLOW if the flag is set.  Handles opened with FMD_OPEN_NO_TABLES work; two-base blocks are not used. */
+typedef struct { uint64_t rank; uint32_t n, off, query, reserved; } fmd_locate_run_t;   /* ranks rank .. rank+n-1, all at offset off */
+typedef struct { uint64_t n_runs, n_rows, n_skipped, n_unfinished, overflow, n_ext; } fmd_locate_stat_t;
+size_t fmd_locate_work_bytes(size_t n, uint64_t total_rows);
+int fmd_locate_dev(fmd_dev_t *h, void *stream, size_t n, const uint64_t *d_beg, const uint64_t *d_cnt, uint32_t max_occ, uint32_t levels,
+                   fmd_locate_run_t *d_runs, uint64_t run_cap, fmd_locate_stat_t *d_stat, void *d_work, size_t work_bytes);
+int fmd_locate_batch(fmd_dev_t *h, size_t n, const uint64_t *beg, const uint64_t *cnt, uint32_t max_occ, uint32_t max_len,
+                     fmd_locate_run_t **runs, uint64_t *n_runs, fmd_locate_stat_t *stat);      /* runs freed with fmd_host_free */
+
 /* ---- inspection (`fermi chkbwt`, cmd.c:47-130) ------------------------------------------------
  * export: BWT[first, first+n) as nt6 bytes, decoded from the device layout (chkbwt -p).
  * check_rank: the device layout's rank of every position against the symbols themselves (chkbwt -r):
