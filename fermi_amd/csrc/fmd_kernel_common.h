@@ -199,6 +199,12 @@ enum FmdClsWord {
     FMD_CW_FAST_LIVE = 11,       // ... live lanes in them,
     FMD_CW_FAST_HELD = 12,       // ... lanes of groups that hold a strand,
     FMD_CW_FAST_ROUNDS2 = 13,    // ... rounds in which some strand saw a second base
+    FMD_CW_LANE_ADM = 21,        // FMD_OVLP_STATS, k_ovl_nei_lane's counting instantiations (six words, in LaneStats' order): strands admitted,
+    FMD_CW_LANE_QUIET = 22,      // ... lane rounds: quiet,
+    FMD_CW_LANE_SELF = 23,       // ... the self-end round inline,
+    FMD_CW_LANE_CLOSE = 24,      // ... the closing round inline,
+    FMD_CW_LANE_FULL = 25,       // ... through the full round code,
+    FMD_CW_LANE_MAT = 26,        // ... of those, with a pending self-end round to apply to the column first
     // the slow list's line
     FMD_CW_LATE = 4,             // entries of the late list (`slow_n` of the fast / group kernels)
     FMD_CW_GRP_ROUNDS = 12,      // GRP_STATS, the group kernels: wave rounds,
@@ -217,7 +223,7 @@ template <int... W> constexpr bool fmd_cw_distinct()
 }
 static_assert(fmd_cw_distinct<FMD_CW_COUNT, FMD_CW_DEAL>(), "a general list's counter line");
 static_assert(fmd_cw_distinct<FMD_CW_COUNT, FMD_CW_DEAL, FMD_CW_DOWN, FMD_CW_DOWN_DEAL, FMD_CW_HANDED, FMD_CW_HANDED_AT0, FMD_CW_FAST_ROUNDS, FMD_CW_FAST_LIVE, FMD_CW_FAST_HELD,
-                              FMD_CW_FAST_ROUNDS2>(), "a fast list's counter line");
+                              FMD_CW_FAST_ROUNDS2, FMD_CW_LANE_ADM, FMD_CW_LANE_QUIET, FMD_CW_LANE_SELF, FMD_CW_LANE_CLOSE, FMD_CW_LANE_FULL, FMD_CW_LANE_MAT>(), "a fast list's counter line");
 static_assert(fmd_cw_distinct<FMD_CW_COUNT, FMD_CW_LATE, FMD_CW_GRP_ROUNDS, FMD_CW_GRP_LIVE, FMD_CW_GRP_HELD, FMD_CW_FIX>(), "the slow list's counter line");
 
 // The lists of one part as pointers (the kernels' form; filled through the functions above).  The late and the fix-up list travel beside it (NeiArgs,

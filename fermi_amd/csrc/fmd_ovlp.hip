@@ -175,6 +175,14 @@ static int ovl_phase_b(const OvlBatch &o, hipStream_t st, size_t b, size_t np, i
         }
         static_assert(FMD_GRP_CLASSES == 6, "one %u per general class");
         fprintf(stderr, "[M::fmd_ovlp] ... of those slots %u %u %u %u %u %u hold a strand (general lists of the group classes, smallest first)\n", ne[0], ne[1], ne[2], ne[3], ne[4], ne[5]);
+        // what the lanes of k_ovl_nei_lane did with them (its counting instantiations run under this switch), all classes together
+        uint32_t ln[6] = {0, 0, 0, 0, 0, 0}, adm64 = 0;
+        for (int k = 0; k < 2 * FMD_GRP_CLASSES; ++k) {
+            for (int i = 0; i < 6; ++i) ln[i] += word(fmd_cls_fast(k), FMD_CW_LANE_ADM + i);
+            if (k >= FMD_GRP_CLASSES) adm64 += word(fmd_cls_fast(k), FMD_CW_LANE_ADM);
+        }
+        fprintf(stderr, "[M::fmd_ovlp] ... one lane per strand: %u strands admitted (%u with 64-bit masks), lane rounds: %u quiet, %u self-end inline, %u closing past the loops, %u through the loops of the full round (%u of them applied a pending self-end round first)\n",
+                ln[0], adm64, ln[1], ln[2], ln[3], ln[4], ln[5]);
     }
 #ifdef GRP_STATS
     {

@@ -14,6 +14,15 @@
 // words in registers beside the round's state instead of 128-168); the class of 32 keeps the group form.  Same results by
 // construction: the arithmetic of a round is k_ovl_nei_fast's, statement by statement; a strand that leaves the simple regime is handed to
 // k_ovl_nei_grp in the same FMD_LIST_RESUME form.  FMD_NEI_LANE=0 runs the group form instead (the A/B switch, and the tests' second opinion).
+//
+// An error-free strand of equal-length reads meets the full round code twice, and both visits are simple (fm6_get_nei, unitig.c:93-155).  Round 0, the
+// SELF-END round: the strand itself (and its copies) lies in the window and ends there; nothing can be a neighbour yet, every candidate only loses those
+// rows.  Where they are no more than the rows in front of every candidate's first '$' (dmin, from the admission's decode) the lane does the round as it
+// does a quiet one and leaves the column alone: the ends stay pending (E0) and a candidate is read through lane_self_end until a full round applies it.
+// The CLOSING round: the read of candidate 0 ends, it is the first neighbour and masks the rest; the pass through the full round code takes such a lane
+// past the loops (and past applying E0).  It stays in the pass: done in the lane's own step -- the neighbour, the bases, the record for a dozen lanes
+// every step instead of thirty-two every third -- it cost 9.6 ms per 10^8 strands where this form gains (profiles/nei_inline).  FMD_LANE_INLINE=0 / 1 / 2:
+// neither / the self-end round alone / the closing round alone (the A/B switch); under FMD_OVLP_STATS the counting instantiations run (LaneStats).
 #include "fmd_ovlp_internal.h"
 
 #define LANE_CHUNK FMD_LANE_CHUNK          // list slots a wave reserves at a time for the strands it hands on (64: every lane may hand on in one step)
@@ -60,12 +69,28 @@ __device__ __forceinline__ void lane_flush_bases(uint8_t *seq_out, uint32_t seq_
 #define FMD_LANE_LB 2                       // (LDS decides the residency: G + 4 KiB per wave)
 #endif
 
-template <int G, typename M>
+// The self-end round (round 0) on ONE candidate, when every row of the window that ends there (E0) lies in front of the candidate's first '$' and the strand
+// goes on with one base: the candidate loses its nS0 ending rows -- the first ones of its range in x[0] order, none of them a '$' of D: r0 stays -- and
+// moves up by the ending rows before it.  What the full round's rewrite gives for such a round, statement by statement; E0 = 0 changes nothing.
+template <typename M>
+__device__ __forceinline__ void lane_self_end(M E0, M &D, uint32_t &w)
+{
+    using W = LaneW<M>;
+    const uint32_t d = LC_D(w), sz = LC_SZ(w);
+    const uint32_t nS0 = W::popc(E0 & (W::below(sz) << d));
+    D >>= nS0;
+    w = (w & 0xfff000ffu) | (d - W::popc(E0 & W::below(d))) << 8 | (sz - nS0) << 14;
+}
+
+// What the lanes of a launch did, for FMD_OVLP_STATS (the STATS instantiations; the shipped ones hold none of it): words of the fast list's counter line.
+struct LaneStats { uint32_t adm, quiet, self_end, closing, full, mat; };
+
+template <int G, typename M, bool STATS>
 __global__ __launch_bounds__(64, FMD_LANE_LB) void k_ovl_nei_lane(FmdIndexView ix, const uint32_t *__restrict__ list, const uint32_t *__restrict__ list_n,
                                                                 uint32_t cap, const fmd_intv_t *__restrict__ listA, fmd_intv_t *__restrict__ listB, fmd_ovlp_rec_t *__restrict__ rec,
                                                                 fmd_intv_t *__restrict__ nei_out, uint32_t max_nei, uint8_t *__restrict__ seq_out, uint32_t seq_stride,
                                                                 uint32_t *__restrict__ gen_list, uint32_t *__restrict__ gen_n, uint32_t *__restrict__ bail_n,
-                                                                const uint32_t *__restrict__ gidx, uint32_t *__restrict__ queue, uint32_t tk_chunk, uint32_t slow_min, uint32_t adm_min)
+                                                                const uint32_t *__restrict__ gidx, uint32_t *__restrict__ queue, uint32_t tk_chunk, uint32_t slow_min, uint32_t adm_min, uint32_t inl)
 {
     using W = LaneW<M>;
     constexpr bool WIDE = sizeof(M) == 8;
@@ -97,6 +122,10 @@ __global__ __launch_bounds__(64, FMD_LANE_LB) void k_ovl_nei_lane(FmdIndexView i
     bool adm_bad = false;
     constexpr int HALVES = G > 8 ? 2 : 1, RAWN = (G + HALVES - 1) / HALVES;
     bool drained = false;
+    // for the two inline rounds below: dmin = the fewest rows any candidate has in front of its first '$' (0 when a D is empty or reaches beyond its size), and
+    uint32_t dmin = 0;
+    M E0 = 0;                                              // != 0: the self-end round of these `ends` is done for the window but not yet for the column (lane_self_end)
+    LaneStats stats = {0, 0, 0, 0, 0, 0};
 
     for (;;) {
         {   // ---- hand-overs of the previous step / of the admission below
@@ -200,9 +229,16 @@ __global__ __launch_bounds__(64, FMD_LANE_LB) void k_ovl_nei_lane(FmdIndexView i
             if (__ballot(mixed)) { if (mixed) fmd_block_rank6<false>(img_k, t_k, oke + 1, R, bke); }
             if (!mixed) { uint64_t rz; const uint64_t rc = fmd_block_rank1z(img_k, t_k, oke + 1, cs, bke, rz); R[0] = rz; R[1] = R[2] = R[3] = R[4] = rc; }
             if (go) {
-                if (!mixed && ends == 0) {
+                // the SELF-END round, inline -- round 0, one base, and the rows that end here (the strand itself and its copies) are no more than dmin: for
+                // every candidate j they are nS_j <= popc(ends) <= ctz(D_j) < size_j rows in front of its first '$', so D_j & below(nS_j) == 0 (r0 stays),
+                // (D_j >> nS_j) & below(size_j - nS_j) != 0 (a child: every candidate is kept, the widest -- offset 0 -- stays the origin, lfork = 1), and
+                // nothing is a neighbour in round 0.  The window moves as in the quiet round; the column is left as it is, with E0 pending on it.
+                const bool self_end = (inl & 1u) && !mixed && ends != 0 && round == 0 && W::popc(ends) <= dmin;
+                if ((!mixed && ends == 0) || self_end) {
                     // the QUIET round -- no read of the window ends, all go on with one base: nothing ends, nothing is a neighbour, every candidate keeps
                     // its size, its offset in the window, its D (alive => D != 0: a read starts with it) and r0; the window moves by one LF step.
+                    if (STATS) { if (self_end) ++stats.self_end; else ++stats.quiet; }
+                    if (self_end) { E0 = ends; szw -= W::popc(ends); }
                     if (!(lf & 0x10000u)) lf = round + 1;
                     eb |= (uint64_t)(uint32_t)(4 - cs) << (2 * (round - eb0));
                     ++round;
@@ -217,6 +253,35 @@ __global__ __launch_bounds__(64, FMD_LANE_LB) void k_ovl_nei_lane(FmdIndexView i
             const uint64_t sm = __ballot(slow);
             if (sm && ((uint32_t)__popcll(sm) >= slow_min || __ballot(active && !slow) == 0)) {
                 if (slow) {
+                    // the CLOSING round without the loops -- a round past 0 with one base in which the read of candidate 0 ends (every row of it, and each starts a
+                    // read): it is the first neighbour, which masks every other candidate (f = 0, keep_m = 0), and the strand closes.  Of the others the loops
+                    // would only find out whether any has a child (lfork): the widest one alive (the last; offset 0, size szw) shows one, or lfork is final
+                    // already.  Both entries are read through the pending self-end round, which is then never applied to the column.  (In the pass, not in
+                    // the lane's own step: the close -- the neighbour, the bases, the record -- costs the wave the same for one lane as for thirty-two.)
+                    bool simple = false;
+                    if ((inl & 2u) && scs < 8 && round > 0 && (am & 1u) && n_nei < max_nei) {
+                        const M mw = W::below(szw), any = (sX | sY | sZ) & mw, ends = ~(sX | sY | sZ) & mw;
+                        const uint4 e0 = mc[0], ew = mc[(31 - __clz((int)am)) * 64];
+                        M D0 = CD(e0);
+                        uint32_t w0 = e0.w;
+                        lane_self_end<M>(E0, D0, w0);
+                        const uint32_t sz0 = LC_SZ(w0), na = W::popc(any);
+                        simple = W::popc(ends & (W::below(sz0) << LC_D(w0))) == sz0 && D0 == W::below(sz0) &&
+                                 ((lf & 0x10000u) || (((CD(ew) >> W::popc(E0)) >> (szw - na)) & W::below(na)) != 0);
+                    }
+                    if (STATS) { if (simple) ++stats.closing; else ++stats.full; }
+                    if (E0 != 0 && !simple) {   // the self-end round is still pending on the column: the loops below (and a hand-over) read the candidates as that round leaves them
+                        if (STATS) ++stats.mat;
+                        for (uint32_t j = 0; j < m_lane; ++j)
+                            if ((am >> j) & 1u) {
+                                const uint4 e = mc[j * 64];
+                                M D = CD(e);
+                                uint32_t w = e.w;
+                                lane_self_end<M>(E0, D, w);
+                                mc[j * 64] = make_uint4((uint32_t)D, WIDE ? (uint32_t)((uint64_t)D >> 32) : 0u, e.z, w);
+                            }
+                        E0 = 0;
+                    }
                     const M X = sX, Y = sY, Z = sZ;
                     int cs = scs & 7;
                     const bool mixed = (scs & 8) != 0;
@@ -253,8 +318,9 @@ __global__ __launch_bounds__(64, FMD_LANE_LB) void k_ovl_nei_lane(FmdIndexView i
                     if (bail) { hand = 2; active = false; lane_flush_bases(seq_out, seq_stride, gs, ori_l, eb0, round, eb); }   // (the candidates stay as they are until the hand-over at the top of the next step)
                     else {
                     // ---- every candidate of the strand: is it a neighbour (unitig.c:111-122), does a read that starts with it go on (unitig.c:129)?
-                    uint32_t nei_m = 0, child_m = 0;
-                    for (uint32_t j = 0; j < m_lane; ++j) {
+                    uint32_t nei_m = simple ? 1u : 0u, child_m = nei_m;        // (the closing round without the loops: child_m != 0 where lfork asks, masked by f = 0)
+                    const uint32_t m_loop = simple ? 0u : m_lane;
+                    for (uint32_t j = 0; j < m_loop; ++j) {
                         if ((am >> j) & 1u) {
                             const uint4 e = mc[j * 64];
                             const uint32_t d = LC_D(e.w), sz = LC_SZ(e.w);
@@ -275,7 +341,8 @@ __global__ __launch_bounds__(64, FMD_LANE_LB) void k_ovl_nei_lane(FmdIndexView i
                     const int f = nei_m ? __ffs((int)nei_m) - 1 : 32;           // the first neighbour masks the rest of the (only) category
                     const uint32_t keep_m = f >= 32 ? child_m : child_m & ((1u << f) - 1u);
                     if (nei_m) {
-                        const uint4 e = mc[f * 64];
+                        uint4 e = mc[f * 64];
+                        if (E0 != 0) { M D = CD(e); lane_self_end<M>(E0, D, e.w); }   // (the closing round without the loops: the column may still be the admission's)
                         const uint32_t d = LC_D(e.w), sz = LC_SZ(e.w), pos = LC_POS(e.w);
                         if (n_nei == 0) nei0 = ori_l - pos;                       // info of nei[0] decides rbeg (unitig.c:157)
                         if (n_nei < max_nei)
@@ -321,7 +388,7 @@ __global__ __launch_bounds__(64, FMD_LANE_LB) void k_ovl_nei_lane(FmdIndexView i
                         o->rbeg = n_nei ? (int)(ori_l - nei0) : -1;
                         o->ext_len = n_nei > 1 ? 0 : (int)round;
                         o->n_nei = (int32_t)n_nei;
-                        active = false; am = 0;
+                        active = false; am = 0; E0 = 0;
                     }
                     }
                 }
@@ -332,7 +399,7 @@ __global__ __launch_bounds__(64, FMD_LANE_LB) void k_ovl_nei_lane(FmdIndexView i
             const uint32_t m = adm_m, ori_l = meta >> 16;
             if (st == 2) {
                 gs = g_in;
-                round = 0; n_nei = 0; lf = 0; nei0 = 0; am = 0; eb = 0; eb0 = 0;
+                round = 0; n_nei = 0; lf = 0; nei0 = 0; am = 0; eb = 0; eb0 = 0; E0 = 0; dmin = 63;
                 adm_bad = m == 0 || m > (uint32_t)G || ori_l > LANE_MAX_LEN;
                 uint64_t x1w = 1; uint32_t szw_ = 1;
 #pragma unroll
@@ -350,17 +417,25 @@ __global__ __launch_bounds__(64, FMD_LANE_LB) void k_ovl_nei_lane(FmdIndexView i
                     adm_bad |= !cd.narrow || cd.x1 < X1 || d + cd.sz > szw || cd.sz == 0 || cd.depth > ori_l;
                     mc[j * 64] = make_uint4((uint32_t)cd.D, (uint32_t)(cd.D >> 32), (uint32_t)cd.r0, LC_PACK(cd.r0, d & 63u, cd.sz & 63u, (ori_l - cd.depth) & 0xfffu));
                     am |= 1u << j;
+                    const uint32_t lead = cd.D != 0 && (cd.D >> cd.sz) == 0 ? (uint32_t)__ffsll((long long)cd.D) - 1u : 0u;   // (size <= 63)
+                    dmin = lead < dmin ? lead : dmin;
                 }
             if (st == 2 && adm_h0 != 0 && !adm_bad) st = 3;        // the other half in the next admission pass
             else {
                 if (adm_bad) { hand = 1; am = 0; }     // (sid and meta stay until the hand-over at the top of the next step)
-                else active = true;
+                else { active = true; if (STATS) ++stats.adm; }
                 st = 0;
             }
         }
         if (ld1) { sid = l0; meta = l1; st = 2; }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // the images are read before the next gather lands in the slots
         if (__ballot(active || st != 0 || hand != 0 || !drained) == 0) { if (lane == 0 && n_handed) atomicAdd(bail_n, n_handed); break; }
+    }
+    if (STATS) {
+        uint32_t *c = bail_n + (FMD_CW_LANE_ADM - FMD_CW_HANDED);
+        const uint32_t v[6] = {stats.adm, stats.quiet, stats.self_end, stats.closing, stats.full, stats.mat};
+#pragma unroll
+        for (int i = 0; i < 6; ++i) if (v[i]) atomicAdd(c + i, v[i]);
     }
 }
 
@@ -387,16 +462,20 @@ void fmd_launch_nei_lane(const NeiArgs &a, int cls, int wide, int per_cu_cap, hi
     const uint32_t slow_min = es && atoi(es) >= 1 ? (uint32_t)atoi(es) : 32u;
     const char *ea = getenv("FMD_LANE_ADM_GATE");                   // lanes that must wait for the candidates' decode of an admission (1 = never held back: the form every number up to round 5 was taken with)
     const uint32_t adm_min = ea && atoi(ea) >= 1 ? (uint32_t)atoi(ea) : 1u;
-#define LANE_LAUNCH_(K, MM) do { \
+    const char *ei = getenv("FMD_LANE_INLINE");                     // A/B switch: 0 = the self-end and the closing round go through the full round code like every other
+    const uint32_t inl = ei ? (uint32_t)atoi(ei) & 3u : 3u;          // (1 / 2: the self-end / the closing round alone)
+    const bool stats = getenv("FMD_OVLP_STATS") != nullptr;         // the counting instantiations (what a launch counts: LaneStats)
+#define LANE_LAUNCH_(K, MM) do { if (stats) LANE_LAUNCH__(K, MM, true); else LANE_LAUNCH__(K, MM, false); } while (0)
+#define LANE_LAUNCH__(K, MM, ST) do { \
         static int cached = 0; \
-        if (!cached) cached = lane_blocks_per_cu((const void *)k_ovl_nei_lane<fmd_grp_size(K), MM>, sizeof(uint4) * ((sizeof(MM) == 8 ? FMD_WAVE_LDS_U4 : FMD_SLOT_U4) + 64 * fmd_grp_size(K))); \
+        if (!cached) cached = lane_blocks_per_cu((const void *)k_ovl_nei_lane<fmd_grp_size(K), MM, ST>, sizeof(uint4) * ((sizeof(MM) == 8 ? FMD_WAVE_LDS_U4 : FMD_SLOT_U4) + 64 * fmd_grp_size(K))); \
         int per = cached; \
         if (per_cu_cap > 0 && per_cu_cap < per) per = per_cu_cap; \
         if (e && atoi(e) > 0 && atoi(e) < per) per = atoi(e); \
         int grid = a.n_cu * per; \
         if (grid > FMD_FAST_MAX_WAVES) grid = FMD_FAST_MAX_WAVES; \
-        k_ovl_nei_lane<fmd_grp_size(K), MM><<<grid, 64, 0, st>>>(a.ix, a.cl.fast[fk], a.cnt(fl), a.cap, a.listA, a.listB, a.rec, a.nei, a.max_nei, a.seq, a.seq_stride, \
-                                                                 a.cl.lst[cls], a.cnt(cls), a.cnt(fl, FMD_CW_HANDED), a.gidx, queue, tk_chunk, slow_min, adm_min); \
+        k_ovl_nei_lane<fmd_grp_size(K), MM, ST><<<grid, 64, 0, st>>>(a.ix, a.cl.fast[fk], a.cnt(fl), a.cap, a.listA, a.listB, a.rec, a.nei, a.max_nei, a.seq, a.seq_stride, \
+                                                                 a.cl.lst[cls], a.cnt(cls), a.cnt(fl, FMD_CW_HANDED), a.gidx, queue, tk_chunk, slow_min, adm_min, inl); \
     } while (0)
 #define LANE_LAUNCH2(K) do { if (wide) LANE_LAUNCH_(K, uint64_t); else LANE_LAUNCH_(K, uint32_t); } while (0)
     switch (cls) {
@@ -407,5 +486,6 @@ void fmd_launch_nei_lane(const NeiArgs &a, int cls, int wide, int per_cu_cap, hi
     default: LANE_LAUNCH2(4); break;
     }
 #undef LANE_LAUNCH2
+#undef LANE_LAUNCH__
 #undef LANE_LAUNCH_
 }
