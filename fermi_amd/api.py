@@ -19,6 +19,9 @@ OVLP_DT = np.dtype([("rank", "<u8"), ("k", "<u8", 3), ("len", "<i4"), ("status",
 OVLP_F_FORKED, OVLP_F_OVERFLOW, OVLP_F_FIXED = 1, 2, 4
 LOCATE_RUN_DT = np.dtype([("rank", "<u8"), ("n", "<u4"), ("off", "<u4"), ("query", "<u4"), ("reserved", "<u4")])  # fmd_locate_run_t
 LOCATE_STAT_DT = np.dtype([(f, "<u8") for f in ("n_runs", "n_rows", "n_skipped", "n_unfinished", "overflow", "n_ext")])  # fmd_locate_stat_t
+KCOUNT_STAT_DT = np.dtype([(f, "<u8") for f in ("n_kmers", "n_total", "n_ext", "overflow", "widest_level", "n_parts", "n_retries")])  # fmd_kcount_stat_t
+KCOUNT_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32))  # fmd_kcount_sink_fn
+KCOUNT_MIN_CAP, KCOUNT_MAX_CAP = 4096, 1 << 30   # FMD_KCOUNT_MIN_CAP, FMD_KCOUNT_MAX_CAP
 
 # every symbol include/fmd_hip.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
@@ -48,6 +51,7 @@ ABI_SYMBOLS = [
     "fmd_scaf_links_work_bytes", "fmd_scaf_links_dev", "fmd_scaf_links",
     "fmd_multi_bsearch_work_bytes", "fmd_multi_bsearch_dev", "fmd_multi_bsearch_batch",
     "fmd_locate_work_bytes", "fmd_locate_dev", "fmd_locate_batch",
+    "fmd_kcount_work_bytes", "fmd_kcount_part_dev", "fmd_kcount",
 ]
 
 
@@ -130,6 +134,9 @@ def _configure(L):
     L.fmd_locate_work_bytes.restype = sz; L.fmd_locate_work_bytes.argtypes = [sz, C.c_uint64]
     L.fmd_locate_dev.argtypes = [vp, vp, sz, u64p, u64p, C.c_uint32, C.c_uint32, vp, C.c_uint64, vp, vp, sz]
     L.fmd_locate_batch.argtypes = [vp, sz, u64p, u64p, C.c_uint32, C.c_uint32, C.POINTER(vp), C.POINTER(C.c_uint64), vp]
+    L.fmd_kcount_work_bytes.restype = sz; L.fmd_kcount_work_bytes.argtypes = [C.c_uint64]
+    L.fmd_kcount_part_dev.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, sz, vp, C.c_uint64, C.c_uint32, u64p, u64p, vp, C.c_uint64, vp, vp, sz]
+    L.fmd_kcount.argtypes = [vp, C.c_int, C.c_int, C.c_uint32, u64p, C.c_uint64, vp, vp, vp]
     L.fmd_retrieve_batch.argtypes = [vp, sz, u64p, vp, C.c_uint32, vp, u64p]
     L.fmd_build_bwt.argtypes = [C.c_int, sz, vp, u64p, vp, C.POINTER(C.c_uint64)]
     L.fmd_build_bwt_dev.argtypes = [C.c_int, vp, sz, vp, u64p, C.c_uint64, C.c_uint32, C.c_int, C.POINTER(vp), C.POINTER(C.c_uint64)]
@@ -446,6 +453,37 @@ class DevIndex:
         hit_off = np.zeros(n + 1, dtype=np.int64)
         np.cumsum(np.bincount(q, minlength=n), out=hit_off[1:])
         return cnt, located, hit_off, ids[order], pos[order]
+
+    def _kcount(self, k, min_occ, n_bins, cap, sink):
+        hist = np.zeros(max(int(n_bins), 0), dtype=np.uint64)
+        stat = np.zeros(1, dtype=KCOUNT_STAT_DT)
+        cb = KCOUNT_SINK(sink) if sink is not None else None
+        check(lib().fmd_kcount(self.h, int(k), int(min_occ), int(n_bins), _ptr(hist) if len(hist) else None, int(cap),
+                               C.cast(cb, C.c_void_p) if cb is not None else None, None, _ptr(stat)))
+        return hist, {f: int(stat[0][f]) for f in KCOUNT_STAT_DT.names}
+
+    def kmer_spectrum(self, k, min_occ=1, n_bins=1024, cap=0):
+        """fmd_kcount without a sink: (hist, stat).  hist[i] = the canonical k-mers (1 <= k <= 32) with count i, hist[n_bins - 1] = those with
+        count >= n_bins - 1, hist[0] = 0; only k-mers with count >= min_occ are in it.  stat: the fields of KCOUNT_STAT_DT (n_kmers, n_total,
+        n_ext, widest_level, n_parts, n_retries, ..).  cap: the frontier capacity of a part in entries (KCOUNT_MIN_CAP ..; 0 = sized from
+        the index and the free device memory); the result does not depend on it.  An index of one strand only raises FmdError."""
+        return self._kcount(k, min_occ, n_bins, cap, None)
+
+    def kmer_counts(self, k, min_occ=1, cap=0, slices=None):
+        """fmd_kcount with a sink: (kmers uint64[], counts uint32[], stat), the canonical k-mers with count >= min_occ, ascending.  A k-mer is
+        packed 2 bits per base (A=0 C=1 G=2 T=3), the first base in the highest of the low 2k bits; a count saturates at 2^32 - 1.  slices:
+        a list that receives the length of every slice the sink was handed."""
+        ks, cs = [], []
+
+        def sink(ctx, n, kmer, count):
+            ks.append(np.ctypeslib.as_array(kmer, (n,)).astype(np.uint64, copy=True))
+            cs.append(np.ctypeslib.as_array(count, (n,)).astype(np.uint32, copy=True))
+            if slices is not None:
+                slices.append(int(n))
+            return 0
+
+        _, stat = self._kcount(k, min_occ, 2, cap, sink)
+        return (np.concatenate(ks) if ks else np.zeros(0, np.uint64)), (np.concatenate(cs) if cs else np.zeros(0, np.uint32)), stat
 
 
 FMD_MULTI_MAX = 16   # include/fmd_hip.h

@@ -27,65 +27,14 @@
 #define KM_EXT 68      // backward extensions done (= trie nodes expanded), all levels
 #define KM_WORDS 72
 
-// one trie level: nodes at depth d -> children at depth d+1
+// one trie level: nodes at depth d -> children at depth d+1 (km_level_step, fmd_level.h)
 __global__ __launch_bounds__(64) void k_kmer_level(FmdIndexView ix, int d, int suf_len, int min_occ, const fmd_intv_t *__restrict__ in,
                                                    fmd_intv_t *__restrict__ out, uint64_t cap, uint32_t ch, unsigned long long *__restrict__ ctr,
                                                    int xcd_aware)
 {
     FMD_DECLARE_COMPACT_LDS();
-    const int lane = fmd_lane();
-    const uint64_t n = ctr[d] < cap ? ctr[d] : cap;   // an overflowing level counted more than it stored
     const uint64_t thr = (d + 1 <= suf_len) ? 1 : (uint64_t)min_occ; // exact.c:159 vs correct.c:78
-    const KmRange rg = km_range(n, xcd_aware);
-    const uint64_t stride = rg.stride;
-    KmChunk ck; ck.base = 0; ck.fill = 0; ck.ch = ch; ck.have = false;
-    uint32_t n_ext = 0;
-    uint4 na = make_uint4(0, 0, 0, 0), nb = na;       // the entry of the next iteration, loaded one gather ahead
-    {
-        const uint64_t i0 = rg.beg + lane;
-        if (i0 < rg.end) { const uint4 *q = (const uint4 *)(in + i0); na = q[0]; nb = q[1]; }
-    }
-    for (uint64_t base = rg.beg; base < rg.end; base += stride) {
-        const uint4 a = na, b = nb;
-        const uint64_t x0 = (uint64_t)a.y << 32 | a.x, x1 = (uint64_t)a.w << 32 | a.z;
-        const uint64_t sz = (uint64_t)b.y << 32 | b.x, K = (uint64_t)b.w << 32 | b.z;
-        const bool act = base + lane < rg.end && sz != 0;
-        {
-            const uint64_t i1 = base + stride + lane;
-            na = make_uint4(0, 0, 0, 0); nb = na;
-            if (i1 < rg.end) { const uint4 *q = (const uint4 *)(in + i1); na = q[0]; nb = q[1]; }
-        }
-        const uint64_t m_act = __ballot(act);
-        if (m_act == 0) continue;                     // a run of holes
-        n_ext += (uint32_t)__popcll(m_act);
-        uint64_t tk[6], s[6];
-        km_extend_back<true>(ix, fmd_lds, act, x0, sz, thr, tk, s);
-        // children c = 1..4 (ambiguous bases are skipped, correct.c:77); x[1] = running sum in
-        // the order $,T,G,C,A (exact.c:81-86)
-        const bool has1 = act && s[1] >= thr, has2 = act && s[2] >= thr, has3 = act && s[3] >= thr, has4 = act && s[4] >= thr;
-        const uint64_t m1 = __ballot(has1), m2 = __ballot(has2), m3 = __ballot(has3), m4 = __ballot(has4);
-        const uint32_t tot = (uint32_t)(__popcll(m1) + __popcll(m2) + __popcll(m3) + __popcll(m4));
-        if (tot == 0) continue;
-        const unsigned long long first = km_reserve(out, cap, ck, tot, &ctr[d + 1]);
-        uint64_t o1 = first + fmd_below(m1);
-        uint64_t o2 = first + __popcll(m1) + fmd_below(m2);
-        uint64_t o3 = first + __popcll(m1) + __popcll(m2) + fmd_below(m3);
-        uint64_t o4 = first + __popcll(m1) + __popcll(m2) + __popcll(m3) + fmd_below(m4);
-        const uint64_t x1_4 = x1 + s[0], x1_3 = x1_4 + s[4], x1_2 = x1_3 + s[3], x1_1 = x1_2 + s[2];
-#define KM_PUSH(c, has, o, x1c)                                                                   \
-        if (has) {                                                                                \
-            if (o < cap) {                                                                        \
-                const uint64_t nx0 = ix.cnt[c] + tk[c], nk = K | (uint64_t)(c - 1) << (2 * d);    \
-                uint4 *q = (uint4 *)(out + o);                                                    \
-                q[0] = make_uint4((uint32_t)nx0, (uint32_t)(nx0 >> 32), (uint32_t)(x1c), (uint32_t)((x1c) >> 32)); \
-                q[1] = make_uint4((uint32_t)s[c], (uint32_t)(s[c] >> 32), (uint32_t)nk, (uint32_t)(nk >> 32));     \
-            } else ctr[KM_OVF] = 1;                                                               \
-        }
-        KM_PUSH(1, has1, o1, x1_1) KM_PUSH(2, has2, o2, x1_2) KM_PUSH(3, has3, o3, x1_3) KM_PUSH(4, has4, o4, x1_4)
-#undef KM_PUSH
-    }
-    km_zero_fill(out, cap, ck);
-    if (lane == 0 && n_ext) atomicAdd(&ctr[KM_EXT], (unsigned long long)n_ext);
+    km_level_step(ix, fmd_lds, d, thr, in, out, cap, ch, ctr, KM_OVF, KM_EXT, xcd_aware);
 }
 
 // nodes at depth w: pick the most frequent next base and emit (bucket, key, val), correct.c:56-75.

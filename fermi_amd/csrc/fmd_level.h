@@ -1,5 +1,6 @@
-// fmd_level.h -- what the level-by-level trie walks share (the k-mer harvest, fmd_kmer.hip; locate, fmd_locate.hip): one backward
-// extension per lane on the wave engine, output slots reserved per wave in chunks, the frontier cut into one range per XCD.
+// fmd_level.h -- what the level-by-level trie walks share (the k-mer harvest, fmd_kmer.hip; kcount, fmd_kcount.hip; locate, fmd_locate.hip): one
+// backward extension per lane on the wave engine, output slots reserved per wave in chunks, the frontier cut into one range per XCD, the level step of the
+// two k-mer walks.
 // A frontier entry is a multiple of 16 bytes whose all-zero image is a hole (size 0) that the next level skips.
 #pragma once
 #include "fmd_kernel_common.h"
@@ -123,4 +124,74 @@ __device__ __forceinline__ KmRange km_range(uint64_t n, int xcd_aware)
         r.stride = (uint64_t)per * 64;
     } else { r.beg = (uint64_t)blockIdx.x * 64; r.end = n; r.stride = (uint64_t)gridDim.x * 64; }
     return r;
+}
+
+// the sum of v over the wave, in every lane
+__device__ __forceinline__ uint64_t km_wave_sum(uint64_t v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += (uint64_t)__shfl_xor((unsigned long long)v, o);
+    return v;
+}
+
+// One level of a k-mer trie walk (the harvest, fmd_kmer.hip; kcount, fmd_kcount.hip): the nodes of `in` at depth d -- bi-intervals whose info
+// word K holds the d bases, the rightmost in the lowest two bits -- get one backward extension each, and the children A/C/G/T with at least thr
+// occurrences go to `out` with the new base at bits 2d of K.  Counters, words of ctr: [d] = the entries of `in` (more than cap when that level
+// overflowed: the first cap are there), [d + 1] = the chunk counter of `out`, [i_ovf] is set when a child did not fit cap, [i_ext] counts the extensions.
+__device__ __forceinline__ void km_level_step(const FmdIndexView &ix, uint4 *fmd_lds, int d, uint64_t thr, const fmd_intv_t *__restrict__ in,
+                                              fmd_intv_t *__restrict__ out, uint64_t cap, uint32_t ch, unsigned long long *__restrict__ ctr, int i_ovf,
+                                              int i_ext, int xcd_aware)
+{
+    const int lane = fmd_lane();
+    const uint64_t n = ctr[d] < cap ? ctr[d] : cap;   // an overflowing level counted more than it stored
+    const KmRange rg = km_range(n, xcd_aware);
+    const uint64_t stride = rg.stride;
+    KmChunk ck; ck.base = 0; ck.fill = 0; ck.ch = ch; ck.have = false;
+    uint32_t n_ext = 0;
+    uint4 na = make_uint4(0, 0, 0, 0), nb = na;       // the entry of the next iteration, loaded one gather ahead
+    {
+        const uint64_t i0 = rg.beg + lane;
+        if (i0 < rg.end) { const uint4 *q = (const uint4 *)(in + i0); na = q[0]; nb = q[1]; }
+    }
+    for (uint64_t base = rg.beg; base < rg.end; base += stride) {
+        const uint4 a = na, b = nb;
+        const uint64_t x0 = (uint64_t)a.y << 32 | a.x, x1 = (uint64_t)a.w << 32 | a.z;
+        const uint64_t sz = (uint64_t)b.y << 32 | b.x, K = (uint64_t)b.w << 32 | b.z;
+        const bool act = base + lane < rg.end && sz != 0;
+        {
+            const uint64_t i1 = base + stride + lane;
+            na = make_uint4(0, 0, 0, 0); nb = na;
+            if (i1 < rg.end) { const uint4 *q = (const uint4 *)(in + i1); na = q[0]; nb = q[1]; }
+        }
+        const uint64_t m_act = __ballot(act);
+        if (m_act == 0) continue;                     // a run of holes
+        n_ext += (uint32_t)__popcll(m_act);
+        uint64_t tk[6], s[6];
+        km_extend_back<true>(ix, fmd_lds, act, x0, sz, thr, tk, s);
+        // children c = 1..4 (ambiguous bases are skipped, correct.c:77); x[1] = running sum in
+        // the order $,T,G,C,A (exact.c:81-86)
+        const bool has1 = act && s[1] >= thr, has2 = act && s[2] >= thr, has3 = act && s[3] >= thr, has4 = act && s[4] >= thr;
+        const uint64_t m1 = __ballot(has1), m2 = __ballot(has2), m3 = __ballot(has3), m4 = __ballot(has4);
+        const uint32_t tot = (uint32_t)(__popcll(m1) + __popcll(m2) + __popcll(m3) + __popcll(m4));
+        if (tot == 0) continue;
+        const unsigned long long first = km_reserve(out, cap, ck, tot, &ctr[d + 1]);
+        uint64_t o1 = first + fmd_below(m1);
+        uint64_t o2 = first + __popcll(m1) + fmd_below(m2);
+        uint64_t o3 = first + __popcll(m1) + __popcll(m2) + fmd_below(m3);
+        uint64_t o4 = first + __popcll(m1) + __popcll(m2) + __popcll(m3) + fmd_below(m4);
+        const uint64_t x1_4 = x1 + s[0], x1_3 = x1_4 + s[4], x1_2 = x1_3 + s[3], x1_1 = x1_2 + s[2];
+#define KM_PUSH(c, has, o, x1c)                                                                   \
+        if (has) {                                                                                \
+            if (o < cap) {                                                                        \
+                const uint64_t nx0 = ix.cnt[c] + tk[c], nk = K | (uint64_t)(c - 1) << (2 * d);    \
+                uint4 *q = (uint4 *)(out + o);                                                    \
+                q[0] = make_uint4((uint32_t)nx0, (uint32_t)(nx0 >> 32), (uint32_t)(x1c), (uint32_t)((x1c) >> 32)); \
+                q[1] = make_uint4((uint32_t)s[c], (uint32_t)(s[c] >> 32), (uint32_t)nk, (uint32_t)(nk >> 32));     \
+            } else ctr[i_ovf] = 1;                                                                \
+        }
+        KM_PUSH(1, has1, o1, x1_1) KM_PUSH(2, has2, o2, x1_2) KM_PUSH(3, has3, o3, x1_3) KM_PUSH(4, has4, o4, x1_4)
+#undef KM_PUSH
+    }
+    km_zero_fill(out, cap, ck);
+    if (lane == 0 && n_ext) atomicAdd(&ctr[i_ext], (unsigned long long)n_ext);
 }

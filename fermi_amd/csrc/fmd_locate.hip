@@ -56,13 +56,6 @@ extern "C" size_t fmd_locate_work_bytes(size_t n, uint64_t total_rows)
     return LOC_HDR_BYTES + 2 * (size_t)loc_cap(n, total_rows) * sizeof(LocItem);
 }
 
-__device__ __forceinline__ uint64_t loc_wave_sum(uint64_t v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += (uint64_t)__shfl_xor((unsigned long long)v, o);
-    return v;
-}
-
 // level 0: interval i -> item {beg[i], cnt[i], i}; empty intervals give nothing, those above max_occ -- and those that do not lie in the index -- are
 // skipped whole and counted
 __global__ __launch_bounds__(64) void k_locate_seed(uint64_t n_sym, size_t n, const uint64_t *__restrict__ beg, const uint64_t *__restrict__ cnt, uint32_t max_occ,
@@ -169,7 +162,7 @@ __global__ __launch_bounds__(64) void k_locate_level(FmdIndexView ix, uint32_t d
     }
     km_zero_fill(out, cap, ck);
     loc_flush_runs(run_buf, run_fill, d, ctr, runs, run_cap, rows);
-    rows = loc_wave_sum(rows);
+    rows = km_wave_sum(rows);
     if (lane == 0 && n_ext) atomicAdd(&ctr[LOC_EXT], (unsigned long long)n_ext);
     if (lane == 0 && rows) atomicAdd(&ctr[LOC_ROWS], (unsigned long long)rows);
 }
@@ -180,7 +173,7 @@ __global__ __launch_bounds__(64) void k_locate_rest(uint32_t d, const LocItem *_
     const uint64_t n = ctr[d % 3] < cap ? ctr[d % 3] : cap;
     uint64_t rows = 0;
     for (uint64_t i = (uint64_t)blockIdx.x * 64 + fmd_lane(); i < n; i += (uint64_t)gridDim.x * 64) rows += in[i].size;
-    rows = loc_wave_sum(rows);
+    rows = km_wave_sum(rows);
     if (fmd_lane() == 0 && rows) atomicAdd(&ctr[LOC_UNFIN], (unsigned long long)rows);
 }
 __global__ void k_locate_stat(const unsigned long long *__restrict__ ctr, uint64_t run_cap, fmd_locate_stat_t *__restrict__ stat)

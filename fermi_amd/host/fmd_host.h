@@ -380,6 +380,13 @@ int fmdh_main_msearch(int argc, char *argv[]);
 typedef struct { uint64_t id; uint32_t query, off; } fmdh_locate_hit_t;
 int fmdh_locate_hits(const fmd_locate_run_t *runs, uint64_t n_runs, const uint64_t *sorted, uint64_t n_seq, fmdh_locate_hit_t **hits, uint64_t *n_hits);
 int fmdh_main_locate(int argc, char *argv[]);
+/* kcount_cmd.c: `fermi-amd kcount [-k 21] [-o 1] [-b 10001] [-d] [-g GPU] <reads.fmd>`: the k-mer spectrum (count <tab> n_kmers per non-empty bin), or with -d
+ * the canonical k-mers and their counts, streamed (fmd_kcount); usage and unreadable-file errors return 1 before the device is looked for.  No GPU behind:
+ * fmdh_kmer_text: the k bases of a packed k-mer (include/fmd_hip.h) into buf (k + 1 bytes, NUL-terminated), -> buf; NULL for k outside 1..32
+ * fmdh_kcount_print_hist: one line per non-empty bin, ascending; the last bin's label is n_bins - 1 and stands for "that many or more" */
+char *fmdh_kmer_text(uint64_t kmer, int k, char *buf);
+void fmdh_kcount_print_hist(FILE *out, const uint64_t *hist, uint32_t n_bins);
+int fmdh_main_kcount(int argc, char *argv[]);
 int fmdh_fltuniq_auto_k(long long file_bytes);   /* the k `fltuniq` takes for an input file of that many bytes on disk (seq.c:147-150) */
 
 /* `fermi correct` (cmd.c:253-291, correct.c:305-456); defaults = cmd.c:258 */

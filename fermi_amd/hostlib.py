@@ -82,6 +82,8 @@ def lib():
         L.fmdh_scaf_free.restype = None; L.fmdh_scaf_free.argtypes = [vp]
         L.fmdh_scaf_cal_rdist.restype = C.c_double; L.fmdh_scaf_cal_rdist.argtypes = [vp]
         L.fmdh_locate_hits.argtypes = [vp, C.c_uint64, vp, C.c_uint64, C.POINTER(vp), C.POINTER(C.c_uint64)]
+        L.fmdh_kmer_text.restype = vp; L.fmdh_kmer_text.argtypes = [C.c_uint64, C.c_int, vp]
+        L.fmdh_kcount_print_hist.restype = None; L.fmdh_kcount_print_hist.argtypes = [vp, vp, C.c_uint32]
         _lib = L
     return _lib
 
@@ -134,6 +136,25 @@ def locate_hits(runs, n_seq, sorted_map=None):
         C.memmove(hits.ctypes.data, p.value, n.value * LOCATE_HIT_DT.itemsize)
     _libc.free(p)
     return hits
+
+
+def kmer_text(kmer, k):
+    """fmdh_kmer_text: the k bases of a packed k-mer (2 bits per base, A=0 C=1 G=2 T=3, the first base highest) as str; ValueError for k outside 1..32."""
+    buf = C.create_string_buffer(40)
+    if not lib().fmdh_kmer_text(int(kmer), int(k), buf):
+        raise ValueError("kmer_text: k = %d is outside 1..32" % k)
+    return buf.value.decode()
+
+
+def kcount_hist_text(hist):
+    """fmdh_kcount_print_hist: the lines `fermi-amd kcount` prints for a histogram (count <tab> n_kmers per non-empty bin), as one str."""
+    import tempfile
+    hist = np.ascontiguousarray(hist, dtype=np.uint64)
+    with tempfile.NamedTemporaryFile() as tf:
+        fp = _libc.fopen(tf.name.encode(), b"wb")
+        lib().fmdh_kcount_print_hist(fp, hist.ctypes.data, len(hist))
+        _libc.fclose(fp)
+        return open(tf.name).read()
 
 
 _libc = C.CDLL(None)

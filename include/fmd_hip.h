@@ -154,6 +154,44 @@ int fmd_locate_dev(fmd_dev_t *h, void *stream, size_t n, const uint64_t *d_beg, 
 int fmd_locate_batch(fmd_dev_t *h, size_t n, const uint64_t *beg, const uint64_t *cnt, uint32_t max_occ, uint32_t max_len,
                      fmd_locate_run_t **runs, uint64_t *n_runs, fmd_locate_stat_t *stat);      /* runs freed with fmd_host_free */
 
+/* ---- kcount (no reference counterpart; fermi2 has `count`): k-mer spectrum and counted k-mers from the index ----------------------
+ * A k-mer is k bases of A < C < G < T, 1 <= k <= 32, no N, no sentinel; occ(W) = the positions of the indexed sequences, both strands, where W
+ * occurs.  On an index of both strands occ(W) = occ(rc(W)); the canonical k-mer of W is min(W, rc(W)) and its COUNT is occ(W), or occ(W) / 2
+ * when W = rc(W) (even k only; occ is even then): the number of N-free k-windows of the forward sequences as indexed whose canonical form it is.
+ * Only k-mers with count >= min_occ (>= 1) are reported.  Packed form: uint64_t, 2 bits per base, A=0 C=1 G=2 T=3, the first base in the highest
+ * of the low 2k bits: numeric order is lexicographic order.  Counts are uint32_t and SATURATE at 2^32 - 1; the histogram and n_total use the
+ * exact count.  Histogram of n_bins >= 2 bins: hist[0] = 0, hist[i] = the k-mers with count i for 0 < i < n_bins - 1, hist[n_bins - 1] = those
+ * with count >= n_bins - 1.  stat: n_kmers = k-mers reported, n_total = the sum of their counts (min_occ = 1: the N-free k-windows of the forward
+ * sequences), n_ext = backward extensions done (discarded parts included), overflow (the _dev form), widest_level = the most frontier slots a
+ * level reserved (holes included), n_parts = parts run, n_retries = parts discarded because they did not fit.
+ *
+ * fmd_kcount_part_dev: one part.  d_roots = n_roots <= cap bi-intervals, 16-byte aligned, of suffixes of ONE length root_len (1 <= root_len <
+ * k, so k >= 2; info = the packed suffix; size 0 = skipped); every k-mer W that ends in one of them is walked, kept iff rc(W) <= W, ADDED to
+ * d_hist (n_bins words the caller zeroes) and -- d_kmer != NULL -- stored as (rc(W), count) in d_kmer / d_count, in no particular order, dense,
+ * out_cap entries at most.  cap = the entries of each of the two frontiers the work area (fmd_kcount_work_bytes(cap), 16-byte aligned) holds,
+ * FMD_KCOUNT_MIN_CAP <= cap <= FMD_KCOUNT_MAX_CAP (work_bytes returns 0 outside); chunk and grid shrink with it.  When a frontier entry or a pair
+ * does not fit, d_stat->overflow = 1, nothing is written past either, and histogram, list and sums are incomplete: discard them.  Enqueues on
+ * `stream` and returns: it neither allocates nor synchronises.
+ * fmd_kcount: the whole index.  Parts start from the four single-base roots in the order of rc(suffix); one that overflows is discarded whole and
+ * its run of roots cut in two, a single root replaced by its children one base deeper.  sink == NULL: the spectrum only.  Otherwise every part's
+ * pairs are sorted on the device and handed to sink(ctx, n, kmer, count) -- host arrays that live until it returns -- as consecutive slices,
+ * ascending over the whole run, no k-mer twice; a non-zero return stops the run (FMD_E_IO).  cap = 0: sized from the index and the free device
+ * memory, grown after an overflow while it fits; the list of a part has room for cap pairs.  The large buffers stay in the handle's cache between calls
+ * (fmd_dev_trim).  Histogram, list, n_kmers and n_total are the same for every cap.  k = 1 is answered from the
+ * marginal counts.  FMD_E_ARG: k outside 1..32 (the part entry: 2..32), min_occ < 1, n_bins < 2, a cap outside the range, or an index with
+ * mcnt[A] != mcnt[T], mcnt[C] != mcnt[G] or an odd number of sentinels -- a necessary sign of an index of both strands, NOT a sufficient one: a
+ * one-strand index (fmd_build_bwt_strands, `ropebwt -F/-R`) that passes it gets counts that mean nothing.  FMD_OPEN_NO_TABLES handles work. */
+#define FMD_KCOUNT_MIN_CAP 4096u
+#define FMD_KCOUNT_MAX_CAP (1u << 30)
+typedef struct { uint64_t n_kmers, n_total, n_ext, overflow, widest_level, n_parts, n_retries; } fmd_kcount_stat_t;
+typedef int (*fmd_kcount_sink_fn)(void *ctx, uint64_t n, const uint64_t *kmer, const uint32_t *count);
+size_t fmd_kcount_work_bytes(uint64_t cap);
+int fmd_kcount_part_dev(fmd_dev_t *h, void *stream, int k, int min_occ, int root_len, size_t n_roots, const fmd_intv_t *d_roots, uint64_t cap,
+                        uint32_t n_bins, uint64_t *d_hist, uint64_t *d_kmer, uint32_t *d_count, uint64_t out_cap, fmd_kcount_stat_t *d_stat,
+                        void *d_work, size_t work_bytes);
+int fmd_kcount(fmd_dev_t *h, int k, int min_occ, uint32_t n_bins, uint64_t *hist, uint64_t cap, fmd_kcount_sink_fn sink, void *ctx,
+               fmd_kcount_stat_t *stat);
+
 /* ---- inspection (`fermi chkbwt`, cmd.c:47-130) ------------------------------------------------
  * export: BWT[first, first+n) as nt6 bytes, decoded from the device layout (chkbwt -p).
  * check_rank: the device layout's rank of every position against the symbols themselves (chkbwt -r):
