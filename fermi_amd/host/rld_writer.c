@@ -25,6 +25,13 @@
 #include "fmd_host.h"
 
 #define WORDS_PER_BLOCK 8u
+/* A block's header counts its symbols in 31 bits (rld.c:120-129), so one run of 2^31 symbols or more cannot be ONE code.  The format does not ask for
+ * that: a reader takes the runs code by code, and equal symbols in consecutive codes are one run to it.  A run of SPLIT_FROM symbols or more is written as
+ * pieces of SPLIT_PIECE (a code of 39 bits: at most nine in the six payload words of a block, 1.2 * 10^9 symbols); no index of reads holds such a run, so
+ * the bytes of every file written so far stay what they were.  A block that would still count 2^31 symbols or more is an error (-ERANGE), not a file. */
+#define SPLIT_FROM (1ull << 30)
+#define SPLIT_PIECE (1ull << 27)
+#define E_LONG_RUN 1   /* a speculative slice met a run that has to be split: the caller encodes in one thread, where no block start has to be matched */
 static uint64_t g_words_per_chunk = 1u << 23;   /* rld.h:66; set by encode() before the writers start (test hook: FMD_RLD_TEST_CHUNK_WORDS) */
 #define WORDS_PER_CHUNK g_words_per_chunk
 
@@ -84,6 +91,7 @@ static int open_next_block(writer_t *s)
     uint64_t d[7];
     int i, rc;
     for (i = 0; i < 7; ++i) d[i] = s->total[i] - s->at_open[i];
+    if (d[0] >= 0x80000000ull) return -ERANGE;
     s->head += WORDS_PER_BLOCK;
     if ((rc = grow(s, s->head + 2 * WORDS_PER_BLOCK)) != 0) return rc;
     if (d[0] >= 0x8000) {
@@ -132,6 +140,13 @@ static int put_run(writer_t *s, uint64_t len, int sym)
     s->total[0] += len;
     s->total[1 + sym] += len;
     return 0;
+}
+
+static int put_long_run(writer_t *s, uint64_t len, int sym)
+{
+    int rc = 0;
+    for (; rc == 0 && len >= SPLIT_FROM; len -= SPLIT_PIECE) rc = put_run(s, SPLIT_PIECE, sym);
+    return rc ? rc : put_run(s, len, sym);
 }
 
 static void read_header(const uint64_t *blk, uint64_t h[7])
@@ -226,7 +241,7 @@ static int encode_sequential(const uint8_t *src, int is_bwt, uint64_t n, const c
     runit_t it = {src, is_bwt, 0, n};
     uint64_t len, in;
     int sym, rc = writer_init(&s);
-    while (rc == 0 && run_next(&it, &len, &sym, &in)) rc = put_run(&s, len, sym);
+    while (rc == 0 && run_next(&it, &len, &sym, &in)) rc = put_long_run(&s, len, sym);
     if (rc == 0) rc = finish_and_dump(&s, path);
     free(s.w);
     return rc;
@@ -246,7 +261,7 @@ static void *slice_main(void *p)
     s->recording = 1;
     s->last_usable = WORDS_PER_BLOCK - 1;
     if ((sl->rc = rec_push(s, 0, sl->beg, 2)) != 0) return 0;
-    while (sl->rc == 0 && run_next(&it, &len, &sym, &in)) { s->cur_in = in; sl->rc = put_run(s, len, sym); }
+    while (sl->rc == 0 && run_next(&it, &len, &sym, &in)) { s->cur_in = in; sl->rc = len >= SPLIT_FROM ? E_LONG_RUN : put_run(s, len, sym); }
     return 0;
 }
 static int block_is_empty(const writer_t *s) { return s->cur == s->head + s->cur_hw && s->room == 64; }
@@ -372,7 +387,10 @@ static int encode(const uint8_t *src, int is_bwt, uint64_t n, const char *path)
     { const char *e = getenv("FMD_RLD_THREADS"); if (e && atoi(e) > 0) T = atoi(e); }   /* (tests: 1 = the one-thread encoder) */
     if (T > 256) T = 256;
     if (T < 2 || n < (uint64_t)T * 4096) return encode_sequential(src, is_bwt, n, path);
-    return encode_parallel(src, is_bwt, n, path, T);
+    {
+        const int rc = encode_parallel(src, is_bwt, n, path, T);
+        return rc == E_LONG_RUN ? encode_sequential(src, is_bwt, n, path) : rc;
+    }
 }
 
 int fmdh_write_rld_from_rle6(const uint8_t *runs, uint64_t n_bytes, const char *path) { return encode(runs, 0, n_bytes, path); }

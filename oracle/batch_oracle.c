@@ -52,7 +52,8 @@ typedef struct {
     uint64_t rank, k[3];
     int32_t len, status, n_ovlp, rbeg, ext_len, n_nei;
     uint32_t flags;
-    uint16_t reserved, lfork;   /* lfork: EXACT here (orc_left_fork); the product may know less (see include/fmd_hip.h) */
+    uint16_t reserved, lfork;   /* flags: FORKED and FIXED as fm6_get_nei's own rounds say (orc_get_nei_flags), never OVERFLOW -- the port has no capacities;
+                                   lfork: EXACT here (orc_left_fork); the product may know less (see include/fmd_hip.h) */
 } orc_ovlp_rec_t;
 
 typedef struct { const orc_rld_t *e; size_t n; const uint64_t *ids; int min_match; uint32_t max_nei;
@@ -85,6 +86,7 @@ static void *ov_worker(void *d)
         if (w->with_cls) r->lfork = (uint16_t)orc_left_fork(w->e, w->min_match, s.s, len);   /* with the other check_left field: not part of the reference's per-read work that bench.py counts and times */
         if (a0.n) {
             r->rbeg = orc_get_nei(w->e, w->min_match, 0, &s, &nei, &a0, &a1);
+            r->flags = orc_get_nei_flags;
             r->ext_len = (int32_t)s.n - len;
             r->n_nei = (int32_t)nei.n;
             for (j = 0; j < nei.n && j < w->max_nei; ++j) w->nei[i * w->max_nei + j] = nei.a[j];

@@ -287,6 +287,8 @@ static int cmp_info(const void *a, const void *b)
     return x < y ? -1 : x > y;
 }
 
+__thread unsigned orc_get_nei_flags;
+
 int orc_get_nei(const orc_rld_t *e, int min_match, int beg, orc_str_t *s, orc_intv_v *nei,
                 orc_intv_v *prev, orc_intv_v *curr) /* unitig.c:93-179 with used=sorted=NULL */
 {
@@ -297,6 +299,7 @@ int orc_get_nei(const orc_rld_t *e, int min_match, int beg, orc_str_t *s, orc_in
     orc_intv_t ok[6], ok0;
 
     curr->n = nei->n = 0;
+    orc_get_nei_flags = 0;
     if (prev->n == 0) {
         overlap_intv(e, (int)s->n - beg, s->s + beg, min_match, (int)s->n - beg - 1, 0, prev, 0);
         if (prev->n == 0) return -1;
@@ -352,9 +355,11 @@ int orc_get_nei(const orc_rld_t *e, int min_match, int beg, orc_str_t *s, orc_in
         t = curr; curr = prev; prev = t;
     }
     free(cat);
+    orc_get_nei_flags = is_forked ? 1u : 0u;
     if (nei->n == 0) return -1;
     rbeg = ori_l - (int)(uint32_t)nei->a[0].info;
     if (nei->n == 1 && is_forked) { /* unitig.c:158-176 */
+        orc_get_nei_flags |= 4u;
         orc_set_intv(e, 0, &ok0);
         for (i = rbeg; i < ori_l; ++i) {
             orc_extend(e, &ok0, ok, 0);

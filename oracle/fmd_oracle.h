@@ -83,6 +83,9 @@ int orc_is_contained(const orc_rld_t *e, int min_match, const uint8_t *s, int le
 /* unitig.c:93; s grows (consensus bases appended); returns rbeg or -1 */
 int orc_get_nei(const orc_rld_t *e, int min_match, int beg, orc_str_t *s, orc_intv_v *nei,
                 orc_intv_v *prev, orc_intv_v *curr);
+/* what the last orc_get_nei of this thread saw, in the bits of include/fmd_hip.h: 1 (FMD_OVLP_F_FORKED) = a round left more than one
+ * category (`is_forked`, unitig.c:152), 4 (FMD_OVLP_F_FIXED) = the fix-up of unitig.c:158-176 ran */
+extern __thread unsigned orc_get_nei_flags;
 
 int orc_check_left_simple(const orc_rld_t *e, int min_match, int beg, int rbeg, const uint8_t *s, int len);
 unsigned orc_left_fork(const orc_rld_t *e, int min_match, const uint8_t *x, int len); /* unitig.c:186 */

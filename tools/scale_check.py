@@ -46,6 +46,17 @@ seed = synth.DEFAULT_SEED
 rng = np.random.default_rng(11)
 
 
+def explain_overlap_mismatch(ids, rec, nei, keep, what):
+    """which rows and fields differ from the port's (tests/ovlp_diff.py): a MISMATCH names its ids"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import orcbind
+    import ovlp_diff
+    o = orcbind.OrcIndex(fmd_path)
+    w_rec, w_nei, _ = o.overlap_batch(ids, 50, 100, nei.shape[1], bench.usable_cpus(), check_left=False)
+    o.close()
+    print(ovlp_diff.explain(rec, nei, w_rec, w_nei, ids, fields=("rank", "k", "len", "status", "n_ovlp", "rbeg", "ext_len", "n_nei", "flags"), rows=keep, what=what + " against the port"), flush=True)
+
+
 def hbm_used():
     free_b, total_b = torch.cuda.mem_get_info()
     return (total_b - free_b) / 1e9
@@ -201,6 +212,8 @@ if not noref:
     base, ok = bench.cpu_overlap(fmd_path, ids, 50, rec, nei, keep=keep)
     print("overlap discovery vs %s on %d random sequence ids (%d of them without an answer at %d neighbour slots): %s (reference %.0f reads/s on %d threads)"
           % (base["kind"], len(ids), int((~keep).sum()), MAX_NEI, "bit-exact" if ok else "MISMATCH", base["value"], base["cores"]), flush=True)
+    if not ok:
+        explain_overlap_mismatch(ids, rec, nei, keep, "overlap discovery of random ids")
     assert ok and keep.mean() > 0.99
     if raw:   # the forked path beyond 2^32 symbols: the sorted job (walk passes, fast and general group kernels, 64-bit forms) on a larger sample, and check_left
         ids2 = np.sort(rng.choice(2 * n_reads, min(10 * sample, 2 * n_reads), replace=False)).astype(np.uint64)
@@ -210,6 +223,8 @@ if not noref:
         _, ok2 = bench.cpu_overlap(fmd_path, ids2, 50, rec2, nei2, keep=keep2)
         print("the sorted job vs the reference on %d random sequence ids: %s (%d forked strands, %d with more than one neighbour, %d without an answer)"
               % (len(ids2), "bit-exact" if ok2 else "MISMATCH", forked, int((rec2["n_nei"] > 1).sum()), int((~keep2).sum())), flush=True)
+        if not ok2:
+            explain_overlap_mismatch(ids2, rec2, nei2, keep2, "the sorted job")
         assert ok2 and keep2.mean() > 0.99 and forked > len(ids2) // 100
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import orcbind
