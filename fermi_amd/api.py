@@ -22,6 +22,10 @@ LOCATE_STAT_DT = np.dtype([(f, "<u8") for f in ("n_runs", "n_rows", "n_skipped",
 KCOUNT_STAT_DT = np.dtype([(f, "<u8") for f in ("n_kmers", "n_total", "n_ext", "overflow", "widest_level", "n_parts", "n_retries")])  # fmd_kcount_stat_t
 KCOUNT_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32))  # fmd_kcount_sink_fn
 KCOUNT_MIN_CAP, KCOUNT_MAX_CAP = 4096, 1 << 30   # FMD_KCOUNT_MIN_CAP, FMD_KCOUNT_MAX_CAP
+ASEARCH_HIT_DT = np.dtype([("beg", "<u8"), ("cnt", "<u8"), ("query", "<u4"), ("n_sub", "<u4"), ("sub", "<u2", 4)])  # fmd_asearch_hit_t
+ASEARCH_STAT_DT = np.dtype([(f, "<u8") for f in ("n_hits", "n_occ", "n_skipped", "n_truncated", "n_unfinished", "overflow", "n_ext", "widest_level")])  # fmd_asearch_stat_t
+ASEARCH_MAX_SUB, ASEARCH_MAX_LEN, ASEARCH_MIN_CAP, ASEARCH_MAX_CAP = 4, 16383, 4096, 1 << 28   # FMD_ASEARCH_*
+ASEARCH_NO_PRUNE, ASEARCH_BEST = 1, 2
 
 # every symbol include/fmd_hip.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
@@ -52,6 +56,7 @@ ABI_SYMBOLS = [
     "fmd_multi_bsearch_work_bytes", "fmd_multi_bsearch_dev", "fmd_multi_bsearch_batch",
     "fmd_locate_work_bytes", "fmd_locate_dev", "fmd_locate_batch",
     "fmd_kcount_work_bytes", "fmd_kcount_part_dev", "fmd_kcount",
+    "fmd_asearch_work_bytes", "fmd_asearch_bound_dev", "fmd_asearch_dev", "fmd_asearch_batch",
 ]
 
 
@@ -137,6 +142,10 @@ def _configure(L):
     L.fmd_kcount_work_bytes.restype = sz; L.fmd_kcount_work_bytes.argtypes = [C.c_uint64]
     L.fmd_kcount_part_dev.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, sz, vp, C.c_uint64, C.c_uint32, u64p, u64p, vp, C.c_uint64, vp, vp, sz]
     L.fmd_kcount.argtypes = [vp, C.c_int, C.c_int, C.c_uint32, u64p, C.c_uint64, vp, vp, vp]
+    L.fmd_asearch_work_bytes.restype = sz; L.fmd_asearch_work_bytes.argtypes = [sz, C.c_uint64]
+    L.fmd_asearch_bound_dev.argtypes = [vp, vp, sz, vp, u64p, vp]
+    L.fmd_asearch_dev.argtypes = [vp, vp, sz, vp, u64p, vp, C.c_int, C.c_uint32, C.c_uint32, vp, C.c_uint64, u64p, vp, vp, sz]
+    L.fmd_asearch_batch.argtypes = [vp, sz, vp, u64p, C.c_int, C.c_uint32, C.c_uint, C.c_uint64, C.POINTER(vp), C.POINTER(C.c_uint64), u64p, vp]
     L.fmd_retrieve_batch.argtypes = [vp, sz, u64p, vp, C.c_uint32, vp, u64p]
     L.fmd_build_bwt.argtypes = [C.c_int, sz, vp, u64p, vp, C.POINTER(C.c_uint64)]
     L.fmd_build_bwt_dev.argtypes = [C.c_int, vp, sz, vp, u64p, C.c_uint64, C.c_uint32, C.c_int, C.POINTER(vp), C.POINTER(C.c_uint64)]
@@ -484,6 +493,67 @@ class DevIndex:
 
         _, stat = self._kcount(k, min_occ, 2, cap, sink)
         return (np.concatenate(ks) if ks else np.zeros(0, np.uint64)), (np.concatenate(cs) if cs else np.zeros(0, np.uint32)), stat
+
+    def approx_search(self, seqs, max_sub=1, max_hits=1000, best=False, prune=True, cap=0, count_only=False, with_stat=False):
+        """fmd_asearch_batch: the patterns within max_sub substitutions (0 .. ASEARCH_MAX_SUB; no insertions or deletions) of every query that occur
+        -> (strata[n, max_sub + 1, 2], hits).  strata[i, j] = (the hits of query i with j substitutions, the sum of their counts), exact whether or
+        not the hits are listed; hits = a structured array (ASEARCH_HIT_DT: beg, cnt = the SA interval of the pattern, query, n_sub, sub[4] =
+        pos << 2 | base - 1 by descending pos, 0xffff = unused; approx_pattern gives the pattern) sorted by (query, n_sub, beg), without those of
+        the queries that have more than max_hits.  An N in a query costs one substitution.  best: only the lowest stratum of every query that
+        has a hit.  prune=False: without the lower bound (approx_bound) -- the same result, more extensions.  cap: the frontier capacity in entries
+        (ASEARCH_MIN_CAP ..; 0 = sized from the batch); the result does not depend on it.  count_only: hits is empty, nothing is listed.
+        with_stat: a third element, the fields of ASEARCH_STAT_DT as a dict."""
+        flat, off = flatten_reads(seqs)
+        n = len(off) - 1
+        if not 0 <= int(max_sub) <= ASEARCH_MAX_SUB:
+            raise FmdError("approx_search: max_sub = %d is outside 0..%d" % (max_sub, ASEARCH_MAX_SUB))
+        strata = np.zeros((n, int(max_sub) + 1, 2), dtype=np.uint64)
+        stat = np.zeros(1, dtype=ASEARCH_STAT_DT)
+        p, m = C.c_void_p(), C.c_uint64()
+        flags = (0 if prune else ASEARCH_NO_PRUNE) | (ASEARCH_BEST if best else 0)
+        check(lib().fmd_asearch_batch(self.h, n, _ptr(flat), _ptr(off), int(max_sub), int(max_hits), flags, int(cap),
+                                      None if count_only else C.byref(p), None if count_only else C.byref(m), _ptr(strata) if n else None, _ptr(stat)))
+        hits = np.zeros(m.value, dtype=ASEARCH_HIT_DT)
+        if m.value:
+            C.memmove(_ptr(hits), p.value, m.value * ASEARCH_HIT_DT.itemsize)
+        if p.value:
+            lib().fmd_host_free(p)
+        if with_stat:
+            return strata, hits, {f: int(stat[0][f]) for f in ASEARCH_STAT_DT.names}
+        return strata, hits
+
+    def approx_bound(self, seqs):
+        """fmd_asearch_bound_dev: per query a uint8 array, lb[p] = min(255, the disjoint substrings of q[0 .. p], taken greedily from the left, that
+        do not occur) -- a lower bound of the substitutions a hit spends in q[0 .. p]; an N costs one.  All zero on an index that is not of
+        both strands; zero for a query longer than ASEARCH_MAX_LEN."""
+        flat, off = flatten_reads(seqs)
+        n = len(off) - 1
+        if n == 0:
+            return []
+        L = lib()
+        bufs = []
+        try:
+            for a in (flat, off, np.zeros(len(flat), dtype=np.uint8)):
+                p = C.c_void_p()
+                check(L.fmd_dev_malloc(self.device, max(a.nbytes, 16), C.byref(p)))
+                bufs.append(p)
+                check(L.fmd_memcpy_h2d(p, _ptr(a), a.nbytes, None))
+            check(L.fmd_asearch_bound_dev(self.h, None, n, bufs[0], bufs[1], bufs[2]))
+            self.sync()
+            lb = np.zeros(len(flat), dtype=np.uint8)
+            check(L.fmd_memcpy_d2h(_ptr(lb), bufs[2], lb.nbytes, None))
+        finally:
+            for p in bufs:
+                L.fmd_dev_free(p)
+        return [lb[int(off[i]):int(off[i + 1])].copy() for i in range(n)]
+
+
+def approx_pattern(query, hit):
+    """The pattern of a hit of approx_search: `query` (nt6) with the hit's substitutions applied, as a uint8 array."""
+    out = np.array(query, dtype=np.uint8)
+    for v in hit["sub"][:int(hit["n_sub"])]:
+        out[int(v) >> 2] = 1 + (int(v) & 3)
+    return out
 
 
 FMD_MULTI_MAX = 16   # include/fmd_hip.h

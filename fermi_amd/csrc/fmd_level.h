@@ -1,4 +1,4 @@
-// fmd_level.h -- what the level-by-level trie walks share (the k-mer harvest, fmd_kmer.hip; kcount, fmd_kcount.hip; locate, fmd_locate.hip): one
+// fmd_level.h -- what the level-by-level trie walks share (the k-mer harvest, fmd_kmer.hip; kcount, fmd_kcount.hip; locate, fmd_locate.hip; asearch, fmd_asearch.hip): one
 // backward extension per lane on the wave engine, output slots reserved per wave in chunks, the frontier cut into one range per XCD, the level step of the
 // two k-mer walks.
 // A frontier entry is a multiple of 16 bytes whose all-zero image is a hole (size 0) that the next level skips.
@@ -11,9 +11,10 @@
 // only).  Wide intervals: two six-symbol block ranks.
 // ALL6 = false: the kept children are the bases A/C/G/T with at least thr occurrences (the harvest).  ALL6 = true: every child that
 // occurs, '$' and N included (locate: the rank of the '$' child is where its run of sentinels starts), and x0 = 0 is a legal start.
-template <bool NEED_TK, bool ALL6 = false>
+// MASKED = true: of those children, a narrow interval gets tk[c] only where bit c of `keep` is set (asearch: the children its budget still allows).
+template <bool NEED_TK, bool ALL6 = false, bool MASKED = false>
 __device__ __forceinline__ void km_extend_back(const FmdIndexView &ix, uint4 *lds, bool active, uint64_t x0, uint64_t sz,
-                                               uint64_t thr, uint64_t tk[6], uint64_t s[6])
+                                               uint64_t thr, uint64_t tk[6], uint64_t s[6], uint32_t keep = 0x3fu)
 {
     FmdRank2c r = fmd_wave_rank2_fetch_compact(ix, lds, active ? x0 - 1 : NONE64, active ? x0 - 1 + sz : NONE64);
     const bool narrow = active && sz <= 63 && !(r.two_phase && r.l_sep) && (!ALL6 || x0 != 0);   // (x0 = 0 has no k side to hang the window on)
@@ -34,6 +35,7 @@ __device__ __forceinline__ void km_extend_back(const FmdIndexView &ix, uint4 *ld
         if (NEED_TK) {
             uint32_t todo = (s[1] >= thr ? 2u : 0u) | (s[2] >= thr ? 4u : 0u) | (s[3] >= thr ? 8u : 0u) | (s[4] >= thr ? 16u : 0u);
             if (ALL6) todo |= (s[0] >= thr ? 1u : 0u) | (s[5] >= thr ? 32u : 0u);
+            if (MASKED) todo &= keep;
             while (__ballot(todo != 0)) {
                 const int cc = todo ? __ffs((int)todo) - 1 : 1;
                 const uint64_t v = r.hk ? fmd_block_rank1(r.bk, r.t, r.nk, cc, r.blk_k) : 0;

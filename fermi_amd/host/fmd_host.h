@@ -387,6 +387,13 @@ int fmdh_main_locate(int argc, char *argv[]);
 char *fmdh_kmer_text(uint64_t kmer, int k, char *buf);
 void fmdh_kcount_print_hist(FILE *out, const uint64_t *hist, uint32_t n_bins);
 int fmdh_main_kcount(int argc, char *argv[]);
+/* asearch_cmd.c: `fermi-amd asearch [-g GPU] [-d 1] [-b] [-m 1000] [-l] [-M 1000] [-r reads.rank] <reads.fmd> <query.fa>`: the patterns within -d substitutions of
+ * every query that occur (fmd_asearch_batch), with -l the reads that hold each (fmd_locate_batch + fmdh_locate_hits); usage and unreadable-file errors return 1
+ * before the device is looked for.  No GPU behind:
+ * fmdh_asearch_pattern: the pattern of a hit -- the query (nt6, len bases) with the hit's substitutions applied -- into out (len bytes, nt6); 1 when a
+ * substitution lies outside the query, names no base, or the list is not in descending order of position, 0 otherwise */
+int fmdh_asearch_pattern(const uint8_t *query, uint32_t len, const fmd_asearch_hit_t *hit, uint8_t *out);
+int fmdh_main_asearch(int argc, char *argv[]);
 int fmdh_fltuniq_auto_k(long long file_bytes);   /* the k `fltuniq` takes for an input file of that many bytes on disk (seq.c:147-150) */
 
 /* `fermi correct` (cmd.c:253-291, correct.c:305-456); defaults = cmd.c:258 */

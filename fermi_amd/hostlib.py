@@ -84,6 +84,7 @@ def lib():
         L.fmdh_locate_hits.argtypes = [vp, C.c_uint64, vp, C.c_uint64, C.POINTER(vp), C.POINTER(C.c_uint64)]
         L.fmdh_kmer_text.restype = vp; L.fmdh_kmer_text.argtypes = [C.c_uint64, C.c_int, vp]
         L.fmdh_kcount_print_hist.restype = None; L.fmdh_kcount_print_hist.argtypes = [vp, vp, C.c_uint32]
+        L.fmdh_asearch_pattern.argtypes = [vp, C.c_uint32, vp, vp]
         _lib = L
     return _lib
 
@@ -144,6 +145,21 @@ def kmer_text(kmer, k):
     if not lib().fmdh_kmer_text(int(kmer), int(k), buf):
         raise ValueError("kmer_text: k = %d is outside 1..32" % k)
     return buf.value.decode()
+
+
+ASEARCH_HIT_DT = np.dtype([("beg", "<u8"), ("cnt", "<u8"), ("query", "<u4"), ("n_sub", "<u4"), ("sub", "<u2", 4)])   # fmd_asearch_hit_t (include/fmd_hip.h)
+
+
+def asearch_pattern(query, hit):
+    """fmdh_asearch_pattern: the pattern of an asearch hit -- `query` (nt6) with the hit's substitutions applied -- as a uint8 array; ValueError when a
+    substitution lies outside the query or the list is not 0xffff-padded and in descending order of position."""
+    q = np.ascontiguousarray(query, dtype=np.uint8)
+    h = np.zeros(1, dtype=ASEARCH_HIT_DT)
+    h[0] = hit
+    out = np.zeros(max(len(q), 1), dtype=np.uint8)
+    if lib().fmdh_asearch_pattern(q.ctypes.data, len(q), h.ctypes.data, out.ctypes.data) != 0:
+        raise ValueError("asearch_pattern: a substitution list that does not fit a query of %d bases" % len(q))
+    return out[:len(q)]
 
 
 def kcount_hist_text(hist):

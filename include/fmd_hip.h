@@ -192,6 +192,57 @@ int fmd_kcount_part_dev(fmd_dev_t *h, void *stream, int k, int min_occ, int root
 int fmd_kcount(fmd_dev_t *h, int k, int min_occ, uint32_t n_bins, uint64_t *hist, uint64_t cap, fmd_kcount_sink_fn sink, void *ctx,
                fmd_kcount_stat_t *stat);
 
+/* ---- asearch (no reference counterpart): search with up to max_sub substitutions ---------------------------------------------------
+ * Query i is seqs[off[i] .. off[i+1]) in nt6, L bases (the contract of fmd_bsearch_dev: the bytes 4-byte aligned and readable to the next
+ * multiple of 4).  A PATTERN P is a string over A/C/G/T of length L; it is a HIT of the query when occ(P) > 0 and P differs from the query in
+ * at most max_sub positions, 0 <= max_sub <= FMD_ASEARCH_MAX_SUB.  A query base outside A/C/G/T (N) equals no pattern base: every pattern pays
+ * one substitution there.  N and '$' of the index match nothing, so a hit never spans two sequences.  ONLY SUBSTITUTIONS: insertions and
+ * deletions are not looked for.  A hit: beg, cnt = the SA interval of P (the beg fmd_bsearch gives for P); query; n_sub; sub[j] = pos << 2 |
+ * (base - 1) of each substitution (base = the pattern's, nt6), by DESCENDING pos, unused entries 0xffff -- hence L <= FMD_ASEARCH_MAX_LEN.
+ * Distinct hits of one query have disjoint intervals.  Per query i and stratum j = 0 .. max_sub two exact counters,
+ * strata[(i * (max_sub + 1) + j) * 2 + {0, 1}] = the hits with j substitutions and the sum of their cnt; they are kept whether or not hits are
+ * listed (d_hits == NULL, hit_cap == 0: count-only).  A query with more than max_hits hits is TRUNCATED: none of its hits is listed (as locate does
+ * with max_occ), its strata stay exact.  A query that is empty or longer than FMD_ASEARCH_MAX_LEN gives nothing and is counted in n_skipped.
+ * stat: n_hits, n_occ = the hits of the queries that are not truncated and the sum of their cnt; n_skipped; n_truncated; n_unfinished = items
+ * still walking after the last level; overflow != 0: a frontier entry (bit 0) or a hit (bit 1) did not fit -- it was written nowhere, the result
+ * is incomplete; n_ext = backward extensions done; widest_level = the most frontier slots a level reserved (holes included).
+ *
+ * The walk: the trie of the patterns, rooted at the LAST base, level by level -- level 0 takes the last base from the
+ * marginal counts, an item of level t >= 1 stands before position L - 1 - t and takes one backward extension --, each item with the number of
+ * substitutions spent so far.  fmd_asearch_bound_dev gives the bound that prunes it: lb[off[i] + p] = min(255, the number of disjoint substrings
+ * of q[0 .. p] that do not occur, found greedily from the left), a lower bound of the substitutions any hit spends in q[0 .. p] (what BWA calls
+ * D); an N costs one.  It relies on occ(W) > 0 <=> occ(rc(W)) > 0: on an index that fails kcount's necessary test of both strands (mcnt[A] !=
+ * mcnt[T], mcnt[C] != mcnt[G] or an odd number of sentinels) lb is all zero -- no pruning.  lb of a skipped query is not written.
+ * fmd_asearch_dev: d_lb = NULL walks without the bound.  It zeroes d_strata (n * (max_sub + 1) * 2 words), enqueues level 0 and exactly `levels`
+ * levels (L - 1 finish a query of L bases) on `stream` and returns: it neither allocates nor synchronises.  d_hits receives hits in no
+ * particular order, dense: those of the queries that are not truncated and max_hits of every truncated one -- n_hits + n_truncated * max_hits
+ * entries, which the caller sorts out by the strata -- never more than hit_cap.  The work area is fmd_asearch_work_bytes(n, cap) bytes, 16-byte
+ * aligned; cap = the entries of each of the two frontiers, FMD_ASEARCH_MIN_CAP <= cap <= FMD_ASEARCH_MAX_CAP (0 outside); the capacity follows
+ * from work_bytes.
+ * fmd_asearch_batch: host arrays.  The bound, then parts of the query range, levels in groups until the frontier is empty; a part that overflows
+ * is discarded and its range cut in two; a single query that does not fit is retried in twice the capacity while cap = 0 allows (cap = 0: sized
+ * from the batch and the free device memory), FMD_E_OVERFLOW otherwise.  hits (may be NULL: count only; else freed with fmd_host_free): those of
+ * the queries that are not truncated, sorted by (query, n_sub, beg).  strata: n * (max_sub + 1) * 2 words.  The result is the same for every
+ * cap.  FMD_ASEARCH_NO_PRUNE: without the bound.  FMD_ASEARCH_BEST: only the lowest stratum of every query that has a hit -- budgets 0, 1, .. over
+ * the queries still without one; the strata above it are reported as zero.
+ * FMD_E_ARG: max_sub outside 0 .. FMD_ASEARCH_MAX_SUB, a null pointer with n > 0, n >= 2^32, a work area too small or misaligned, a cap out of
+ * range, unknown flags.  n = 0 is a no-op.  FMD_OPEN_NO_TABLES handles work; two-base blocks are not used. */
+#define FMD_ASEARCH_MAX_SUB 4
+#define FMD_ASEARCH_MAX_LEN 16383u
+#define FMD_ASEARCH_MIN_CAP 4096u
+#define FMD_ASEARCH_MAX_CAP (1u << 28)
+#define FMD_ASEARCH_NO_PRUNE 1u
+#define FMD_ASEARCH_BEST 2u
+typedef struct { uint64_t beg, cnt; uint32_t query, n_sub; uint16_t sub[4]; } fmd_asearch_hit_t;
+typedef struct { uint64_t n_hits, n_occ, n_skipped, n_truncated, n_unfinished, overflow, n_ext, widest_level; } fmd_asearch_stat_t;
+size_t fmd_asearch_work_bytes(size_t n, uint64_t cap);
+int fmd_asearch_bound_dev(fmd_dev_t *h, void *stream, size_t n, const uint8_t *d_seqs, const uint64_t *d_off, uint8_t *d_lb);
+int fmd_asearch_dev(fmd_dev_t *h, void *stream, size_t n, const uint8_t *d_seqs, const uint64_t *d_off, const uint8_t *d_lb, int max_sub,
+                    uint32_t max_hits, uint32_t levels, fmd_asearch_hit_t *d_hits, uint64_t hit_cap, uint64_t *d_strata,
+                    fmd_asearch_stat_t *d_stat, void *d_work, size_t work_bytes);
+int fmd_asearch_batch(fmd_dev_t *h, size_t n, const uint8_t *seqs, const uint64_t *off, int max_sub, uint32_t max_hits, unsigned flags,
+                      uint64_t cap, fmd_asearch_hit_t **hits, uint64_t *n_hits, uint64_t *strata, fmd_asearch_stat_t *stat);
+
 /* ---- inspection (`fermi chkbwt`, cmd.c:47-130) ------------------------------------------------
  * export: BWT[first, first+n) as nt6 bytes, decoded from the device layout (chkbwt -p).
  * check_rank: the device layout's rank of every position against the symbols themselves (chkbwt -r):
