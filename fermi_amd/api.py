@@ -26,6 +26,10 @@ ASEARCH_HIT_DT = np.dtype([("beg", "<u8"), ("cnt", "<u8"), ("query", "<u4"), ("n
 ASEARCH_STAT_DT = np.dtype([(f, "<u8") for f in ("n_hits", "n_occ", "n_skipped", "n_truncated", "n_unfinished", "overflow", "n_ext", "widest_level")])  # fmd_asearch_stat_t
 ASEARCH_MAX_SUB, ASEARCH_MAX_LEN, ASEARCH_MIN_CAP, ASEARCH_MAX_CAP = 4, 16383, 4096, 1 << 28   # FMD_ASEARCH_*
 ASEARCH_NO_PRUNE, ASEARCH_BEST = 1, 2
+ESEARCH_HIT_DT = np.dtype([("beg", "<u8"), ("cnt", "<u8"), ("query", "<u4"), ("n_edit", "<u4"), ("len", "<u4"), ("reserved", "<u4")])  # fmd_esearch_hit_t
+ESEARCH_STAT_DT = ASEARCH_STAT_DT                                                                           # fmd_esearch_stat_t: the same fields
+ESEARCH_MAX_EDIT, ESEARCH_MAX_LEN, ESEARCH_MIN_CAP, ESEARCH_MAX_CAP = 4, 16383, 4096, 1 << 28   # FMD_ESEARCH_*
+ESEARCH_NO_PRUNE, ESEARCH_BEST = 1, 2
 
 # every symbol include/fmd_hip.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
@@ -57,6 +61,7 @@ ABI_SYMBOLS = [
     "fmd_locate_work_bytes", "fmd_locate_dev", "fmd_locate_batch",
     "fmd_kcount_work_bytes", "fmd_kcount_part_dev", "fmd_kcount",
     "fmd_asearch_work_bytes", "fmd_asearch_bound_dev", "fmd_asearch_dev", "fmd_asearch_batch",
+    "fmd_esearch_work_bytes", "fmd_esearch_dev", "fmd_esearch_batch",
 ]
 
 
@@ -146,6 +151,9 @@ def _configure(L):
     L.fmd_asearch_bound_dev.argtypes = [vp, vp, sz, vp, u64p, vp]
     L.fmd_asearch_dev.argtypes = [vp, vp, sz, vp, u64p, vp, C.c_int, C.c_uint32, C.c_uint32, vp, C.c_uint64, u64p, vp, vp, sz]
     L.fmd_asearch_batch.argtypes = [vp, sz, vp, u64p, C.c_int, C.c_uint32, C.c_uint, C.c_uint64, C.POINTER(vp), C.POINTER(C.c_uint64), u64p, vp]
+    L.fmd_esearch_work_bytes.restype = sz; L.fmd_esearch_work_bytes.argtypes = [sz, C.c_uint64]
+    L.fmd_esearch_dev.argtypes = [vp, vp, sz, vp, u64p, vp, C.c_int, C.c_uint32, C.c_uint32, vp, C.c_uint64, u64p, vp, vp, sz]
+    L.fmd_esearch_batch.argtypes = [vp, sz, vp, u64p, C.c_int, C.c_uint32, C.c_uint, C.c_uint64, C.POINTER(vp), C.POINTER(C.c_uint64), u64p, vp]
     L.fmd_retrieve_batch.argtypes = [vp, sz, u64p, vp, C.c_uint32, vp, u64p]
     L.fmd_build_bwt.argtypes = [C.c_int, sz, vp, u64p, vp, C.POINTER(C.c_uint64)]
     L.fmd_build_bwt_dev.argtypes = [C.c_int, vp, sz, vp, u64p, C.c_uint64, C.c_uint32, C.c_int, C.POINTER(vp), C.POINTER(C.c_uint64)]
@@ -521,6 +529,42 @@ class DevIndex:
         if with_stat:
             return strata, hits, {f: int(stat[0][f]) for f in ASEARCH_STAT_DT.names}
         return strata, hits
+
+    def edit_search(self, seqs, max_edit=1, max_hits=1000, best=False, prune=True, cap=0, count_only=False, with_stat=False):
+        """fmd_esearch_batch: the patterns within max_edit edits (0 .. ESEARCH_MAX_EDIT; substitutions, insertions and deletions, 1 each) of every query
+        that occur -> (strata[n, max_edit + 1, 2], hits).  strata[i, j] = (the hits of query i at edit distance j, the sum of their counts), exact whether
+        or not the hits are listed; hits = a structured array (ESEARCH_HIT_DT: beg, cnt = the SA interval of the pattern, query, n_edit = its exact
+        distance, len = its length, max(1, L - max_edit) .. L + max_edit; edit_patterns reads the patterns back) sorted by (query, n_edit, beg, len),
+        without those of the queries that have more than max_hits.  Every distinct pattern is one hit.  An N in a query costs one.  best: only the
+        lowest stratum of every query that has a hit.  prune=False: without the lower bound (approx_bound) -- the same result, more extensions.  cap:
+        the frontier capacity in entries (ESEARCH_MIN_CAP ..; 0 = sized from the batch); the result does not depend on it.  count_only: hits is empty,
+        nothing is listed.  with_stat: a third element, the fields of ESEARCH_STAT_DT as a dict."""
+        flat, off = flatten_reads(seqs)
+        n = len(off) - 1
+        if not 0 <= int(max_edit) <= ESEARCH_MAX_EDIT:
+            raise FmdError("edit_search: max_edit = %d is outside 0..%d" % (max_edit, ESEARCH_MAX_EDIT))
+        strata = np.zeros((n, int(max_edit) + 1, 2), dtype=np.uint64)
+        stat = np.zeros(1, dtype=ESEARCH_STAT_DT)
+        p, m = C.c_void_p(), C.c_uint64()
+        flags = (0 if prune else ESEARCH_NO_PRUNE) | (ESEARCH_BEST if best else 0)
+        check(lib().fmd_esearch_batch(self.h, n, _ptr(flat), _ptr(off), int(max_edit), int(max_hits), flags, int(cap),
+                                      None if count_only else C.byref(p), None if count_only else C.byref(m), _ptr(strata) if n else None, _ptr(stat)))
+        hits = np.zeros(m.value, dtype=ESEARCH_HIT_DT)
+        if m.value:
+            C.memmove(_ptr(hits), p.value, m.value * ESEARCH_HIT_DT.itemsize)
+        if p.value:
+            lib().fmd_host_free(p)
+        if with_stat:
+            return strata, hits, {f: int(stat[0][f]) for f in ESEARCH_STAT_DT.names}
+        return strata, hits
+
+    def edit_patterns(self, hits):
+        """hostlib.esearch_patterns for the hits of edit_search on this index: a list of uint8 arrays (nt6), the pattern of every hit.  The map from
+        sentinel ranks to rows (hostlib.esearch_rankmap: one walk over every sequence) is made at the first call and kept."""
+        from . import hostlib
+        if getattr(self, "_esearch_row_of", None) is None:
+            self._esearch_row_of = hostlib.esearch_rankmap(self.h)
+        return hostlib.esearch_patterns(self.h, self._esearch_row_of, hits)
 
     def approx_bound(self, seqs):
         """fmd_asearch_bound_dev: per query a uint8 array, lb[p] = min(255, the disjoint substrings of q[0 .. p], taken greedily from the left, that

@@ -394,6 +394,21 @@ int fmdh_main_kcount(int argc, char *argv[]);
  * substitution lies outside the query, names no base, or the list is not in descending order of position, 0 otherwise */
 int fmdh_asearch_pattern(const uint8_t *query, uint32_t len, const fmd_asearch_hit_t *hit, uint8_t *out);
 int fmdh_main_asearch(int argc, char *argv[]);
+/* esearch_cmd.c: `fermi-amd esearch [-g GPU] [-e 1] [-b] [-m 1000] [-l] [-M 1000] [-r reads.rank] <reads.fmd> <query.fa>`: the patterns within -e edits --
+ * substitutions, insertions, deletions -- of every query that occur (fmd_esearch_batch), with -l the reads that hold each; usage and unreadable-file errors
+ * return 1 before the device is looked for.
+ * fmdh_esearch_cigar (no GPU): one optimal alignment of the pattern (nt6, plen bases) to the query (nt6, qlen bases; a base outside A/C/G/T equals none) as a
+ * run-length CIGAR from the start of both -- '=' equal, 'X' substituted, 'I' a query base absent from the pattern, 'D' a pattern base absent from the query --,
+ * malloc'ed (free()), "" for two empty strings, NULL without memory; *n_edit (may be NULL) = the edit distance = the operations that are not '='.  Traced
+ * back from the END of both strings, taking at every step the first of diagonal ('=' / 'X'), 'I', 'D' that keeps the cost optimal.
+ * fmdh_esearch_rankmap: row_of[r] (malloc'ed, *n_seq entries) = the row i < n_seq whose LF-walk (fmd_retrieve_batch) ends on sentinel rank r; one walk over
+ * every sequence of the index.  fmdh_esearch_patterns: the patterns of n hits, read back from the index -- hit j's into pats[pat_off[j] .. + len), nt6 --: the
+ * walk from row beg gives the sentinel rank of a sequence that holds the pattern and the bases before it, the walk from row_of[rank] that sequence, as `unpack`
+ * reads it.  Both return 1 on a device error, no memory, or rows and lengths that do not fit the index. */
+char *fmdh_esearch_cigar(const uint8_t *query, uint32_t qlen, const uint8_t *pat, uint32_t plen, uint32_t *n_edit);
+int fmdh_esearch_rankmap(fmd_dev_t *d, uint64_t **row_of, uint64_t *n_seq);
+int fmdh_esearch_patterns(fmd_dev_t *d, const uint64_t *row_of, uint64_t n_seq, size_t n, const fmd_esearch_hit_t *hits, const uint64_t *pat_off, uint8_t *pats);
+int fmdh_main_esearch(int argc, char *argv[]);
 int fmdh_fltuniq_auto_k(long long file_bytes);   /* the k `fltuniq` takes for an input file of that many bytes on disk (seq.c:147-150) */
 
 /* `fermi correct` (cmd.c:253-291, correct.c:305-456); defaults = cmd.c:258 */

@@ -85,6 +85,9 @@ def lib():
         L.fmdh_kmer_text.restype = vp; L.fmdh_kmer_text.argtypes = [C.c_uint64, C.c_int, vp]
         L.fmdh_kcount_print_hist.restype = None; L.fmdh_kcount_print_hist.argtypes = [vp, vp, C.c_uint32]
         L.fmdh_asearch_pattern.argtypes = [vp, C.c_uint32, vp, vp]
+        L.fmdh_esearch_cigar.restype = vp; L.fmdh_esearch_cigar.argtypes = [vp, C.c_uint32, vp, C.c_uint32, C.POINTER(C.c_uint32)]
+        L.fmdh_esearch_rankmap.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_uint64)]
+        L.fmdh_esearch_patterns.argtypes = [vp, vp, C.c_uint64, C.c_size_t, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -160,6 +163,46 @@ def asearch_pattern(query, hit):
     if lib().fmdh_asearch_pattern(q.ctypes.data, len(q), h.ctypes.data, out.ctypes.data) != 0:
         raise ValueError("asearch_pattern: a substitution list that does not fit a query of %d bases" % len(q))
     return out[:len(q)]
+
+
+ESEARCH_HIT_DT = np.dtype([("beg", "<u8"), ("cnt", "<u8"), ("query", "<u4"), ("n_edit", "<u4"), ("len", "<u4"), ("reserved", "<u4")])   # fmd_esearch_hit_t (include/fmd_hip.h)
+
+
+def esearch_cigar(query, pattern):
+    """fmdh_esearch_cigar: (cigar, n_edit) of one optimal alignment of `pattern` to `query` (both nt6; a base outside A/C/G/T equals none): run lengths
+    and '=' equal, 'X' substituted, 'I' a query base absent from the pattern, 'D' a pattern base absent from the query, from the start of both; n_edit
+    = the edit distance = the operations that are not '='.  Traced back from the end, preferring the diagonal to 'I' and 'I' to 'D'."""
+    q = np.ascontiguousarray(query, dtype=np.uint8); p = np.ascontiguousarray(pattern, dtype=np.uint8)
+    ne = C.c_uint32()
+    s = lib().fmdh_esearch_cigar(q.ctypes.data, len(q), p.ctypes.data, len(p), C.byref(ne))
+    if not s:
+        raise MemoryError("fmdh_esearch_cigar")
+    try:
+        return C.string_at(s).decode(), int(ne.value)
+    finally:
+        _libc.free(s)
+
+
+def esearch_rankmap(dev_handle):
+    """fmdh_esearch_rankmap (GPU): row_of[r] = the row whose LF-walk ends on sentinel rank r, for the index behind dev_handle (an api.DevIndex.h)."""
+    p, n = C.c_void_p(), C.c_uint64()
+    if lib().fmdh_esearch_rankmap(dev_handle, C.byref(p), C.byref(n)) != 0:
+        raise RuntimeError("fmdh_esearch_rankmap failed")
+    out = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint64)), (max(n.value, 1),))[:n.value].copy()
+    _libc.free(p)
+    return out
+
+
+def esearch_patterns(dev_handle, row_of, hits):
+    """fmdh_esearch_patterns (GPU): the patterns of esearch hits (ESEARCH_HIT_DT), read back from the index: a list of uint8 arrays (nt6)."""
+    hits = np.ascontiguousarray(hits, dtype=ESEARCH_HIT_DT)
+    row_of = np.ascontiguousarray(row_of, dtype=np.uint64)
+    off = np.zeros(len(hits) + 1, dtype=np.uint64)
+    np.cumsum(hits["len"], out=off[1:])
+    pats = np.zeros(int(off[-1]) + 1, dtype=np.uint8)
+    if len(hits) and lib().fmdh_esearch_patterns(dev_handle, row_of.ctypes.data, len(row_of), len(hits), hits.ctypes.data, off.ctypes.data, pats.ctypes.data) != 0:
+        raise RuntimeError("fmdh_esearch_patterns: hits that do not fit the index")
+    return [pats[int(off[j]):int(off[j + 1])].copy() for j in range(len(hits))]
 
 
 def kcount_hist_text(hist):

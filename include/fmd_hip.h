@@ -243,6 +243,55 @@ int fmd_asearch_dev(fmd_dev_t *h, void *stream, size_t n, const uint8_t *d_seqs,
 int fmd_asearch_batch(fmd_dev_t *h, size_t n, const uint8_t *seqs, const uint64_t *off, int max_sub, uint32_t max_hits, unsigned flags,
                       uint64_t cap, fmd_asearch_hit_t **hits, uint64_t *n_hits, uint64_t *strata, fmd_asearch_stat_t *stat);
 
+/* ---- esearch (no reference counterpart): search within max_edit edits, insertions and deletions included -------------------------------
+ * Query i is seqs[off[i] .. off[i+1]) in nt6, L bases (read byte by byte: no alignment is asked for).  A PATTERN P is a non-empty string over
+ * A/C/G/T that occurs in the index; N and '$' of the index match nothing, so a pattern never spans two sequences.  P is a HIT of the query Q at
+ * budget max_edit when the global (Levenshtein) edit distance ed(P, Q) <= max_edit, 0 <= max_edit <= FMD_ESEARCH_MAX_EDIT: a substitution, an
+ * insertion and a deletion cost 1 each, so the length of P lies in [max(1, L - max_edit), L + max_edit].  A query base outside A/C/G/T (N) equals no
+ * pattern base: it costs 1, substituted or skipped.  Every distinct pattern is ONE hit with its exact distance n_edit, however many alignments
+ * reach it.  A hit: beg, cnt = the SA interval of P (what fmd_bsearch gives for P); query; n_edit = ed(P, Q); len = the length of P; reserved = 0.
+ * The hit does not carry P: it is the first len symbols of the suffix of row beg (fmdh_esearch_patterns reads it back).  A pattern and its only
+ * extension to the left share beg and cnt and differ in len.  Per query i and stratum j = 0 .. max_edit two exact counters,
+ * strata[(i * (max_edit + 1) + j) * 2 + {0, 1}] = the hits at distance j and the sum of their cnt; they are kept whether or not hits are listed
+ * (d_hits == NULL, hit_cap == 0: count-only).  A query with more than max_hits hits is TRUNCATED: none of its hits is listed, its strata stay
+ * exact.  A query that is empty or longer than FMD_ESEARCH_MAX_LEN gives nothing and is counted in n_skipped.  stat: the fields of asearch's --
+ * n_hits, n_occ = the hits of the queries that are not truncated and the sum of their cnt; n_skipped; n_truncated; n_unfinished = items still
+ * walking after the last level; overflow != 0: a frontier entry (bit 0) or a hit (bit 1) did not fit -- it was written nowhere, the result is
+ * incomplete; n_ext = backward extensions done; widest_level = the most frontier slots a level reserved (holes included).
+ *
+ * The walk: the trie of the index rooted at the END of the pattern, level by level; level t holds the nodes of pattern
+ * length t, each with the band of the edit-distance column of its t bases against the query's suffixes of t - max_edit .. t + max_edit bases.
+ * Level 0 takes the four one-base patterns from the marginal counts.  d_lb = the bound fmd_asearch_bound_dev gives (it holds with insertions and
+ * deletions: an edit breaks at most one of the disjoint substrings that do not occur): a cell is dropped when its value + the bound of the part
+ * of the query still ahead exceeds max_edit.  Pruning changes no result; d_lb = NULL walks without it.
+ * fmd_esearch_dev: zeroes d_strata (n * (max_edit + 1) * 2 words), enqueues level 0 and exactly `levels` levels (L + max_edit - 1 finish a query
+ * of L bases: patterns of up to L + max_edit bases) on `stream` and returns: it neither allocates nor synchronises.  d_hits receives hits in
+ * no particular order, dense: those of the queries that are not truncated and max_hits of every truncated one -- n_hits + n_truncated * max_hits
+ * entries -- never more than hit_cap.  The work area is fmd_esearch_work_bytes(n, cap) bytes, 16-byte aligned; cap = the entries of each of the
+ * two frontiers, FMD_ESEARCH_MIN_CAP <= cap <= FMD_ESEARCH_MAX_CAP (0 outside); the capacity follows from work_bytes.
+ * fmd_esearch_batch: host arrays.  The bound, then parts of the query range, levels in groups until the frontier is empty; a part that overflows
+ * is discarded and its range cut in two; a single query that does not fit is retried in twice the capacity while cap = 0 allows (cap = 0: sized
+ * from the batch and the free device memory), FMD_E_OVERFLOW otherwise.  hits (may be NULL: count only; else freed with fmd_host_free): those of
+ * the queries that are not truncated, sorted by (query, n_edit, beg, len).  strata: n * (max_edit + 1) * 2 words.  The result is the same for
+ * every cap.  FMD_ESEARCH_NO_PRUNE: without the bound.  FMD_ESEARCH_BEST: only the lowest stratum of every query that has a hit -- budgets 0, 1,
+ * .. over the queries still without one; the strata above it are reported as zero.
+ * FMD_E_ARG: max_edit outside 0 .. FMD_ESEARCH_MAX_EDIT, a null pointer with n > 0, n >= 2^32, a work area too small or misaligned, a cap out of
+ * range, unknown flags.  n = 0 is a no-op.  FMD_OPEN_NO_TABLES handles work; two-base blocks are not used. */
+#define FMD_ESEARCH_MAX_EDIT 4
+#define FMD_ESEARCH_MAX_LEN 16383u
+#define FMD_ESEARCH_MIN_CAP 4096u
+#define FMD_ESEARCH_MAX_CAP (1u << 28)
+#define FMD_ESEARCH_NO_PRUNE 1u
+#define FMD_ESEARCH_BEST 2u
+typedef struct { uint64_t beg, cnt; uint32_t query, n_edit, len, reserved; } fmd_esearch_hit_t;
+typedef struct { uint64_t n_hits, n_occ, n_skipped, n_truncated, n_unfinished, overflow, n_ext, widest_level; } fmd_esearch_stat_t;
+size_t fmd_esearch_work_bytes(size_t n, uint64_t cap);
+int fmd_esearch_dev(fmd_dev_t *h, void *stream, size_t n, const uint8_t *d_seqs, const uint64_t *d_off, const uint8_t *d_lb, int max_edit,
+                    uint32_t max_hits, uint32_t levels, fmd_esearch_hit_t *d_hits, uint64_t hit_cap, uint64_t *d_strata,
+                    fmd_esearch_stat_t *d_stat, void *d_work, size_t work_bytes);
+int fmd_esearch_batch(fmd_dev_t *h, size_t n, const uint8_t *seqs, const uint64_t *off, int max_edit, uint32_t max_hits, unsigned flags,
+                      uint64_t cap, fmd_esearch_hit_t **hits, uint64_t *n_hits, uint64_t *strata, fmd_esearch_stat_t *stat);
+
 /* ---- inspection (`fermi chkbwt`, cmd.c:47-130) ------------------------------------------------
  * export: BWT[first, first+n) as nt6 bytes, decoded from the device layout (chkbwt -p).
  * check_rank: the device layout's rank of every position against the symbols themselves (chkbwt -r):
