@@ -22,6 +22,11 @@ LOCATE_STAT_DT = np.dtype([(f, "<u8") for f in ("n_runs", "n_rows", "n_skipped",
 KCOUNT_STAT_DT = np.dtype([(f, "<u8") for f in ("n_kmers", "n_total", "n_ext", "overflow", "widest_level", "n_parts", "n_retries")])  # fmd_kcount_stat_t
 KCOUNT_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32))  # fmd_kcount_sink_fn
 KCOUNT_MIN_CAP, KCOUNT_MAX_CAP = 4096, 1 << 30   # FMD_KCOUNT_MIN_CAP, FMD_KCOUNT_MAX_CAP
+KCMP_STAT_DT = np.dtype([(f, "<u8") for f in ("n_kmers", "n_total0", "n_total1", "n_only0", "n_only1", "n_shared", "n_ext", "overflow", "widest_level", "n_parts", "n_retries")])  # fmd_kcmp_stat_t
+KCMP_NODE_DT = np.dtype([("x0", "<u8", 2), ("size", "<u8", 2), ("kmer", "<u8"), ("reserved", "<u8")])  # fmd_kcmp_node_t
+KCMP_SEL_DT = np.dtype([(f, "<u4") for f in ("min0", "max0", "min1", "max1")])  # fmd_kcmp_sel_t
+KCMP_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32))  # fmd_kcmp_sink_fn
+KCMP_MIN_CAP, KCMP_MAX_CAP, KCMP_NO_MAX = 4096, 1 << 30, 0xFFFFFFFF   # FMD_KCMP_MIN_CAP, FMD_KCMP_MAX_CAP, FMD_KCMP_NO_MAX
 ASEARCH_HIT_DT = np.dtype([("beg", "<u8"), ("cnt", "<u8"), ("query", "<u4"), ("n_sub", "<u4"), ("sub", "<u2", 4)])  # fmd_asearch_hit_t
 ASEARCH_STAT_DT = np.dtype([(f, "<u8") for f in ("n_hits", "n_occ", "n_skipped", "n_truncated", "n_unfinished", "overflow", "n_ext", "widest_level")])  # fmd_asearch_stat_t
 ASEARCH_MAX_SUB, ASEARCH_MAX_LEN, ASEARCH_MIN_CAP, ASEARCH_MAX_CAP = 4, 16383, 4096, 1 << 28   # FMD_ASEARCH_*
@@ -60,6 +65,7 @@ ABI_SYMBOLS = [
     "fmd_multi_bsearch_work_bytes", "fmd_multi_bsearch_dev", "fmd_multi_bsearch_batch",
     "fmd_locate_work_bytes", "fmd_locate_dev", "fmd_locate_batch",
     "fmd_kcount_work_bytes", "fmd_kcount_part_dev", "fmd_kcount",
+    "fmd_kcmp_work_bytes", "fmd_kcmp_part_dev", "fmd_kcmp",
     "fmd_asearch_work_bytes", "fmd_asearch_bound_dev", "fmd_asearch_dev", "fmd_asearch_batch",
     "fmd_esearch_work_bytes", "fmd_esearch_dev", "fmd_esearch_batch",
 ]
@@ -147,6 +153,9 @@ def _configure(L):
     L.fmd_kcount_work_bytes.restype = sz; L.fmd_kcount_work_bytes.argtypes = [C.c_uint64]
     L.fmd_kcount_part_dev.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, sz, vp, C.c_uint64, C.c_uint32, u64p, u64p, vp, C.c_uint64, vp, vp, sz]
     L.fmd_kcount.argtypes = [vp, C.c_int, C.c_int, C.c_uint32, u64p, C.c_uint64, vp, vp, vp]
+    L.fmd_kcmp_work_bytes.restype = sz; L.fmd_kcmp_work_bytes.argtypes = [C.c_uint64]
+    L.fmd_kcmp_part_dev.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int, sz, vp, C.c_uint64, C.c_uint32, u64p, u64p, u64p, C.c_uint64, vp, vp, sz]
+    L.fmd_kcmp.argtypes = [vp, vp, C.c_int, vp, C.c_uint32, u64p, C.c_uint64, vp, vp, vp]
     L.fmd_asearch_work_bytes.restype = sz; L.fmd_asearch_work_bytes.argtypes = [sz, C.c_uint64]
     L.fmd_asearch_bound_dev.argtypes = [vp, vp, sz, vp, u64p, vp]
     L.fmd_asearch_dev.argtypes = [vp, vp, sz, vp, u64p, vp, C.c_int, C.c_uint32, C.c_uint32, vp, C.c_uint64, u64p, vp, vp, sz]
@@ -501,6 +510,41 @@ class DevIndex:
 
         _, stat = self._kcount(k, min_occ, 2, cap, sink)
         return (np.concatenate(ks) if ks else np.zeros(0, np.uint64)), (np.concatenate(cs) if cs else np.zeros(0, np.uint32)), stat
+
+    def _kcmp(self, other, k, sel, n_bins, cap, sink):
+        hist = np.zeros(max(int(n_bins), 0) ** 2, dtype=np.uint64)
+        stat = np.zeros(1, dtype=KCMP_STAT_DT)
+        s = np.zeros(1, dtype=KCMP_SEL_DT)
+        s[0] = tuple(KCMP_NO_MAX if v is None else int(v) for v in sel)
+        cb = KCMP_SINK(sink) if sink is not None else None
+        check(lib().fmd_kcmp(self.h, other.h, int(k), _ptr(s), int(n_bins), _ptr(hist) if len(hist) else None, int(cap),
+                             C.cast(cb, C.c_void_p) if cb is not None else None, None, _ptr(stat)))
+        return hist.reshape(max(int(n_bins), 0), -1), {f: int(stat[0][f]) for f in KCMP_STAT_DT.names}
+
+    def kmer_compare_spectrum(self, other, k, sel=(0, None, 0, None), n_bins=256, cap=0):
+        """fmd_kcmp without a sink: (hist2d, stat), the joint counts of the canonical k-mers (1 <= k <= 32) of this index (c0) and `other` (c1), both of
+        both strands.  sel = (min0, max0, min1, max1), None or KCMP_NO_MAX = no upper bound: a k-mer is reported iff c0 + c1 >= 1, min0 <= c0 <= max0 and
+        min1 <= c1 <= max1.  hist2d[min(c0, n_bins - 1), min(c1, n_bins - 1)] = the reported k-mers there (2 <= n_bins <= 1024), hist2d[0, 0] = 0.  stat:
+        the fields of KCMP_STAT_DT (n_kmers, n_total0, n_total1, n_only0, n_only1, n_shared, n_ext, widest_level, n_parts, n_retries, ..).  cap: the
+        frontier capacity of a part in entries (KCMP_MIN_CAP ..; 0 = sized from the indexes and the free device memory); the result does not depend on it."""
+        return self._kcmp(other, k, sel, n_bins, cap, None)
+
+    def kmer_compare(self, other, k, sel=(0, None, 0, None), cap=0, slices=None):
+        """fmd_kcmp with a sink: (kmers uint64[], c0 uint32[], c1 uint32[], stat), the reported canonical k-mers (kmer_compare_spectrum) ascending with
+        their counts in this index and in `other`; a count saturates at 2^32 - 1.  slices: a list that receives the length of every slice the sink was handed."""
+        ks, a0, a1 = [], [], []
+
+        def sink(ctx, n, kmer, c0, c1):
+            ks.append(np.ctypeslib.as_array(kmer, (n,)).astype(np.uint64, copy=True))
+            a0.append(np.ctypeslib.as_array(c0, (n,)).astype(np.uint32, copy=True))
+            a1.append(np.ctypeslib.as_array(c1, (n,)).astype(np.uint32, copy=True))
+            if slices is not None:
+                slices.append(int(n))
+            return 0
+
+        _, stat = self._kcmp(other, k, sel, 2, cap, sink)
+        cat = lambda xs, dt: np.concatenate(xs) if xs else np.zeros(0, dt)
+        return cat(ks, np.uint64), cat(a0, np.uint32), cat(a1, np.uint32), stat
 
     def approx_search(self, seqs, max_sub=1, max_hits=1000, best=False, prune=True, cap=0, count_only=False, with_stat=False):
         """fmd_asearch_batch: the patterns within max_sub substitutions (0 .. ASEARCH_MAX_SUB; no insertions or deletions) of every query that occur

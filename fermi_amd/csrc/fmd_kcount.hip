@@ -59,14 +59,6 @@ __global__ __launch_bounds__(64) void k_kcount_level(FmdIndexView ix, int d, uin
     km_level_step(ix, fmd_lds, d, min_occ, in, out, cap, ch, ctr, KC_OVF, KC_EXT, xcd_aware);
 }
 
-// reverse complement of the k-mer in the low 2k bits of w: complement, reverse the 2-bit groups, shift the k groups down
-__device__ __forceinline__ uint64_t kc_revcomp(uint64_t w, int k)
-{
-    uint64_t x = __brevll(~w);                        // the groups reversed, and the two bits of every group swapped
-    x = ((x >> 1) & 0x5555555555555555ull) | ((x & 0x5555555555555555ull) << 1);
-    return x >> (64 - 2 * k);
-}
-
 // the staged pairs -> the list (all 64 lanes together): ONE atomic for `fill` dense slots, stores of consecutive lanes side by side
 __device__ __forceinline__ void kc_flush_pairs(const uint64_t *ek, const uint32_t *ec, uint32_t &fill, unsigned long long *ctr, uint64_t *o_kmer, uint32_t *o_count,
                                                uint64_t out_cap)

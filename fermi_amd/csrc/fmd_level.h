@@ -136,6 +136,14 @@ __device__ __forceinline__ uint64_t km_wave_sum(uint64_t v)
     return v;
 }
 
+// reverse complement of the k-mer in the low 2k bits of w (kcount, kcmp): complement, reverse the 2-bit groups, shift the k groups down
+__device__ __forceinline__ uint64_t kc_revcomp(uint64_t w, int k)
+{
+    uint64_t x = __brevll(~w);                        // the groups reversed, and the two bits of every group swapped
+    x = ((x >> 1) & 0x5555555555555555ull) | ((x & 0x5555555555555555ull) << 1);
+    return x >> (64 - 2 * k);
+}
+
 // One level of a k-mer trie walk (the harvest, fmd_kmer.hip; kcount, fmd_kcount.hip): the nodes of `in` at depth d -- bi-intervals whose info
 // word K holds the d bases, the rightmost in the lowest two bits -- get one backward extension each, and the children A/C/G/T with at least thr
 // occurrences go to `out` with the new base at bits 2d of K.  Counters, words of ctr: [d] = the entries of `in` (more than cap when that level

@@ -387,6 +387,12 @@ int fmdh_main_locate(int argc, char *argv[]);
 char *fmdh_kmer_text(uint64_t kmer, int k, char *buf);
 void fmdh_kcount_print_hist(FILE *out, const uint64_t *hist, uint32_t n_bins);
 int fmdh_main_kcount(int argc, char *argv[]);
+/* kcmp_cmd.c: `fermi-amd kcmp [-k 21] [-a 0] [-A inf] [-b 0] [-B inf] [-n 256] [-d] [-g GPU] <a.fmd> <b.fmd>`: the joint k-mer counts of two indexes (fmd_kcmp):
+ * c0 <tab> c1 <tab> n_kmers per non-empty cell of the 2-D histogram, or with -d the selected canonical k-mers with both counts, streamed; usage and
+ * unreadable-file errors return 1 before the device is looked for.  No GPU behind:
+ * fmdh_kcmp_print_hist: one line per non-empty cell of the n_bins x n_bins row-major histogram, in row-major order; a label of n_bins - 1 stands for "that many or more" */
+void fmdh_kcmp_print_hist(FILE *out, const uint64_t *hist, uint32_t n_bins);
+int fmdh_main_kcmp(int argc, char *argv[]);
 /* asearch_cmd.c: `fermi-amd asearch [-g GPU] [-d 1] [-b] [-m 1000] [-l] [-M 1000] [-r reads.rank] <reads.fmd> <query.fa>`: the patterns within -d substitutions of
  * every query that occur (fmd_asearch_batch), with -l the reads that hold each (fmd_locate_batch + fmdh_locate_hits); usage and unreadable-file errors return 1
  * before the device is looked for.  No GPU behind:

@@ -84,6 +84,7 @@ def lib():
         L.fmdh_locate_hits.argtypes = [vp, C.c_uint64, vp, C.c_uint64, C.POINTER(vp), C.POINTER(C.c_uint64)]
         L.fmdh_kmer_text.restype = vp; L.fmdh_kmer_text.argtypes = [C.c_uint64, C.c_int, vp]
         L.fmdh_kcount_print_hist.restype = None; L.fmdh_kcount_print_hist.argtypes = [vp, vp, C.c_uint32]
+        L.fmdh_kcmp_print_hist.restype = None; L.fmdh_kcmp_print_hist.argtypes = [vp, vp, C.c_uint32]
         L.fmdh_asearch_pattern.argtypes = [vp, C.c_uint32, vp, vp]
         L.fmdh_esearch_cigar.restype = vp; L.fmdh_esearch_cigar.argtypes = [vp, C.c_uint32, vp, C.c_uint32, C.POINTER(C.c_uint32)]
         L.fmdh_esearch_rankmap.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_uint64)]
@@ -212,6 +213,19 @@ def kcount_hist_text(hist):
     with tempfile.NamedTemporaryFile() as tf:
         fp = _libc.fopen(tf.name.encode(), b"wb")
         lib().fmdh_kcount_print_hist(fp, hist.ctypes.data, len(hist))
+        _libc.fclose(fp)
+        return open(tf.name).read()
+
+
+def kcmp_hist_text(hist2d):
+    """fmdh_kcmp_print_hist: the lines `fermi-amd kcmp` prints for a square 2-D histogram (c0 <tab> c1 <tab> n_kmers per non-empty cell, row-major), as one str."""
+    import tempfile
+    hist2d = np.ascontiguousarray(hist2d, dtype=np.uint64)
+    if hist2d.ndim != 2 or hist2d.shape[0] != hist2d.shape[1]:
+        raise ValueError("kcmp_hist_text: the histogram is not square")
+    with tempfile.NamedTemporaryFile() as tf:
+        fp = _libc.fopen(tf.name.encode(), b"wb")
+        lib().fmdh_kcmp_print_hist(fp, hist2d.ctypes.data, hist2d.shape[0])
         _libc.fclose(fp)
         return open(tf.name).read()
 

@@ -192,6 +192,53 @@ int fmd_kcount_part_dev(fmd_dev_t *h, void *stream, int k, int min_occ, int root
 int fmd_kcount(fmd_dev_t *h, int k, int min_occ, uint32_t n_bins, uint64_t *hist, uint64_t cap, fmd_kcount_sink_fn sink, void *ctx,
                fmd_kcount_stat_t *stat);
 
+/* ---- kcmp (no reference counterpart): the joint k-mer counts of TWO indexes of both strands ---------------------------------------
+ * k, a k-mer, its packed and its canonical form are kcount's (above), 1 <= k <= 32.  c_i(W) = kcount's COUNT of W in index i: occ_i(W), halved
+ * when W = rc(W).  A selection is four bounds, min <= max on each side, a max of 0xffffffff = no upper bound; a canonical k-mer is REPORTED iff
+ * c0 + c1 >= 1, min0 <= c0 <= max0 and min1 <= c1 <= max1, tested on the exact counts.  Histogram, list and sums cover the reported k-mers and
+ * nothing else.  The walk is the trie of the k-mers of both indexes, level by level, a node = one suffix's interval (start, size) in each
+ * index; an inner node is DROPPED iff occ0 < min0, or occ1 < min1, or occ0 = occ1 = 0.  That is exact: a count never exceeds the occ of a
+ * suffix of the k-mer, and a palindrome's occ is at least its count.  Upper bounds prune nothing.  A side whose interval is empty is never
+ * fetched again: from there the node walks in the other index alone.
+ * Histogram: n_bins per axis, 2 <= n_bins <= 1024, row-major: hist[min(c0, n_bins - 1) * n_bins + min(c1, n_bins - 1)] = the reported k-mers
+ * there; hist[0] = 0.  List: (kmer, c0, c1), both counts uint32_t that SATURATE at 2^32 - 1 (histogram and sums use the exact counts),
+ * ascending by k-mer over the whole run, no k-mer twice.  stat: n_kmers = k-mers reported, n_total0 / n_total1 = the sums of their counts
+ * (the selection of everything: the N-free k-windows of each set), n_only0 = those with c1 = 0, n_only1 = those with c0 = 0, n_shared = those
+ * with both >= 1, n_ext = backward extensions done, one per (node, non-empty side), discarded parts included, overflow (the _dev form),
+ * widest_level = the most frontier slots a level reserved (holes included), n_parts = parts run, n_retries = parts discarded.
+ * Handles: both on one device; each passes kcount's test of both strands; the same handle may be given twice; FMD_OPEN_NO_TABLES handles
+ * work; a handle of an empty index (FMD_OPEN_EMPTY_OK) is a side on which every count is 0.  Two-base blocks are not used.
+ *
+ * fmd_kcmp_part_dev: one part, for k >= 2.  d_roots = n_roots <= cap nodes, 16-byte aligned, of suffixes of ONE length root_len (1 <= root_len <
+ * k; kmer = the packed suffix; size 0 on both sides = skipped); every k-mer W that ends in one of them is walked, kept iff rc(W) <= W and the
+ * selection holds, ADDED to d_hist (n_bins x n_bins words the caller zeroes) and -- d_kmer != NULL -- stored as rc(W) in d_kmer and c0 | c1 << 32
+ * (saturated) in d_c01, dense, in no particular order, out_cap entries at most (d_kmer == NULL: no list, out_cap is ignored).  cap = the
+ * entries of each of the two frontiers the work area (fmd_kcmp_work_bytes(cap), 16-byte aligned) holds, FMD_KCMP_MIN_CAP <= cap <=
+ * FMD_KCMP_MAX_CAP (work_bytes returns 0 outside).  When a frontier entry or a list entry does not fit, d_stat->overflow = 1, nothing is
+ * written past either, and histogram, list and sums are incomplete: discard them.  Enqueues on `stream` and returns: it neither allocates
+ * nor synchronises.
+ * fmd_kcmp: both indexes whole.  Parts start from the single-base roots in the order of rc(suffix); one that overflows is discarded whole and
+ * its run of roots cut in two, a single root replaced by its children one base deeper (fmd_extend_batch on each index; those the pruning rule
+ * drops are dropped).  sink == NULL: the histogram and the sums only.  Otherwise every part's list is sorted on the device and handed to
+ * sink(ctx, n, kmer, c0, c1) -- host arrays that live until it returns -- as consecutive slices; a non-zero return stops the run (FMD_E_IO).
+ * cap = 0: sized from the indexes and the free device memory, grown after an overflow while it fits; the list of a part has room for cap
+ * entries.  The large buffers stay in h0's cache between calls (fmd_dev_trim).  Histogram, list and sums are the same for every cap.  k = 1 is
+ * answered from the marginal counts.  FMD_E_ARG: k outside 1..32 (the part entry: 2..32), n_bins outside 2..1024, min > max, a cap outside the
+ * range, a null handle, handles on different devices, a handle that fails the strand test, a work area that is too small. */
+#define FMD_KCMP_MIN_CAP 4096u
+#define FMD_KCMP_MAX_CAP (1u << 30)
+#define FMD_KCMP_NO_MAX 0xffffffffu
+typedef struct { uint32_t min0, max0, min1, max1; } fmd_kcmp_sel_t;
+typedef struct { uint64_t x0[2], size[2], kmer, reserved; } fmd_kcmp_node_t;   /* 48 bytes: one suffix's interval start and size in each index; size 0 on both = skipped */
+typedef struct { uint64_t n_kmers, n_total0, n_total1, n_only0, n_only1, n_shared, n_ext, overflow, widest_level, n_parts, n_retries; } fmd_kcmp_stat_t;
+typedef int (*fmd_kcmp_sink_fn)(void *ctx, uint64_t n, const uint64_t *kmer, const uint32_t *c0, const uint32_t *c1);
+size_t fmd_kcmp_work_bytes(uint64_t cap);                     /* 0 outside FMD_KCMP_MIN_CAP..FMD_KCMP_MAX_CAP */
+int fmd_kcmp_part_dev(fmd_dev_t *h0, fmd_dev_t *h1, void *stream, int k, const fmd_kcmp_sel_t *sel, int root_len, size_t n_roots,
+                      const fmd_kcmp_node_t *d_roots, uint64_t cap, uint32_t n_bins, uint64_t *d_hist, uint64_t *d_kmer, uint64_t *d_c01,
+                      uint64_t out_cap, fmd_kcmp_stat_t *d_stat, void *d_work, size_t work_bytes);
+int fmd_kcmp(fmd_dev_t *h0, fmd_dev_t *h1, int k, const fmd_kcmp_sel_t *sel, uint32_t n_bins, uint64_t *hist, uint64_t cap,
+             fmd_kcmp_sink_fn sink, void *ctx, fmd_kcmp_stat_t *stat);
+
 /* ---- asearch (no reference counterpart): search with up to max_sub substitutions ---------------------------------------------------
  * Query i is seqs[off[i] .. off[i+1]) in nt6, L bases (the contract of fmd_bsearch_dev: the bytes 4-byte aligned and readable to the next
  * multiple of 4).  A PATTERN P is a string over A/C/G/T of length L; it is a HIT of the query when occ(P) > 0 and P differs from the query in
