@@ -27,6 +27,8 @@ KCMP_NODE_DT = np.dtype([("x0", "<u8", 2), ("size", "<u8", 2), ("kmer", "<u8"), 
 KCMP_SEL_DT = np.dtype([(f, "<u4") for f in ("min0", "max0", "min1", "max1")])  # fmd_kcmp_sel_t
 KCMP_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32))  # fmd_kcmp_sink_fn
 KCMP_MIN_CAP, KCMP_MAX_CAP, KCMP_NO_MAX = 4096, 1 << 30, 0xFFFFFFFF   # FMD_KCMP_MIN_CAP, FMD_KCMP_MAX_CAP, FMD_KCMP_NO_MAX
+KPROFILE_STAT_DT = np.dtype([(f, "<u8") for f in ("n_windows", "n_valid", "n_hit", "n_ext", "n_table")])  # fmd_kprofile_stat_t
+KPROFILE_MAX_K, KPROFILE_PLAIN = 255, 1   # FMD_KPROFILE_MAX_K, FMD_KPROFILE_PLAIN
 ASEARCH_HIT_DT = np.dtype([("beg", "<u8"), ("cnt", "<u8"), ("query", "<u4"), ("n_sub", "<u4"), ("sub", "<u2", 4)])  # fmd_asearch_hit_t
 ASEARCH_STAT_DT = np.dtype([(f, "<u8") for f in ("n_hits", "n_occ", "n_skipped", "n_truncated", "n_unfinished", "overflow", "n_ext", "widest_level")])  # fmd_asearch_stat_t
 ASEARCH_MAX_SUB, ASEARCH_MAX_LEN, ASEARCH_MIN_CAP, ASEARCH_MAX_CAP = 4, 16383, 4096, 1 << 28   # FMD_ASEARCH_*
@@ -66,6 +68,7 @@ ABI_SYMBOLS = [
     "fmd_locate_work_bytes", "fmd_locate_dev", "fmd_locate_batch",
     "fmd_kcount_work_bytes", "fmd_kcount_part_dev", "fmd_kcount",
     "fmd_kcmp_work_bytes", "fmd_kcmp_part_dev", "fmd_kcmp",
+    "fmd_kprofile_dev", "fmd_kprofile_batch",
     "fmd_asearch_work_bytes", "fmd_asearch_bound_dev", "fmd_asearch_dev", "fmd_asearch_batch",
     "fmd_esearch_work_bytes", "fmd_esearch_dev", "fmd_esearch_batch",
 ]
@@ -156,6 +159,8 @@ def _configure(L):
     L.fmd_kcmp_work_bytes.restype = sz; L.fmd_kcmp_work_bytes.argtypes = [C.c_uint64]
     L.fmd_kcmp_part_dev.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int, sz, vp, C.c_uint64, C.c_uint32, u64p, u64p, u64p, C.c_uint64, vp, vp, sz]
     L.fmd_kcmp.argtypes = [vp, vp, C.c_int, vp, C.c_uint32, u64p, C.c_uint64, vp, vp, vp]
+    L.fmd_kprofile_dev.argtypes = [vp, vp, sz, vp, u64p, u64p, C.c_int, C.c_uint, vp, vp]
+    L.fmd_kprofile_batch.argtypes = [vp, sz, vp, u64p, C.c_int, C.c_uint, u64p, C.POINTER(vp), vp]
     L.fmd_asearch_work_bytes.restype = sz; L.fmd_asearch_work_bytes.argtypes = [sz, C.c_uint64]
     L.fmd_asearch_bound_dev.argtypes = [vp, vp, sz, vp, u64p, vp]
     L.fmd_asearch_dev.argtypes = [vp, vp, sz, vp, u64p, vp, C.c_int, C.c_uint32, C.c_uint32, vp, C.c_uint64, u64p, vp, vp, sz]
@@ -545,6 +550,25 @@ class DevIndex:
         _, stat = self._kcmp(other, k, sel, 2, cap, sink)
         cat = lambda xs, dt: np.concatenate(xs) if xs else np.zeros(0, dt)
         return cat(ks, np.uint64), cat(a0, np.uint32), cat(a1, np.uint32), stat
+
+    def kmer_profile(self, seqs, k, flags=0, with_stat=False):
+        """fmd_kprofile_batch: (counts uint32[], woff uint64[n + 1][, stat]).  Window j of sequence i -- its bases [j, j + k), 1 <= k <= KPROFILE_MAX_K --
+        has counts[woff[i] + j] = kcount's COUNT of its k-mer: occ on the index of both strands, halved for a k-mer that is its own reverse complement,
+        saturated at 2^32 - 1, and 0 for a window with a base outside A/C/G/T.  flags: 0 = the library chooses the path, KPROFILE_PLAIN = the plain
+        path (the only one there is).  stat: the fields of KPROFILE_STAT_DT as a dict.  An index of one strand only raises FmdError."""
+        flat, off = flatten_reads(seqs)
+        n = len(off) - 1
+        woff = np.zeros(n + 1, dtype=np.uint64)
+        stat = np.zeros(1, dtype=KPROFILE_STAT_DT)
+        p = C.c_void_p()
+        check(lib().fmd_kprofile_batch(self.h, n, _ptr(flat), _ptr(off), int(k), int(flags), _ptr(woff), C.byref(p), _ptr(stat)))
+        counts = np.zeros(int(woff[n]), dtype=np.uint32)
+        if p.value:
+            C.memmove(_ptr(counts), p.value, counts.nbytes)
+        lib().fmd_host_free(p)
+        if with_stat:
+            return counts, woff, {f: int(stat[0][f]) for f in KPROFILE_STAT_DT.names}
+        return counts, woff
 
     def approx_search(self, seqs, max_sub=1, max_hits=1000, best=False, prune=True, cap=0, count_only=False, with_stat=False):
         """fmd_asearch_batch: the patterns within max_sub substitutions (0 .. ASEARCH_MAX_SUB; no insertions or deletions) of every query that occur

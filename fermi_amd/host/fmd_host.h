@@ -393,6 +393,22 @@ int fmdh_main_kcount(int argc, char *argv[]);
  * fmdh_kcmp_print_hist: one line per non-empty cell of the n_bins x n_bins row-major histogram, in row-major order; a label of n_bins - 1 stands for "that many or more" */
 void fmdh_kcmp_print_hist(FILE *out, const uint64_t *hist, uint32_t n_bins);
 int fmdh_main_kcmp(int argc, char *argv[]);
+/* kprofile_cmd.c: `fermi-amd kprofile [-k 21] [-s] [-q] [-g GPU] <queries.fa> <a.fmd> [<b.fmd> ...]`: the count of the k-mer at every position of every query
+ * sequence in the reads of every index (fmd_kprofile_batch); usage and unreadable-file errors return 1 before the device is looked for.
+ * fmdh_kprofile_run: the command behind its argument checks -- the queries of query_fn in batches of about batch_bases bases (0 = the command's 64 MB; a longer
+ * sequence is a batch of its own), every batch against the n_idx open handles, printed to out; mode 0 = KP lines, 's' = KS lines, 'q' = FASTQ (n_idx = 1).
+ * No GPU behind:
+ * fmdh_kprofile_print_kp: the line KP <tab> idx <tab> c_0,c_1,.. of one sequence's n_windows counts; * for none
+ * fmdh_kprofile_print_ks: the line KS <tab> idx <tab> n_valid <tab> n_zero <tab> min <tab> median <tab> max <tab> mean over the counts of the windows of the
+ *   sequence (nt6, len bases) that hold only A/C/G/T; median = element (n_valid - 1) / 2 of the sorted counts, mean as %.3f, the last four * when n_valid = 0;
+ *   1 without memory
+ * fmdh_kprofile_qual: qual[p] = 33 + min(93, the largest count among the windows [j, j + k) that cover base p; 0 where none does), len characters and a NUL;
+ *   count = the len - k + 1 counts of the sequence (not read when len < k); 1 without memory */
+void fmdh_kprofile_print_kp(FILE *out, int idx, const uint32_t *count, uint64_t n_windows);
+int fmdh_kprofile_print_ks(FILE *out, int idx, const uint8_t *nt6, uint64_t len, int k, const uint32_t *count);
+int fmdh_kprofile_qual(const uint32_t *count, uint64_t len, int k, char *qual);
+int fmdh_kprofile_run(FILE *out, const char *query_fn, int n_idx, fmd_dev_t *const *idx, int k, int mode, size_t batch_bases);
+int fmdh_main_kprofile(int argc, char *argv[]);
 /* asearch_cmd.c: `fermi-amd asearch [-g GPU] [-d 1] [-b] [-m 1000] [-l] [-M 1000] [-r reads.rank] <reads.fmd> <query.fa>`: the patterns within -d substitutions of
  * every query that occur (fmd_asearch_batch), with -l the reads that hold each (fmd_locate_batch + fmdh_locate_hits); usage and unreadable-file errors return 1
  * before the device is looked for.  No GPU behind:

@@ -85,6 +85,10 @@ def lib():
         L.fmdh_kmer_text.restype = vp; L.fmdh_kmer_text.argtypes = [C.c_uint64, C.c_int, vp]
         L.fmdh_kcount_print_hist.restype = None; L.fmdh_kcount_print_hist.argtypes = [vp, vp, C.c_uint32]
         L.fmdh_kcmp_print_hist.restype = None; L.fmdh_kcmp_print_hist.argtypes = [vp, vp, C.c_uint32]
+        L.fmdh_kprofile_print_kp.restype = None; L.fmdh_kprofile_print_kp.argtypes = [vp, C.c_int, vp, C.c_uint64]
+        L.fmdh_kprofile_print_ks.argtypes = [vp, C.c_int, vp, C.c_uint64, C.c_int, vp]
+        L.fmdh_kprofile_qual.argtypes = [vp, C.c_uint64, C.c_int, vp]
+        L.fmdh_kprofile_run.argtypes = [vp, C.c_char_p, C.c_int, vp, C.c_int, C.c_int, C.c_size_t]
         L.fmdh_asearch_pattern.argtypes = [vp, C.c_uint32, vp, vp]
         L.fmdh_esearch_cigar.restype = vp; L.fmdh_esearch_cigar.argtypes = [vp, C.c_uint32, vp, C.c_uint32, C.POINTER(C.c_uint32)]
         L.fmdh_esearch_rankmap.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_uint64)]
@@ -228,6 +232,58 @@ def kcmp_hist_text(hist2d):
         lib().fmdh_kcmp_print_hist(fp, hist2d.ctypes.data, hist2d.shape[0])
         _libc.fclose(fp)
         return open(tf.name).read()
+
+
+def _printed(call):
+    """what call(FILE *) writes, as one str"""
+    import tempfile
+    with tempfile.NamedTemporaryFile() as tf:
+        fp = _libc.fopen(tf.name.encode(), b"wb")
+        try:
+            call(fp)
+        finally:
+            _libc.fclose(fp)
+        return open(tf.name).read()
+
+
+def kprofile_kp_text(idx, counts):
+    """fmdh_kprofile_print_kp: the line `fermi-amd kprofile` prints for one sequence's counts in index idx (KP <tab> idx <tab> c_0,c_1,..; * for no window)."""
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    return _printed(lambda fp: lib().fmdh_kprofile_print_kp(fp, int(idx), counts.ctypes.data if len(counts) else None, len(counts)))
+
+
+def kprofile_ks_text(idx, seq, k, counts):
+    """fmdh_kprofile_print_ks: the line `kprofile -s` prints for one sequence (nt6) and its len - k + 1 counts in index idx: KS <tab> idx <tab> n_valid
+    <tab> n_zero <tab> min <tab> median <tab> max <tab> mean over the windows without an N; median = the lower one, the last four * when n_valid = 0."""
+    seq = np.ascontiguousarray(seq, dtype=np.uint8); counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    if len(counts) != max(0, len(seq) - int(k) + 1):
+        raise ValueError("kprofile_ks_text: %d counts for %d bases and k = %d" % (len(counts), len(seq), k))
+    def call(fp):
+        if lib().fmdh_kprofile_print_ks(fp, int(idx), seq.ctypes.data if len(seq) else None, len(seq), int(k), counts.ctypes.data if len(counts) else None) != 0:
+            raise MemoryError("fmdh_kprofile_print_ks")
+    return _printed(call)
+
+
+def kprofile_qual_text(length, k, counts):
+    """fmdh_kprofile_qual: the quality line `kprofile -q` prints for a sequence of `length` bases and its length - k + 1 counts: per base the character
+    33 + min(93, the largest count among the windows that cover it), 33 where no window does."""
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    if len(counts) != max(0, int(length) - int(k) + 1):
+        raise ValueError("kprofile_qual_text: %d counts for %d bases and k = %d" % (len(counts), length, k))
+    buf = C.create_string_buffer(int(length) + 1)
+    if lib().fmdh_kprofile_qual(counts.ctypes.data if len(counts) else None, int(length), int(k), buf) != 0:
+        raise MemoryError("fmdh_kprofile_qual")
+    return buf.value.decode()
+
+
+def kprofile_run(query_path, dev_handles, k, mode="", batch_bases=0):
+    """fmdh_kprofile_run (GPU): what `fermi-amd kprofile` prints for the queries of query_path against the open indexes (api.DevIndex.h each), as one str;
+    mode "" = KP lines, "s" = KS lines, "q" = FASTQ (one index); batch_bases = the bases of a batch of queries (0 = the command's 64 MB)."""
+    hs = (C.c_void_p * len(dev_handles))(*dev_handles)
+    def call(fp):
+        if lib().fmdh_kprofile_run(fp, query_path.encode(), len(dev_handles), hs, int(k), ord(mode) if mode else 0, int(batch_bases)) != 0:
+            raise RuntimeError("fmdh_kprofile_run failed")
+    return _printed(call)
 
 
 _libc = C.CDLL(None)

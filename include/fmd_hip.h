@@ -239,6 +239,33 @@ int fmd_kcmp_part_dev(fmd_dev_t *h0, fmd_dev_t *h1, void *stream, int k, const f
 int fmd_kcmp(fmd_dev_t *h0, fmd_dev_t *h1, int k, const fmd_kcmp_sel_t *sel, uint32_t n_bins, uint64_t *hist, uint64_t cap,
              fmd_kcmp_sink_fn sink, void *ctx, fmd_kcmp_stat_t *stat);
 
+/* ---- kprofile (no reference counterpart): kcount's COUNT of every k-window of the query sequences -------------------------------------
+ * Sequence i is seqs[off[i] .. off[i+1]) in nt6 (the contract of fmd_bsearch_dev: the bytes 4-byte aligned and readable to the next multiple
+ * of 4).  Window j of sequence i is its bases [j, j + k), 0 <= j <= len_i - k: nw_i = max(0, len_i - k + 1) windows, woff[0] = 0, woff[i+1] =
+ * woff[i] + nw_i, and window j of sequence i writes count[woff[i] + j].  count = kcount's COUNT of the window's k-mer (above): occ(W) on the
+ * index of both strands, halved when W = rc(W) -- which is seen from the window's bases --, uint32_t, SATURATED at 2^32 - 1; 0 for a window
+ * with any base outside A/C/G/T, for which no search is made (an N never matches an N).  For k <= 32 it is the number `kcount -d -o1` prints
+ * for that k-mer, or 0 when kcount does not list it.  1 <= k <= FMD_KPROFILE_MAX_K: nothing is packed, so k > 32 is ordinary; the bound is the
+ * bytes one sequence's windows in a wave may take in that wave's LDS.  flags: 0 = the library chooses the path, FMD_KPROFILE_PLAIN = one lane per
+ * window, one rank pair per base behind the prefix table.  That is the only path: a second one, which searched the bases that G consecutive
+ * windows share once and grew that bi-interval at both ends, was built, measured and lost everywhere -- it is not in
+ * the library, and its flag (2u) is refused like every other bit.
+ * stat (ADDED to: the caller zeroes it): n_windows = windows written, n_valid = those free of N, n_hit = those with count >= 1, n_ext = rank
+ * pairs requested, n_table = windows that started from the prefix table.
+ * fmd_kprofile_dev enqueues on `stream` and returns: it neither allocates nor synchronises, and it does not validate d_woff (n + 1 words, as
+ * defined above for this k; d_count has room for d_woff[n] words).  d_stat may be NULL.  fmd_kprofile_batch writes woff (n + 1 words) itself
+ * and returns the counts in *count (malloc'ed: fmd_host_free); with n = 0 or no window at all woff is still written and *count is NULL.
+ * FMD_E_ARG: k out of range, unknown flags, a null pointer with n > 0, n >= 2^32, or a handle that fails kcount's test of both strands (a
+ * necessary sign, NOT a sufficient one: a one-strand index that passes it gets counts that mean nothing).  FMD_OPEN_NO_TABLES handles work
+ * (every search starts from its last base); a handle of an empty index (FMD_OPEN_EMPTY_OK) gives all zeros.  Two-base blocks are not used. */
+#define FMD_KPROFILE_MAX_K 255
+#define FMD_KPROFILE_PLAIN  1u
+typedef struct { uint64_t n_windows, n_valid, n_hit, n_ext, n_table; } fmd_kprofile_stat_t;
+int fmd_kprofile_dev(fmd_dev_t *h, void *stream, size_t n, const uint8_t *d_seqs, const uint64_t *d_off, const uint64_t *d_woff,
+                     int k, unsigned flags, uint32_t *d_count, fmd_kprofile_stat_t *d_stat /* may be NULL; the caller zeroes it */);
+int fmd_kprofile_batch(fmd_dev_t *h, size_t n, const uint8_t *seqs, const uint64_t *off, int k, unsigned flags,
+                       uint64_t *woff /* n + 1, written */, uint32_t **count /* fmd_host_free */, fmd_kprofile_stat_t *stat);
+
 /* ---- asearch (no reference counterpart): search with up to max_sub substitutions ---------------------------------------------------
  * Query i is seqs[off[i] .. off[i+1]) in nt6, L bases (the contract of fmd_bsearch_dev: the bytes 4-byte aligned and readable to the next
  * multiple of 4).  A PATTERN P is a string over A/C/G/T of length L; it is a HIT of the query when occ(P) > 0 and P differs from the query in
