@@ -27,6 +27,11 @@ KCMP_NODE_DT = np.dtype([("x0", "<u8", 2), ("size", "<u8", 2), ("kmer", "<u8"), 
 KCMP_SEL_DT = np.dtype([(f, "<u4") for f in ("min0", "max0", "min1", "max1")])  # fmd_kcmp_sel_t
 KCMP_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32))  # fmd_kcmp_sink_fn
 KCMP_MIN_CAP, KCMP_MAX_CAP, KCMP_NO_MAX = 4096, 1 << 30, 0xFFFFFFFF   # FMD_KCMP_MIN_CAP, FMD_KCMP_MAX_CAP, FMD_KCMP_NO_MAX
+KMAT_MAX_IDX, KMAT_MIN_CAP, KMAT_MAX_CAP, KMAT_NO_MAX = 8, 4096, 1 << 30, 0xFFFFFFFF   # FMD_KMAT_MAX_IDX, FMD_KMAT_MIN_CAP, FMD_KMAT_MAX_CAP, FMD_KMAT_NO_MAX
+KMAT_SEL_DT = np.dtype([("min", "<u4", 8), ("max", "<u4", 8), ("present", "<u4"), ("reserved", "<u4")])  # fmd_kmat_sel_t
+KMAT_STAT_DT = np.dtype([("n_kmers", "<u8"), ("n_total", "<u8", 8), ("n_present", "<u8", 8), ("n_ext", "<u8"), ("overflow", "<u8"), ("widest_level", "<u8"), ("n_parts", "<u8"),
+                         ("n_retries", "<u8")])  # fmd_kmat_stat_t
+KMAT_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.POINTER(C.c_uint32)))  # fmd_kmat_sink_fn
 KPROFILE_STAT_DT = np.dtype([(f, "<u8") for f in ("n_windows", "n_valid", "n_hit", "n_ext", "n_table")])  # fmd_kprofile_stat_t
 KPROFILE_MAX_K, KPROFILE_PLAIN = 255, 1   # FMD_KPROFILE_MAX_K, FMD_KPROFILE_PLAIN
 ASEARCH_HIT_DT = np.dtype([("beg", "<u8"), ("cnt", "<u8"), ("query", "<u4"), ("n_sub", "<u4"), ("sub", "<u2", 4)])  # fmd_asearch_hit_t
@@ -68,6 +73,7 @@ ABI_SYMBOLS = [
     "fmd_locate_work_bytes", "fmd_locate_dev", "fmd_locate_batch",
     "fmd_kcount_work_bytes", "fmd_kcount_part_dev", "fmd_kcount",
     "fmd_kcmp_work_bytes", "fmd_kcmp_part_dev", "fmd_kcmp",
+    "fmd_kmat_node_bytes", "fmd_kmat_work_bytes", "fmd_kmat_part_dev", "fmd_kmat",
     "fmd_kprofile_dev", "fmd_kprofile_batch",
     "fmd_asearch_work_bytes", "fmd_asearch_bound_dev", "fmd_asearch_dev", "fmd_asearch_batch",
     "fmd_esearch_work_bytes", "fmd_esearch_dev", "fmd_esearch_batch",
@@ -159,6 +165,10 @@ def _configure(L):
     L.fmd_kcmp_work_bytes.restype = sz; L.fmd_kcmp_work_bytes.argtypes = [C.c_uint64]
     L.fmd_kcmp_part_dev.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int, sz, vp, C.c_uint64, C.c_uint32, u64p, u64p, u64p, C.c_uint64, vp, vp, sz]
     L.fmd_kcmp.argtypes = [vp, vp, C.c_int, vp, C.c_uint32, u64p, C.c_uint64, vp, vp, vp]
+    L.fmd_kmat_node_bytes.restype = sz; L.fmd_kmat_node_bytes.argtypes = [C.c_int]
+    L.fmd_kmat_work_bytes.restype = sz; L.fmd_kmat_work_bytes.argtypes = [C.c_int, C.c_uint64]
+    L.fmd_kmat_part_dev.argtypes = [C.c_int, vp, vp, C.c_int, vp, C.c_int, sz, vp, C.c_uint64, vp, vp, vp, C.c_uint64, vp, vp, sz]
+    L.fmd_kmat.argtypes = [C.c_int, vp, C.c_int, vp, vp, C.c_uint64, vp, vp, vp]
     L.fmd_kprofile_dev.argtypes = [vp, vp, sz, vp, u64p, u64p, C.c_int, C.c_uint, vp, vp]
     L.fmd_kprofile_batch.argtypes = [vp, sz, vp, u64p, C.c_int, C.c_uint, u64p, C.POINTER(vp), vp]
     L.fmd_asearch_work_bytes.restype = sz; L.fmd_asearch_work_bytes.argtypes = [sz, C.c_uint64]
@@ -681,6 +691,66 @@ def multi_backward_search(indexes, seqs):
     cnt = np.zeros(n, dtype=np.uint64); beg = np.zeros(n, dtype=np.uint64); end = np.zeros(n, dtype=np.uint64)
     check(lib().fmd_multi_bsearch_batch(len(indexes), hs, n, _ptr(flat), _ptr(off), _ptr(cnt), _ptr(beg), _ptr(end)))
     return cnt, beg, end
+
+
+def kmat_sel(n_idx, sel=None, present=1):
+    """The fmd_kmat_sel_t (a KMAT_SEL_DT array of one) of a selection given as up to n_idx pairs (min, max), max None or KMAT_NO_MAX = no upper bound;
+    missing trailing pairs are (0, None)."""
+    s = np.zeros(1, dtype=KMAT_SEL_DT)
+    s["max"] = KMAT_NO_MAX
+    s["present"] = int(present)
+    sel = list(sel) if sel is not None else []
+    if len(sel) > n_idx:
+        raise ValueError("kmat_sel: %d bounds for %d indexes" % (len(sel), n_idx))
+    for i, (lo, hi) in enumerate(sel):
+        s["min"][0, i] = int(lo); s["max"][0, i] = KMAT_NO_MAX if hi is None else int(hi)
+    return s
+
+
+def _kmat(indexes, k, sel, present, cap, sink):
+    n = len(indexes)
+    hist = np.zeros(1 << n if 1 <= n <= KMAT_MAX_IDX else 0, dtype=np.uint64)
+    stat = np.zeros(1, dtype=KMAT_STAT_DT)
+    s = kmat_sel(max(n, 0) if n <= KMAT_MAX_IDX else KMAT_MAX_IDX, sel, present)
+    hs = (C.c_void_p * max(n, 1))(*[d.h for d in indexes])
+    cb = KMAT_SINK(sink) if sink is not None else None
+    check(lib().fmd_kmat(n, hs, int(k), _ptr(s), _ptr(hist) if len(hist) else None, int(cap), C.cast(cb, C.c_void_p) if cb is not None else None, None, _ptr(stat)))
+    st = {f: int(stat[0][f]) for f in KMAT_STAT_DT.names if f not in ("n_total", "n_present")}
+    st["n_total"] = [int(v) for v in stat[0]["n_total"][:n]]; st["n_present"] = [int(v) for v in stat[0]["n_present"][:n]]
+    return hist, st
+
+
+def kmer_matrix_spectrum(indexes, k, sel=None, present=1, cap=0):
+    """fmd_kmat without a sink: (hist, stat), the presence patterns of the canonical k-mers (1 <= k <= 32) of 1 to KMAT_MAX_IDX indexes of both strands (DevIndex
+    objects on one GPU; the same one may appear several times), unmerged.  c_i = kcount's count of a k-mer in indexes[i].  sel = up to one (min, max) per index,
+    max None = no upper bound, missing ones (0, None): a k-mer is reported iff some c_i >= 1 and min_i <= c_i <= max_i for every i.  hist[pattern] = the reported
+    k-mers with bit i of pattern set iff c_i >= present (2^N words).  stat: the fields of KMAT_STAT_DT as a dict, n_total and n_present as lists of N.  cap: the
+    frontier capacity of a part in entries (KMAT_MIN_CAP ..; 0 = sized from the indexes and the free device memory); the result does not depend on it."""
+    return _kmat(indexes, k, sel, present, cap, None)
+
+
+def kmer_matrix(indexes, k, sel=None, present=1, cap=0, slices=None):
+    """fmd_kmat with a sink: (kmers uint64[n], counts uint32[n, N], stat), the reported canonical k-mers (kmer_matrix_spectrum) ascending with their count in every
+    index; a count saturates at 2^32 - 1.  counts is held column by column (Fortran order), as the sink hands the columns over.  slices: a list that receives
+    the length of every slice the sink was handed."""
+    n_idx = len(indexes)
+    ks, cs = [], [[] for _ in range(n_idx)]
+
+    def sink(ctx, n, kmer, count):
+        ks.append(np.ctypeslib.as_array(kmer, (n,)).astype(np.uint64, copy=True))
+        for i in range(n_idx):
+            cs[i].append(np.ctypeslib.as_array(count[i], (n,)).astype(np.uint32, copy=True))
+        if slices is not None:
+            slices.append(int(n))
+        return 0
+
+    _, stat = _kmat(indexes, k, sel, present, cap, sink)
+    kmers = np.concatenate(ks) if ks else np.zeros(0, np.uint64)
+    counts = np.empty((len(kmers), n_idx), dtype=np.uint32, order="F")
+    for i in range(n_idx):
+        if cs[i]:
+            np.concatenate(cs[i], out=counts[:, i])
+    return kmers, counts, stat
 
 
 def _ovlp(self, ids, min_match, max_len=100, max_nei=4, check_left=True):

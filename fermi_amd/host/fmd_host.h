@@ -393,6 +393,17 @@ int fmdh_main_kcount(int argc, char *argv[]);
  * fmdh_kcmp_print_hist: one line per non-empty cell of the n_bins x n_bins row-major histogram, in row-major order; a label of n_bins - 1 stands for "that many or more" */
 void fmdh_kcmp_print_hist(FILE *out, const uint64_t *hist, uint32_t n_bins);
 int fmdh_main_kcmp(int argc, char *argv[]);
+/* kmat_cmd.c: `fermi-amd kmat [-k 21] [-p 1] [-s min:max,min:max,...] [-d] [-g GPU] <a.fmd> <b.fmd> [<c.fmd> ...]`: the joint k-mer counts of 1 to 8 indexes
+ * (fmd_kmat): PT <tab> bits <tab> n_kmers per non-empty presence pattern and SM <tab> i <tab> n_present <tab> n_total per index, or with -d the selected canonical
+ * k-mers with their count in every index, streamed; usage and unreadable-file errors return 1 before the device is looked for.  No GPU behind:
+ * fmdh_kmat_parse_sel: the argument of -s (NULL = none given) for n_idx indexes into sel -- one min:max per index in order, either end may be empty (0 / no
+ *   bound), missing trailing entries are `0:'; present = 1.  1 for an entry without a colon, anything but digits, min > max, or more entries than indexes
+ * fmdh_kmat_print_pt: one PT line per non-empty cell of the 1 << n_idx pattern spectrum, ascending by pattern; bits = n_idx characters, index 0 first
+ * fmdh_kmat_print_sm: one SM line per index */
+int fmdh_kmat_parse_sel(const char *s, int n_idx, fmd_kmat_sel_t *sel);
+void fmdh_kmat_print_pt(FILE *out, const uint64_t *hist, int n_idx);
+void fmdh_kmat_print_sm(FILE *out, int n_idx, const fmd_kmat_stat_t *st);
+int fmdh_main_kmat(int argc, char *argv[]);
 /* kprofile_cmd.c: `fermi-amd kprofile [-k 21] [-s] [-q] [-g GPU] <queries.fa> <a.fmd> [<b.fmd> ...]`: the count of the k-mer at every position of every query
  * sequence in the reads of every index (fmd_kprofile_batch); usage and unreadable-file errors return 1 before the device is looked for.
  * fmdh_kprofile_run: the command behind its argument checks -- the queries of query_fn in batches of about batch_bases bases (0 = the command's 64 MB; a longer

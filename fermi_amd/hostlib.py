@@ -85,6 +85,9 @@ def lib():
         L.fmdh_kmer_text.restype = vp; L.fmdh_kmer_text.argtypes = [C.c_uint64, C.c_int, vp]
         L.fmdh_kcount_print_hist.restype = None; L.fmdh_kcount_print_hist.argtypes = [vp, vp, C.c_uint32]
         L.fmdh_kcmp_print_hist.restype = None; L.fmdh_kcmp_print_hist.argtypes = [vp, vp, C.c_uint32]
+        L.fmdh_kmat_parse_sel.argtypes = [C.c_char_p, C.c_int, vp]
+        L.fmdh_kmat_print_pt.restype = None; L.fmdh_kmat_print_pt.argtypes = [vp, vp, C.c_int]
+        L.fmdh_kmat_print_sm.restype = None; L.fmdh_kmat_print_sm.argtypes = [vp, C.c_int, vp]
         L.fmdh_kprofile_print_kp.restype = None; L.fmdh_kprofile_print_kp.argtypes = [vp, C.c_int, vp, C.c_uint64]
         L.fmdh_kprofile_print_ks.argtypes = [vp, C.c_int, vp, C.c_uint64, C.c_int, vp]
         L.fmdh_kprofile_qual.argtypes = [vp, C.c_uint64, C.c_int, vp]
@@ -244,6 +247,34 @@ def _printed(call):
         finally:
             _libc.fclose(fp)
         return open(tf.name).read()
+
+
+def kmat_parse_sel(text, n_idx):
+    """fmdh_kmat_parse_sel: the argument of `fermi-amd kmat -s` (None = not given) for n_idx indexes -> [(min, max)] * n_idx, max = None for no upper bound;
+    ValueError where the command prints its usage (an entry without a colon, anything but digits, min > max, more entries than indexes)."""
+    sel = np.zeros(18, dtype=np.uint32)               # fmd_kmat_sel_t: min[8], max[8], present, reserved
+    if lib().fmdh_kmat_parse_sel(None if text is None else text.encode(), int(n_idx), sel.ctypes.data) != 0:
+        raise ValueError("kmat_parse_sel: %r for %d indexes" % (text, n_idx))
+    return [(int(sel[i]), None if sel[8 + i] == 0xFFFFFFFF else int(sel[8 + i])) for i in range(int(n_idx))]
+
+
+def kmat_pt_text(hist):
+    """fmdh_kmat_print_pt: the PT lines `fermi-amd kmat` prints for a pattern spectrum of 2^n cells (PT <tab> bits <tab> n_kmers per non-empty pattern, ascending
+    by pattern; bits = n characters, index 0 first), as one str."""
+    hist = np.ascontiguousarray(hist, dtype=np.uint64)
+    n = len(hist).bit_length() - 1
+    if hist.ndim != 1 or n < 1 or n > 8 or len(hist) != 1 << n:
+        raise ValueError("kmat_pt_text: not the spectrum of 1 to 8 indexes")
+    return _printed(lambda fp: lib().fmdh_kmat_print_pt(fp, hist.ctypes.data, n))
+
+
+def kmat_sm_text(n_present, n_total):
+    """fmdh_kmat_print_sm: the SM lines `fermi-amd kmat` prints (SM <tab> i <tab> n_present <tab> n_total per index), as one str."""
+    if len(n_present) != len(n_total) or not 1 <= len(n_total) <= 8:
+        raise ValueError("kmat_sm_text: one n_present and one n_total for each of 1 to 8 indexes")
+    st = np.zeros(22, dtype=np.uint64)                # fmd_kmat_stat_t: n_kmers, n_total[8], n_present[8], ..
+    st[1:1 + len(n_total)] = n_total; st[9:9 + len(n_present)] = n_present
+    return _printed(lambda fp: lib().fmdh_kmat_print_sm(fp, len(n_total), st.ctypes.data))
 
 
 def kprofile_kp_text(idx, counts):

@@ -239,6 +239,59 @@ int fmd_kcmp_part_dev(fmd_dev_t *h0, fmd_dev_t *h1, void *stream, int k, const f
 int fmd_kcmp(fmd_dev_t *h0, fmd_dev_t *h1, int k, const fmd_kcmp_sel_t *sel, uint32_t n_bins, uint64_t *hist, uint64_t cap,
              fmd_kcmp_sink_fn sink, void *ctx, fmd_kcmp_stat_t *stat);
 
+/* ---- kmat (no reference counterpart): the joint k-mer counts of UP TO EIGHT indexes of both strands, unmerged ------------------------------
+ * The "k-mer matrix": rows are canonical k-mers, columns are the n_idx indexes h[0 .. n_idx - 1], 1 <= n_idx <= FMD_KMAT_MAX_IDX.  k, a k-mer,
+ * its packed and its canonical form are kcount's (above), 1 <= k <= 32.  c_i(W) = kcount's COUNT of W in index i: occ_i(W), halved when W =
+ * rc(W), each side on its own.  A selection is one pair (min[i], max[i]) per index, min <= max, a max of FMD_KMAT_NO_MAX = no upper bound (the
+ * entries from n_idx on are ignored), and a presence threshold `present` >= 1.  A canonical k-mer is REPORTED iff the sum of its c_i is >= 1 and
+ * min[i] <= c_i <= max[i] for every i, tested on the exact counts; its PATTERN is the n_idx-bit number with bit i set iff c_i >= present.
+ * Histogram, list and sums cover the reported k-mers and nothing else.  The walk is the trie of the k-mers of all the indexes, level by level, a
+ * node = one suffix's interval (start, size) in each index; an inner node is DROPPED iff occ_i < min[i] for some i, or occ_i = 0 for all i.
+ * That is exact (kcmp's argument, side by side): a count never exceeds the occ of a suffix of the k-mer, and a palindrome's occ is at least its
+ * count.  Upper bounds and `present` prune nothing.  A side whose interval is empty is never fetched again.
+ * Pattern spectrum: hist = 1 << n_idx words, hist[pattern] = the reported k-mers with that pattern; with present = 1, hist[0] = 0.  List: (kmer,
+ * c_0 .. c_{n_idx - 1}), the counts uint32_t that SATURATE at 2^32 - 1 (pattern and sums use the exact counts), ascending by k-mer over the whole
+ * run, no k-mer twice.  stat: n_kmers = k-mers reported, n_total[i] = the sum of their c_i (the selection of everything: the N-free k-windows of
+ * set i), n_present[i] = those with c_i >= present, n_ext = backward extensions done, one per (node, non-empty side), discarded parts included,
+ * overflow (the _dev form), widest_level = the most frontier slots a level reserved (holes included), n_parts = parts run, n_retries = parts
+ * discarded.  The entries of n_total and n_present from n_idx on are 0.
+ * Handles: all on one device; each passes kcount's test of both strands; the same handle may be given several times; FMD_OPEN_NO_TABLES
+ * handles work; a handle of an empty index (FMD_OPEN_EMPTY_OK) is a side on which every count is 0.
+ *
+ * A frontier entry (a root) is fmd_kmat_node_bytes(n_idx) = 16 (n_idx + 1) bytes of uint64_t: the packed suffix, a reserved 0, x0[n_idx] (the
+ * interval start in each index; 0 where the size is 0), size[n_idx]; all sizes 0 = skipped.  The stride depends on n_idx on purpose: three
+ * indexes do not move the bytes of eight.
+ * fmd_kmat_part_dev: one part, for k >= 2.  d_roots = n_roots <= cap entries, 16-byte aligned, of suffixes of ONE length root_len (1 <= root_len
+ * < k); every k-mer W that ends in one of them is walked, kept iff rc(W) <= W and the selection holds, its pattern ADDED to d_hist (1 << n_idx
+ * words the caller zeroes) and -- d_kmer != NULL -- stored as rc(W) in d_kmer[j] and c_i (saturated) in d_count[i * out_cap + j], dense, in no
+ * particular order, out_cap entries at most (d_kmer == NULL: no list, out_cap is ignored).  cap = the entries of each of the two frontiers the
+ * work area (fmd_kmat_work_bytes(n_idx, cap), 16-byte aligned) holds, FMD_KMAT_MIN_CAP <= cap <= FMD_KMAT_MAX_CAP (work_bytes returns 0
+ * outside, and for an n_idx outside 1..8).  When a frontier entry or a list entry does not fit, d_stat->overflow = 1, nothing is written past
+ * either, and histogram, list and sums are incomplete: discard them.  Enqueues on `stream` and returns: it neither allocates nor synchronises.
+ * fmd_kmat: all indexes whole.  Parts start from the single-base roots in the order of rc(suffix); one that overflows is discarded whole and
+ * its run of roots cut in two, a single root replaced by its children one base deeper (fmd_extend_batch on each index with a non-empty side;
+ * those the pruning rule drops are dropped).  sink == NULL: the spectrum and the sums only.  Otherwise every part's k-mers are sorted on the
+ * device, the count columns gathered in their order, and handed to sink(ctx, n, kmer, count) -- count[i][j] = c_i of kmer[j]; host arrays that
+ * live until it returns -- as consecutive slices; a non-zero return stops the run (FMD_E_IO).  cap = 0: sized from the indexes and the free
+ * device memory, grown after an overflow while it fits; the list of a part has room for cap entries.  The large buffers stay in h[0]'s cache
+ * between calls (fmd_dev_trim).  Spectrum, list and sums are the same for every cap.  k = 1 is answered from the marginal counts.
+ * FMD_E_ARG: n_idx outside 1..8, k outside 1..32 (the part entry: 2..32), min > max, present < 1, a cap outside the range, a null handle,
+ * handles on different devices, a handle that fails the strand test, a work area that is too small or not 16-byte aligned. */
+#define FMD_KMAT_MAX_IDX 8
+#define FMD_KMAT_MIN_CAP 4096u
+#define FMD_KMAT_MAX_CAP (1u << 30)
+#define FMD_KMAT_NO_MAX 0xffffffffu
+typedef struct { uint32_t min[8], max[8], present, reserved; } fmd_kmat_sel_t;
+typedef struct { uint64_t n_kmers, n_total[8], n_present[8], n_ext, overflow, widest_level, n_parts, n_retries; } fmd_kmat_stat_t;
+typedef int (*fmd_kmat_sink_fn)(void *ctx, uint64_t n, const uint64_t *kmer, const uint32_t *const *count);   /* count[i][j] */
+size_t fmd_kmat_node_bytes(int n_idx);                        /* 16 (n_idx + 1); 0 outside 1..FMD_KMAT_MAX_IDX */
+size_t fmd_kmat_work_bytes(int n_idx, uint64_t cap);          /* 0 outside the ranges */
+int fmd_kmat_part_dev(int n_idx, fmd_dev_t *const *h, void *stream, int k, const fmd_kmat_sel_t *sel, int root_len, size_t n_roots,
+                      const void *d_roots, uint64_t cap, uint64_t *d_hist, uint64_t *d_kmer, uint32_t *d_count, uint64_t out_cap,
+                      fmd_kmat_stat_t *d_stat, void *d_work, size_t work_bytes);
+int fmd_kmat(int n_idx, fmd_dev_t *const *h, int k, const fmd_kmat_sel_t *sel, uint64_t *hist, uint64_t cap, fmd_kmat_sink_fn sink, void *ctx,
+             fmd_kmat_stat_t *stat);
+
 /* ---- kprofile (no reference counterpart): kcount's COUNT of every k-window of the query sequences -------------------------------------
  * Sequence i is seqs[off[i] .. off[i+1]) in nt6 (the contract of fmd_bsearch_dev: the bytes 4-byte aligned and readable to the next multiple
  * of 4).  Window j of sequence i is its bases [j, j + k), 0 <= j <= len_i - k: nw_i = max(0, len_i - k + 1) windows, woff[0] = 0, woff[i+1] =
