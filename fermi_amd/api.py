@@ -34,6 +34,10 @@ KMAT_STAT_DT = np.dtype([("n_kmers", "<u8"), ("n_total", "<u8", 8), ("n_present"
 KMAT_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.POINTER(C.c_uint32)))  # fmd_kmat_sink_fn
 KPROFILE_STAT_DT = np.dtype([(f, "<u8") for f in ("n_windows", "n_valid", "n_hit", "n_ext", "n_table")])  # fmd_kprofile_stat_t
 KPROFILE_MAX_K, KPROFILE_PLAIN = 255, 1   # FMD_KPROFILE_MAX_K, FMD_KPROFILE_PLAIN
+KGRAPH_STAT_DT = np.dtype([(f, "<u8") for f in ("n_nodes", "n_arcs", "n_links", "n_unitigs", "n_cycles", "n_ext", "n_rounds")] +
+                          [(f, "<f8") for f in ("ms_arcs", "ms_links", "ms_label")])  # fmd_kgraph_stat_t
+KARCS_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint8))  # fmd_karcs_sink_fn
+KGRAPH_MAX_NODES, KGRAPH_CYCLE = 0x7FFFFFFE, 1   # FMD_KGRAPH_MAX_NODES, FMD_KGRAPH_CYCLE
 ASEARCH_HIT_DT = np.dtype([("beg", "<u8"), ("cnt", "<u8"), ("query", "<u4"), ("n_sub", "<u4"), ("sub", "<u2", 4)])  # fmd_asearch_hit_t
 ASEARCH_STAT_DT = np.dtype([(f, "<u8") for f in ("n_hits", "n_occ", "n_skipped", "n_truncated", "n_unfinished", "overflow", "n_ext", "widest_level")])  # fmd_asearch_stat_t
 ASEARCH_MAX_SUB, ASEARCH_MAX_LEN, ASEARCH_MIN_CAP, ASEARCH_MAX_CAP = 4, 16383, 4096, 1 << 28   # FMD_ASEARCH_*
@@ -75,6 +79,7 @@ ABI_SYMBOLS = [
     "fmd_kcmp_work_bytes", "fmd_kcmp_part_dev", "fmd_kcmp",
     "fmd_kmat_node_bytes", "fmd_kmat_work_bytes", "fmd_kmat_part_dev", "fmd_kmat",
     "fmd_kprofile_dev", "fmd_kprofile_batch",
+    "fmd_karcs", "fmd_kunitig",
     "fmd_asearch_work_bytes", "fmd_asearch_bound_dev", "fmd_asearch_dev", "fmd_asearch_batch",
     "fmd_esearch_work_bytes", "fmd_esearch_dev", "fmd_esearch_batch",
 ]
@@ -91,6 +96,58 @@ FMD_OK, FMD_E_NODEV, FMD_E_ARG, FMD_E_FORMAT, FMD_E_IO, FMD_E_NOMEM, FMD_E_HIP, 
 class Info(C.Structure):
     _fields_ = [("cnt", C.c_uint64 * 7), ("mcnt", C.c_uint64 * 7), ("n_blocks", C.c_uint64),
                 ("hbm_bytes", C.c_uint64), ("device", C.c_int)]
+
+
+class KGraphStatC(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("n_nodes", "n_arcs", "n_links", "n_unitigs", "n_cycles", "n_ext", "n_rounds")] + \
+               [(f, C.c_double) for f in ("ms_arcs", "ms_links", "ms_label")]
+
+
+class KUnitigC(C.Structure):
+    """fmd_kunitig_t"""
+    _fields_ = [("n_nodes", C.c_uint64), ("n_unitigs", C.c_uint64)] + \
+               [(f, C.c_void_p) for f in ("kmer", "count", "arcs", "unitig", "offset", "orient", "u_nodes", "u_first", "u_flags")] + [("stat", KGraphStatC)]
+
+
+class KUnitigs:
+    """The compacted de Bruijn graph of DevIndex.kmer_unitigs (fmd_kunitig_t as numpy arrays).  Per node, ascending by k-mer: kmers uint64, counts uint32,
+    arcs uint8, unitig uint32, offset uint32, orient uint8 (1 = the node reads reversed in the printed unitig); per unitig: u_nodes uint32, u_first uint32
+    (the node at offset 0), u_flags uint8 (KGRAPH_CYCLE); stat = the fields of KGRAPH_STAT_DT as a dict (None when not asked for)."""
+    NODE = (("kmers", "kmer", np.uint64), ("counts", "count", np.uint32), ("arcs", "arcs", np.uint8), ("unitig", "unitig", np.uint32),
+            ("offset", "offset", np.uint32), ("orient", "orient", np.uint8))
+    UNITIG = (("u_nodes", "u_nodes", np.uint32), ("u_first", "u_first", np.uint32), ("u_flags", "u_flags", np.uint8))
+
+    def __init__(self, k, **arrays):
+        self.k, self.stat = int(k), None
+        for name, _, dt in self.NODE + self.UNITIG:
+            setattr(self, name, np.ascontiguousarray(arrays[name], dtype=dt))
+
+    def as_c(self):
+        """a KUnitigC over these arrays (they must outlive it)"""
+        g = KUnitigC()
+        g.n_nodes, g.n_unitigs = len(self.kmers), len(self.u_nodes)
+        for name, field, _ in self.NODE + self.UNITIG:
+            a = getattr(self, name)
+            setattr(g, field, a.ctypes.data if len(a) else None)
+        return g
+
+    def strings(self):
+        """the unitigs as printed: one str per unitig, u_nodes + k - 1 bases"""
+        k = self.k
+        first = np.zeros(len(self.u_nodes) + 1, dtype=np.int64)
+        np.cumsum(self.u_nodes, out=first[1:])
+        order = np.zeros(len(self.kmers), dtype=np.int64)
+        order[first[self.unitig.astype(np.int64)] + self.offset.astype(np.int64)] = np.arange(len(self.kmers))
+        sh = (2 * (k - 1 - np.arange(k))).astype(np.uint64)
+        base = ((self.kmers[:, None] >> sh) & np.uint64(3)).astype(np.int64)          # the bases of every node, forward
+        rev = self.orient.astype(bool)
+        base[rev] = 3 - base[rev][:, ::-1]
+        out = []
+        for u in range(len(self.u_nodes)):
+            nodes = order[first[u]:first[u + 1]]
+            s = np.concatenate([base[nodes[0]], base[nodes[1:], k - 1]])
+            out.append("".join("ACGT"[c] for c in s))
+        return out
 
 
 _lib = None
@@ -171,6 +228,8 @@ def _configure(L):
     L.fmd_kmat.argtypes = [C.c_int, vp, C.c_int, vp, vp, C.c_uint64, vp, vp, vp]
     L.fmd_kprofile_dev.argtypes = [vp, vp, sz, vp, u64p, u64p, C.c_int, C.c_uint, vp, vp]
     L.fmd_kprofile_batch.argtypes = [vp, sz, vp, u64p, C.c_int, C.c_uint, u64p, C.POINTER(vp), vp]
+    L.fmd_karcs.argtypes = [vp, C.c_int, C.c_int, C.c_uint64, vp, vp, vp]
+    L.fmd_kunitig.argtypes = [vp, C.c_int, C.c_int, C.c_uint64, C.POINTER(KUnitigC)]
     L.fmd_asearch_work_bytes.restype = sz; L.fmd_asearch_work_bytes.argtypes = [sz, C.c_uint64]
     L.fmd_asearch_bound_dev.argtypes = [vp, vp, sz, vp, u64p, vp]
     L.fmd_asearch_dev.argtypes = [vp, vp, sz, vp, u64p, vp, C.c_int, C.c_uint32, C.c_uint32, vp, C.c_uint64, u64p, vp, vp, sz]
@@ -579,6 +638,48 @@ class DevIndex:
         if with_stat:
             return counts, woff, {f: int(stat[0][f]) for f in KPROFILE_STAT_DT.names}
         return counts, woff
+
+    def kmer_arcs(self, k, min_occ=1, cap=0, with_stat=False, slices=None):
+        """fmd_karcs: (kmers uint64[], counts uint32[], arcs uint8[][, stat]): the canonical k-mers (k odd, 3..31) with count >= min_occ, ascending -- the list of
+        kmer_counts(k, min_occ) -- and per k-mer x its arc byte: bit c (A, C, G, T = 0..3) set iff the (k+1)-mer x.c has count >= min_occ, bit 4 + c iff c.x
+        has.  cap: the most nodes (0 = no limit); more raise FmdError (-5).  slices: a list that receives the length of every slice the sink was handed."""
+        ks, cs, As = [], [], []
+
+        def sink(ctx, n, kmer, count, arcs):
+            ks.append(np.ctypeslib.as_array(kmer, (n,)).astype(np.uint64, copy=True))
+            cs.append(np.ctypeslib.as_array(count, (n,)).astype(np.uint32, copy=True))
+            As.append(np.ctypeslib.as_array(arcs, (n,)).astype(np.uint8, copy=True))
+            if slices is not None:
+                slices.append(int(n))
+            return 0
+
+        cb = KARCS_SINK(sink)
+        stat = np.zeros(1, dtype=KGRAPH_STAT_DT)
+        check(lib().fmd_karcs(self.h, int(k), int(min_occ), int(cap), C.cast(cb, C.c_void_p), None, _ptr(stat)))
+        cat = lambda xs, dt: np.concatenate(xs) if xs else np.zeros(0, dt)
+        out = (cat(ks, np.uint64), cat(cs, np.uint32), cat(As, np.uint8))
+        return out + ({f: stat[0][f].item() for f in KGRAPH_STAT_DT.names},) if with_stat else out
+
+    def kmer_unitigs(self, k, min_occ=1, cap=0, with_stat=False):
+        """fmd_kunitig: the de Bruijn graph of kmer_arcs compacted to unitigs, as a KUnitigs (its strings() are the unitigs as `fermi-amd kgraph` prints
+        them); with_stat: its .stat is filled in (n_nodes, n_arcs, n_links, n_unitigs, n_cycles, n_ext, n_rounds, ms_arcs, ms_links, ms_label)."""
+        g = KUnitigC()
+        try:
+            check(lib().fmd_kunitig(self.h, int(k), int(min_occ), int(cap), C.byref(g)))
+            arrays = {}
+            for name, field, dt in KUnitigs.NODE + KUnitigs.UNITIG:
+                n = int(g.n_nodes if (name, field, dt) in KUnitigs.NODE else g.n_unitigs)
+                a = np.zeros(n, dtype=dt)
+                if n:
+                    C.memmove(_ptr(a), getattr(g, field), a.nbytes)
+                arrays[name] = a
+        finally:
+            for _, field, _ in KUnitigs.NODE + KUnitigs.UNITIG:
+                lib().fmd_host_free(getattr(g, field))
+        out = KUnitigs(k, **arrays)
+        if with_stat:
+            out.stat = {f: getattr(g.stat, f) for f in KGRAPH_STAT_DT.names}
+        return out
 
     def approx_search(self, seqs, max_sub=1, max_hits=1000, best=False, prune=True, cap=0, count_only=False, with_stat=False):
         """fmd_asearch_batch: the patterns within max_sub substitutions (0 .. ASEARCH_MAX_SUB; no insertions or deletions) of every query that occur

@@ -85,6 +85,16 @@ int fmd_index_finish(fmd_dev *h, int tables = 1);   // tables = 0: no prefix / t
 // the two-base blocks (fmd_pair.hip): built when forced (fmd_dev_build_pairs) or FMD_PAIR asks, and they fit; FMD_OK either way (h->pair says)
 int fmd_pairs_ensure(fmd_dev *h, int force);
 
+// kcount's walk without its end (fmd_kcount.hip), for a walk that ends differently (kgraph, fmd_kgraph.hip): on a work area of fmd_kcount_work_bytes(cap),
+// from n_roots <= cap roots of one length (fmd_kcount_part_dev's), the levels root_len .. depth - 1 (depth <= 31).  *d_frontier = the nodes at `depth`, both
+// orientations of every k-mer with min_occ occurrences and more, size 0 = a hole; the u64 counters at the head of d_work: [depth] = the entries of that
+// frontier (more than cap when it overflowed), [FMD_KCOUNT_CTR_OVF] != 0 when an entry did not fit, [FMD_KCOUNT_CTR_EXT] = the extensions done.
+// *level_grid (may be NULL) = the waves a level ran on.  Enqueues on st; checks nothing.
+#define FMD_KCOUNT_CTR_OVF 41
+#define FMD_KCOUNT_CTR_EXT 44
+int fmd_kcount_levels(fmd_dev *h, hipStream_t st, int depth, int min_occ, int root_len, size_t n_roots, const fmd_intv_t *d_roots, uint64_t cap, void *d_work,
+                      const fmd_intv_t **d_frontier, int *level_grid);
+
 // next zeroed work-queue head for a persistent launch on `stream`
 uint32_t *fmd_next_queue(fmd_dev *h, hipStream_t stream);
 

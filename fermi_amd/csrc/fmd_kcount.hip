@@ -199,6 +199,31 @@ static void kc_plan(fmd_dev_t *h, uint64_t cap, bool listed, int &grid, int &lea
     if (leaf_grid < 1) leaf_grid = 1;
 }
 
+static_assert(FMD_KCOUNT_CTR_OVF == KC_OVF && FMD_KCOUNT_CTR_EXT == KC_EXT, "the counters fmd_internal.h names for fmd_kcount_levels");
+
+// The walk without its end (fmd_internal.h): the counters start from the roots, and the levels root_len .. depth - 1 run; *d_frontier = the nodes at `depth`
+// (d_roots itself when depth = root_len), ctr[depth] of them with the holes, ctr = the head of d_work.  The arguments are the caller's to check.
+int fmd_kcount_levels(fmd_dev_t *h, hipStream_t st, int depth, int min_occ, int root_len, size_t n_roots, const fmd_intv_t *d_roots, uint64_t cap, void *d_work,
+                      const fmd_intv_t **d_frontier, int *level_grid)
+{
+    unsigned long long *ctr = (unsigned long long *)d_work;
+    fmd_intv_t *f[2];
+    f[0] = (fmd_intv_t *)(((uintptr_t)((uint8_t *)d_work + KC_HDR_BYTES) + 255) & ~(uintptr_t)255); f[1] = f[0] + cap;
+    const FmdIndexView ix = fmd_view(h);
+    int grid, leaf_grid; uint32_t ch;
+    kc_plan(h, cap, false, grid, leaf_grid, ch);
+    k_kcount_init<<<1, 64, 0, st>>>(ctr, root_len, (unsigned long long)n_roots);
+    const fmd_intv_t *in = d_roots;
+    for (int d = root_len; d < depth; ++d) {
+        fmd_intv_t *out = f[(d - root_len) & 1];
+        k_kcount_level<<<grid, 64, 0, st>>>(ix, d, (uint64_t)min_occ, in, out, cap, ch, ctr, 1);
+        in = out;
+    }
+    *d_frontier = in;
+    if (level_grid) *level_grid = grid;
+    return FMD_OK;
+}
+
 extern "C" int fmd_kcount_part_dev(fmd_dev_t *h, void *stream, int k, int min_occ, int root_len, size_t n_roots, const fmd_intv_t *d_roots, uint64_t cap,
                                    uint32_t n_bins, uint64_t *d_hist, uint64_t *d_kmer, uint32_t *d_count, uint64_t out_cap, fmd_kcount_stat_t *d_stat,
                                    void *d_work, size_t work_bytes)
@@ -210,18 +235,11 @@ extern "C" int fmd_kcount_part_dev(fmd_dev_t *h, void *stream, int k, int min_oc
     FMD_HIP_TRY(hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)stream;
     unsigned long long *ctr = (unsigned long long *)d_work;
-    fmd_intv_t *f[2];
-    f[0] = (fmd_intv_t *)(((uintptr_t)((uint8_t *)d_work + KC_HDR_BYTES) + 255) & ~(uintptr_t)255); f[1] = f[0] + cap;
     const FmdIndexView ix = fmd_view(h);
     int grid, leaf_grid; uint32_t ch;
     kc_plan(h, cap, d_kmer != nullptr, grid, leaf_grid, ch);
-    k_kcount_init<<<1, 64, 0, st>>>(ctr, root_len, (unsigned long long)n_roots);
-    const fmd_intv_t *in = d_roots;
-    for (int d = root_len; d < k - 1; ++d) {
-        fmd_intv_t *out = f[(d - root_len) & 1];
-        k_kcount_level<<<grid, 64, 0, st>>>(ix, d, (uint64_t)min_occ, in, out, cap, ch, ctr, 1);
-        in = out;
-    }
+    const fmd_intv_t *in = nullptr;
+    FMD_TRY(fmd_kcount_levels(h, st, k - 1, min_occ, root_len, n_roots, d_roots, cap, d_work, &in, nullptr));
     if (d_kmer) k_kcount_leaf<true><<<leaf_grid, 64, 0, st>>>(ix, k, (uint64_t)min_occ, in, cap, n_bins, (unsigned long long *)d_hist, d_kmer, d_count, out_cap, ctr, 1);
     else k_kcount_leaf<false><<<leaf_grid, 64, 0, st>>>(ix, k, (uint64_t)min_occ, in, cap, n_bins, (unsigned long long *)d_hist, nullptr, nullptr, 0, ctr, 1);
     k_kcount_stat<<<1, 64, 0, st>>>(ctr, root_len, k, out_cap, d_kmer != nullptr, d_stat);

@@ -420,6 +420,21 @@ int fmdh_kprofile_print_ks(FILE *out, int idx, const uint8_t *nt6, uint64_t len,
 int fmdh_kprofile_qual(const uint32_t *count, uint64_t len, int k, char *qual);
 int fmdh_kprofile_run(FILE *out, const char *query_fn, int n_idx, fmd_dev_t *const *idx, int k, int mode, size_t batch_bases);
 int fmdh_main_kprofile(int argc, char *argv[]);
+/* kgraph_cmd.c: `fermi-amd kgraph [-k 21] [-o 2] [-f] [-a] [-g GPU] <reads.fmd>`: the de Bruijn graph of the counted k-mers (k odd, 3..31) and its unitigs as
+ * GFA1, as FASTA (-f), or uncompacted (-a: fmd_karcs, streamed); usage and unreadable-file errors return 1 before the device is looked for.  No GPU behind:
+ * fmdh_kgraph_compact_host: the labelling of fmd_kunitig (include/fmd_hip.h) from the n ascending canonical k-mers and their arc bytes alone, walked by one
+ *   thread: the test oracle of the device's labelling and its timing yardstick.  Writes out->unitig / offset / orient / u_nodes / u_first / u_flags (malloc'ed:
+ *   fmdh_kgraph_free, or fmd_host_free each), n_nodes, n_unitigs and of stat n_nodes, n_arcs, n_links, n_unitigs, n_cycles; kmer / count / arcs stay NULL.
+ *   1 without memory, 2 for k even or outside 3..31, more than FMD_KGRAPH_MAX_NODES nodes or a null pointer
+ * fmdh_kgraph_print_gfa / _fasta: the command's output for a graph with all nine arrays set; 1 without memory, 2 when (unitig, offset) are not a partition
+ * fmdh_kgraph_print_arcs: the lines of -a for n nodes
+ * fmdh_kgraph_free: releases the nine arrays and zeroes *g */
+int fmdh_kgraph_compact_host(int k, uint64_t n, const uint64_t *kmer, const uint8_t *arcs, fmd_kunitig_t *out);
+int fmdh_kgraph_print_gfa(FILE *out, int k, const fmd_kunitig_t *g);
+int fmdh_kgraph_print_fasta(FILE *out, int k, const fmd_kunitig_t *g);
+void fmdh_kgraph_print_arcs(FILE *out, int k, uint64_t n, const uint64_t *kmer, const uint32_t *count, const uint8_t *arcs);
+void fmdh_kgraph_free(fmd_kunitig_t *g);
+int fmdh_main_kgraph(int argc, char *argv[]);
 /* asearch_cmd.c: `fermi-amd asearch [-g GPU] [-d 1] [-b] [-m 1000] [-l] [-M 1000] [-r reads.rank] <reads.fmd> <query.fa>`: the patterns within -d substitutions of
  * every query that occur (fmd_asearch_batch), with -l the reads that hold each (fmd_locate_batch + fmdh_locate_hits); usage and unreadable-file errors return 1
  * before the device is looked for.  No GPU behind:

@@ -92,6 +92,11 @@ def lib():
         L.fmdh_kprofile_print_ks.argtypes = [vp, C.c_int, vp, C.c_uint64, C.c_int, vp]
         L.fmdh_kprofile_qual.argtypes = [vp, C.c_uint64, C.c_int, vp]
         L.fmdh_kprofile_run.argtypes = [vp, C.c_char_p, C.c_int, vp, C.c_int, C.c_int, C.c_size_t]
+        L.fmdh_kgraph_compact_host.argtypes = [C.c_int, C.c_uint64, vp, vp, vp]
+        L.fmdh_kgraph_print_gfa.argtypes = [vp, C.c_int, vp]
+        L.fmdh_kgraph_print_fasta.argtypes = [vp, C.c_int, vp]
+        L.fmdh_kgraph_print_arcs.restype = None; L.fmdh_kgraph_print_arcs.argtypes = [vp, C.c_int, C.c_uint64, vp, vp, vp]
+        L.fmdh_kgraph_free.restype = None; L.fmdh_kgraph_free.argtypes = [vp]
         L.fmdh_asearch_pattern.argtypes = [vp, C.c_uint32, vp, vp]
         L.fmdh_esearch_cigar.restype = vp; L.fmdh_esearch_cigar.argtypes = [vp, C.c_uint32, vp, C.c_uint32, C.POINTER(C.c_uint32)]
         L.fmdh_esearch_rankmap.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_uint64)]
@@ -315,6 +320,61 @@ def kprofile_run(query_path, dev_handles, k, mode="", batch_bases=0):
         if lib().fmdh_kprofile_run(fp, query_path.encode(), len(dev_handles), hs, int(k), ord(mode) if mode else 0, int(batch_bases)) != 0:
             raise RuntimeError("fmdh_kprofile_run failed")
     return _printed(call)
+
+
+def kgraph_compact_host(k, kmers, arcs, counts=None):
+    """fmdh_kgraph_compact_host: the unitigs of the de Bruijn graph given by its ascending canonical k-mers and their arc bytes (include/fmd_hip.h, kgraph),
+    walked by one thread on the host -> an api.KUnitigs whose stat has n_nodes, n_arcs, n_links, n_unitigs and n_cycles.  counts: carried along (default 0)."""
+    from . import api
+    kmers = np.ascontiguousarray(kmers, dtype=np.uint64); arcs = np.ascontiguousarray(arcs, dtype=np.uint8)
+    if len(arcs) != len(kmers):
+        raise ValueError("kgraph_compact_host: %d k-mers and %d arc bytes" % (len(kmers), len(arcs)))
+    g = api.KUnitigC()
+    rc = lib().fmdh_kgraph_compact_host(int(k), len(kmers), kmers.ctypes.data if len(kmers) else None, arcs.ctypes.data if len(arcs) else None, C.addressof(g))
+    if rc == 1:
+        raise MemoryError("fmdh_kgraph_compact_host")
+    if rc:
+        raise ValueError("kgraph_compact_host: k = %d with %d nodes" % (k, len(kmers)))
+    try:
+        arrays = dict(kmers=kmers, arcs=arcs, counts=np.zeros(len(kmers), np.uint32) if counts is None else counts)
+        for name, field, dt in api.KUnitigs.NODE[3:] + api.KUnitigs.UNITIG:
+            n = int(g.n_nodes if field in ("unitig", "offset", "orient") else g.n_unitigs)
+            a = np.zeros(n, dtype=dt)
+            if n:
+                C.memmove(a.ctypes.data, getattr(g, field), a.nbytes)
+            arrays[name] = a
+        out = api.KUnitigs(k, **arrays)
+        out.stat = {f: getattr(g.stat, f) for f in ("n_nodes", "n_arcs", "n_links", "n_unitigs", "n_cycles")}
+    finally:
+        lib().fmdh_kgraph_free(C.addressof(g))
+    return out
+
+
+def kgraph_gfa_text(g):
+    """fmdh_kgraph_print_gfa: what `fermi-amd kgraph` prints for an api.KUnitigs (H, S and L lines), as one str."""
+    def call(fp):
+        c = g.as_c()
+        if lib().fmdh_kgraph_print_gfa(fp, g.k, C.addressof(c)) != 0:
+            raise RuntimeError("fmdh_kgraph_print_gfa failed")
+    return _printed(call)
+
+
+def kgraph_fasta_text(g):
+    """fmdh_kgraph_print_fasta: what `fermi-amd kgraph -f` prints for an api.KUnitigs, as one str."""
+    def call(fp):
+        c = g.as_c()
+        if lib().fmdh_kgraph_print_fasta(fp, g.k, C.addressof(c)) != 0:
+            raise RuntimeError("fmdh_kgraph_print_fasta failed")
+    return _printed(call)
+
+
+def kgraph_arcs_text(k, kmers, counts, arcs):
+    """fmdh_kgraph_print_arcs: the lines `fermi-amd kgraph -a` prints (KMER <tab> count <tab> right <tab> left), as one str."""
+    kmers = np.ascontiguousarray(kmers, dtype=np.uint64); counts = np.ascontiguousarray(counts, dtype=np.uint32); arcs = np.ascontiguousarray(arcs, dtype=np.uint8)
+    if not len(kmers) == len(counts) == len(arcs):
+        raise ValueError("kgraph_arcs_text: arrays of different lengths")
+    return _printed(lambda fp: lib().fmdh_kgraph_print_arcs(fp, int(k), len(kmers), kmers.ctypes.data if len(kmers) else None,
+                                                           counts.ctypes.data if len(kmers) else None, arcs.ctypes.data if len(kmers) else None))
 
 
 _libc = C.CDLL(None)

@@ -319,6 +319,49 @@ int fmd_kprofile_dev(fmd_dev_t *h, void *stream, size_t n, const uint8_t *d_seqs
 int fmd_kprofile_batch(fmd_dev_t *h, size_t n, const uint8_t *seqs, const uint64_t *off, int k, unsigned flags,
                        uint64_t *woff /* n + 1, written */, uint32_t **count /* fmd_host_free */, fmd_kprofile_stat_t *stat);
 
+/* ---- kgraph (no reference counterpart): the de Bruijn graph of kcount's k-mers, and its unitigs ------------------------------------------
+ * k is ODD, 3 <= k <= 31 (no k-mer is its own reverse complement, so every node has two distinct sides); min_occ >= 1.  COUNT(W) is kcount's
+ * (above) for W of k and of k + 1 bases: occ(W) on the index of both strands, halved when W = rc(W) -- which a (k+1)-mer can be.
+ * NODES: the canonical k-mers with COUNT >= min_occ: exactly the list of fmd_kcount(k, min_occ), packed and counted (saturating) as there.  A
+ * node's id is its position in that ascending list; its FORWARD orientation is its canonical string x.
+ * ARCS: one byte per node: bit c (c = 0..3 for A, C, G, T) is set iff COUNT(x.c) >= min_occ, bit 4 + c iff COUNT(c.x) >= min_occ: what
+ * fmd_kcount(k + 1, min_occ) lists, seen from its nodes.  Arcs are symmetric: x.c and rc(x.c) have the same COUNT.
+ * LINK: for oriented nodes u and v = the last k - 1 bases of u followed by c, the arc u -> v is COMPACTABLE iff u has exactly one right arc, v
+ * has exactly one left arc, and u and v are different nodes (a loop A^k -> A^k, and a hairpin u -> rc(u) through a (k+1)-mer that is its own
+ * reverse complement, always end a unitig).
+ * UNITIGS: the maximal chains of compactable links; every node is in exactly one, and a unitig of n nodes spells n + k - 1 bases.  A chain with
+ * two ends is printed as the lexicographically smaller of its string and that string's reverse complement.  A chain that closes on itself (an
+ * isolated cycle; flag FMD_KGRAPH_CYCLE) is opened at its smallest node id and printed from that node in forward orientation, n + k - 1 bases.
+ * Unitig ids ascend by the smallest node id contained.  Per node: unitig = its unitig's id, offset = its position in the printed string (the
+ * node's k bases are [offset, offset + k) there), orient = 0 when the node reads forward in the printed string, 1 when reversed.  Per unitig:
+ * u_nodes = its nodes, u_first = the node at offset 0, u_flags.
+ * stat: n_nodes; n_arcs = the (k+1)-mers up to reverse complement behind the arc bits (= the length of kcount's list for k + 1); n_links =
+ * compactable links, a link and its reverse-complement twin counted once; n_unitigs = n_nodes - n_links + n_cycles; n_ext = backward extensions
+ * done (discarded tries included); n_rounds = doubling rounds run; ms_arcs / ms_links / ms_label = host wall time of the three stages (the walk,
+ * the sort and the arc kernel; link resolution; labelling), each ended by a wait for the device.
+ * fmd_karcs: sink(ctx, n, kmer, count, arcs) gets the nodes ascending in consecutive slices -- host arrays that live until it returns; a non-zero
+ * return stops the run (FMD_E_IO); sink == NULL: stat only.  fmd_kunitig: *out is written whole; its nine arrays are malloc'ed, each released
+ * with fmd_host_free (all NULL, and the counts 0, for an empty graph and after an error).  Both allocate device memory from the handle's cache
+ * (fmd_dev_trim), run on the null stream and return after the device is done.  cap = the most nodes the graph may have, 0 = no limit but
+ * FMD_KGRAPH_MAX_NODES (node ids and ports are 32-bit words); the frontiers of the walk are sized from the index and the free device memory as
+ * fmd_kcount sizes them and grown after an overflow.  FMD_E_NOMEM, with nothing kept, when the graph has more nodes than cap or the frontiers do
+ * not fit; the handle stays usable.  FMD_E_ARG: k even or outside 3..31, min_occ < 1, cap > FMD_KGRAPH_MAX_NODES, a null pointer, or a handle that
+ * fails kcount's test of both strands (necessary, NOT sufficient).  A handle of an empty index (FMD_OPEN_EMPTY_OK) gives an empty graph;
+ * FMD_OPEN_NO_TABLES handles work. */
+#define FMD_KGRAPH_MAX_NODES 0x7ffffffeu
+#define FMD_KGRAPH_CYCLE 1u
+typedef struct { uint64_t n_nodes, n_arcs, n_links, n_unitigs, n_cycles, n_ext, n_rounds; double ms_arcs, ms_links, ms_label; } fmd_kgraph_stat_t;
+typedef int (*fmd_karcs_sink_fn)(void *ctx, uint64_t n, const uint64_t *kmer, const uint32_t *count, const uint8_t *arcs);
+typedef struct {
+    uint64_t n_nodes, n_unitigs;
+    uint64_t *kmer; uint32_t *count; uint8_t *arcs;        /* per node */
+    uint32_t *unitig, *offset; uint8_t *orient;            /* per node */
+    uint32_t *u_nodes, *u_first; uint8_t *u_flags;         /* per unitig */
+    fmd_kgraph_stat_t stat;
+} fmd_kunitig_t;
+int fmd_karcs(fmd_dev_t *h, int k, int min_occ, uint64_t cap, fmd_karcs_sink_fn sink, void *ctx, fmd_kgraph_stat_t *stat);
+int fmd_kunitig(fmd_dev_t *h, int k, int min_occ, uint64_t cap, fmd_kunitig_t *out);
+
 /* ---- asearch (no reference counterpart): search with up to max_sub substitutions ---------------------------------------------------
  * Query i is seqs[off[i] .. off[i+1]) in nt6, L bases (the contract of fmd_bsearch_dev: the bytes 4-byte aligned and readable to the next
  * multiple of 4).  A PATTERN P is a string over A/C/G/T of length L; it is a HIT of the query when occ(P) > 0 and P differs from the query in
