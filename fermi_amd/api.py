@@ -38,6 +38,10 @@ KGRAPH_STAT_DT = np.dtype([(f, "<u8") for f in ("n_nodes", "n_arcs", "n_links", 
                           [(f, "<f8") for f in ("ms_arcs", "ms_links", "ms_label")])  # fmd_kgraph_stat_t
 KARCS_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint8))  # fmd_karcs_sink_fn
 KGRAPH_MAX_NODES, KGRAPH_CYCLE = 0x7FFFFFFE, 1   # FMD_KGRAPH_MAX_NODES, FMD_KGRAPH_CYCLE
+KCGRAPH_SPLIT = 1   # FMD_KCGRAPH_SPLIT
+KCGRAPH_STAT_DT = np.dtype(KGRAPH_STAT_DT.descr + [("n_nodes_in", "<u8", 8), ("n_arcs_in", "<u8", 8)])  # fmd_kcgraph_stat_t
+KCARCS_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.POINTER(C.c_uint8)),
+                          C.POINTER(C.c_uint8))  # fmd_kcarcs_sink_fn
 ASEARCH_HIT_DT = np.dtype([("beg", "<u8"), ("cnt", "<u8"), ("query", "<u4"), ("n_sub", "<u4"), ("sub", "<u2", 4)])  # fmd_asearch_hit_t
 ASEARCH_STAT_DT = np.dtype([(f, "<u8") for f in ("n_hits", "n_occ", "n_skipped", "n_truncated", "n_unfinished", "overflow", "n_ext", "widest_level")])  # fmd_asearch_stat_t
 ASEARCH_MAX_SUB, ASEARCH_MAX_LEN, ASEARCH_MIN_CAP, ASEARCH_MAX_CAP = 4, 16383, 4096, 1 << 28   # FMD_ASEARCH_*
@@ -80,6 +84,7 @@ ABI_SYMBOLS = [
     "fmd_kmat_node_bytes", "fmd_kmat_work_bytes", "fmd_kmat_part_dev", "fmd_kmat",
     "fmd_kprofile_dev", "fmd_kprofile_batch",
     "fmd_karcs", "fmd_kunitig",
+    "fmd_kcarcs", "fmd_kcunitig",
     "fmd_asearch_work_bytes", "fmd_asearch_bound_dev", "fmd_asearch_dev", "fmd_asearch_batch",
     "fmd_esearch_work_bytes", "fmd_esearch_dev", "fmd_esearch_batch",
 ]
@@ -107,6 +112,25 @@ class KUnitigC(C.Structure):
     """fmd_kunitig_t"""
     _fields_ = [("n_nodes", C.c_uint64), ("n_unitigs", C.c_uint64)] + \
                [(f, C.c_void_p) for f in ("kmer", "count", "arcs", "unitig", "offset", "orient", "u_nodes", "u_first", "u_flags")] + [("stat", KGraphStatC)]
+
+
+class KCGraphStatC(C.Structure):
+    """fmd_kcgraph_stat_t"""
+    _fields_ = [("g", KGraphStatC), ("n_nodes_in", C.c_uint64 * 8), ("n_arcs_in", C.c_uint64 * 8)]
+
+
+class KCUnitigC(C.Structure):
+    """fmd_kcunitig_t"""
+    _fields_ = [("n_nodes", C.c_uint64), ("n_unitigs", C.c_uint64), ("n_idx", C.c_int32), ("reserved", C.c_int32)] + \
+               [(f, C.c_void_p) for f in ("kmer", "count", "arcs", "uarcs", "pattern", "unitig", "offset", "orient", "u_nodes", "u_first", "u_flags", "u_count",
+                                          "u_present", "u_pattern")] + [("stat", KCGraphStatC)]
+
+
+def _kcgraph_stat(st, n_idx):
+    """a KCGraphStatC as a dict: kgraph's fields on the union graph, n_nodes_in and n_arcs_in as lists of n_idx"""
+    out = {f: getattr(st.g, f) for f in KGRAPH_STAT_DT.names}
+    out["n_nodes_in"] = [int(v) for v in st.n_nodes_in[:n_idx]]; out["n_arcs_in"] = [int(v) for v in st.n_arcs_in[:n_idx]]
+    return out
 
 
 class KUnitigs:
@@ -230,6 +254,8 @@ def _configure(L):
     L.fmd_kprofile_batch.argtypes = [vp, sz, vp, u64p, C.c_int, C.c_uint, u64p, C.POINTER(vp), vp]
     L.fmd_karcs.argtypes = [vp, C.c_int, C.c_int, C.c_uint64, vp, vp, vp]
     L.fmd_kunitig.argtypes = [vp, C.c_int, C.c_int, C.c_uint64, C.POINTER(KUnitigC)]
+    L.fmd_kcarcs.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_uint64, vp, vp, C.POINTER(KCGraphStatC)]
+    L.fmd_kcunitig.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_uint, C.c_uint64, C.POINTER(KCUnitigC)]
     L.fmd_asearch_work_bytes.restype = sz; L.fmd_asearch_work_bytes.argtypes = [sz, C.c_uint64]
     L.fmd_asearch_bound_dev.argtypes = [vp, vp, sz, vp, u64p, vp]
     L.fmd_asearch_dev.argtypes = [vp, vp, sz, vp, u64p, vp, C.c_int, C.c_uint32, C.c_uint32, vp, C.c_uint64, u64p, vp, vp, sz]
@@ -792,6 +818,100 @@ def multi_backward_search(indexes, seqs):
     cnt = np.zeros(n, dtype=np.uint64); beg = np.zeros(n, dtype=np.uint64); end = np.zeros(n, dtype=np.uint64)
     check(lib().fmd_multi_bsearch_batch(len(indexes), hs, n, _ptr(flat), _ptr(off), _ptr(cnt), _ptr(beg), _ptr(end)))
     return cnt, beg, end
+
+
+class KCUnitigs(KUnitigs):
+    """The compacted coloured de Bruijn graph of kmer_joint_unitigs (fmd_kcunitig_t as numpy arrays) of N indexes.  Per node, ascending by k-mer: kmers uint64,
+    counts uint32[n, N] and arcs uint8[n, N] (held column by column), uarcs uint8 (the union byte), pattern uint8, unitig, offset, orient as in KUnitigs; per
+    unitig: u_nodes, u_first, u_flags, u_count uint64[nu, N], u_present uint32[nu, N], u_pattern uint8.  strings() are the unitigs as `fermi-amd kcgraph`
+    prints them."""
+    NODE = (("kmers", "kmer", np.uint64), ("counts", "count", np.uint32), ("arcs", "arcs", np.uint8), ("uarcs", "uarcs", np.uint8), ("pattern", "pattern", np.uint8),
+            ("unitig", "unitig", np.uint32), ("offset", "offset", np.uint32), ("orient", "orient", np.uint8))
+    UNITIG = (("u_nodes", "u_nodes", np.uint32), ("u_first", "u_first", np.uint32), ("u_flags", "u_flags", np.uint8), ("u_count", "u_count", np.uint64),
+              ("u_present", "u_present", np.uint32), ("u_pattern", "u_pattern", np.uint8))
+
+    def __init__(self, k, n_idx, **arrays):
+        self.k, self.n_idx, self.stat = int(k), int(n_idx), None
+        for name, _, dt in self.NODE + self.UNITIG:
+            a = np.asarray(arrays[name], dtype=dt)
+            if name in ("counts", "arcs"):
+                a = np.asfortranarray(a.reshape(-1, self.n_idx))
+            elif name in ("u_count", "u_present"):
+                a = np.ascontiguousarray(a.reshape(-1, self.n_idx))
+            else:
+                a = np.ascontiguousarray(a)
+            setattr(self, name, a)
+
+    def as_c(self):
+        """a KCUnitigC over these arrays (they must outlive it)"""
+        g = KCUnitigC()
+        g.n_nodes, g.n_unitigs, g.n_idx = len(self.kmers), len(self.u_nodes), self.n_idx
+        for name, field, _ in self.NODE + self.UNITIG:
+            a = getattr(self, name)
+            setattr(g, field, a.ctypes.data if len(a) else None)
+        return g
+
+
+def _handles(indexes):
+    return (C.c_void_p * max(len(indexes), 1))(*[None if d is None else d.h for d in indexes])
+
+
+def kmer_joint_arcs(indexes, k, min_occ=1, cap=0, with_stat=False, slices=None):
+    """fmd_kcarcs: (kmers uint64[n], counts uint32[n, N], arcs uint8[n, N], uarcs uint8[n][, stat]): the coloured de Bruijn graph of 1 to KMAT_MAX_IDX indexes
+    of both strands (DevIndex objects on one GPU; the same one may appear several times), k odd, 3..31.  A canonical k-mer is a node iff its count in SOME
+    index is >= min_occ; counts[:, i] is its exact count in indexes[i]; arcs[:, i] is kmer_arcs' byte within index i, uarcs the OR over the indexes.  The node's
+    pattern is counts >= min_occ.  counts and arcs are held column by column.  cap: the most nodes (0 = no limit); more raise FmdError (-5).  slices: a list
+    that receives the length of every slice the sink was handed.  stat: kgraph's fields on the union graph, n_nodes_in and n_arcs_in per index."""
+    n_idx = len(indexes)
+    ks, us, cs, As = [], [], [[] for _ in range(n_idx)], [[] for _ in range(n_idx)]
+
+    def sink(ctx, n, kmer, count, arcs, uarcs):
+        ks.append(np.ctypeslib.as_array(kmer, (n,)).astype(np.uint64, copy=True))
+        us.append(np.ctypeslib.as_array(uarcs, (n,)).astype(np.uint8, copy=True))
+        for i in range(n_idx):
+            cs[i].append(np.ctypeslib.as_array(count[i], (n,)).astype(np.uint32, copy=True))
+            As[i].append(np.ctypeslib.as_array(arcs[i], (n,)).astype(np.uint8, copy=True))
+        if slices is not None:
+            slices.append(int(n))
+        return 0
+
+    cb = KCARCS_SINK(sink)
+    st = KCGraphStatC()
+    check(lib().fmd_kcarcs(n_idx, _handles(indexes), int(k), int(min_occ), int(cap), C.cast(cb, C.c_void_p), None, C.byref(st)))
+    kmers = np.concatenate(ks) if ks else np.zeros(0, np.uint64)
+    uarcs = np.concatenate(us) if us else np.zeros(0, np.uint8)
+    counts = np.zeros((len(kmers), max(n_idx, 0)), dtype=np.uint32, order="F"); arcs = np.zeros((len(kmers), max(n_idx, 0)), dtype=np.uint8, order="F")
+    for i in range(n_idx):
+        if cs[i]:
+            np.concatenate(cs[i], out=counts[:, i]); np.concatenate(As[i], out=arcs[:, i])
+    out = (kmers, counts, arcs, uarcs)
+    return out + (_kcgraph_stat(st, n_idx),) if with_stat else out
+
+
+def kmer_joint_unitigs(indexes, k, min_occ=1, split=False, cap=0, with_stat=False):
+    """fmd_kcunitig: the coloured de Bruijn graph of kmer_joint_arcs compacted to unitigs on its union bytes, as a KCUnitigs.  split (KCGRAPH_SPLIT): a unitig
+    ends where the pattern changes, so every unitig has one pattern.  with_stat: its .stat is filled in."""
+    n_idx = len(indexes)
+    g = KCUnitigC()
+    try:
+        check(lib().fmd_kcunitig(n_idx, _handles(indexes), int(k), int(min_occ), KCGRAPH_SPLIT if split else 0, int(cap), C.byref(g)))
+        arrays = {}
+        for name, field, dt in KCUnitigs.NODE + KCUnitigs.UNITIG:
+            n = int(g.n_nodes if (name, field, dt) in KCUnitigs.NODE else g.n_unitigs)
+            wide = name in ("counts", "arcs", "u_count", "u_present")
+            a = np.zeros(n * n_idx if wide else n, dtype=dt)
+            if n:
+                C.memmove(_ptr(a), getattr(g, field), a.nbytes)
+            if name in ("counts", "arcs"):
+                a = a.reshape(n_idx, n).T               # columns n_nodes apart
+            arrays[name] = a
+    finally:
+        for _, field, _ in KCUnitigs.NODE + KCUnitigs.UNITIG:
+            lib().fmd_host_free(getattr(g, field))
+    out = KCUnitigs(k, n_idx, **arrays)
+    if with_stat:
+        out.stat = _kcgraph_stat(g.stat, n_idx)
+    return out
 
 
 def kmat_sel(n_idx, sel=None, present=1):

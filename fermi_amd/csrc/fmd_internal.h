@@ -95,6 +95,18 @@ int fmd_pairs_ensure(fmd_dev *h, int force);
 int fmd_kcount_levels(fmd_dev *h, hipStream_t st, int depth, int min_occ, int root_len, size_t n_roots, const fmd_intv_t *d_roots, uint64_t cap, void *d_work,
                       const fmd_intv_t **d_frontier, int *level_grid);
 
+// kgraph's compaction (fmd_kgraph.hip: link resolution, pointer doubling, cut, final) on the sorted nodes of ANY de Bruijn graph held on the device --
+// kgraph's own and the union graph of kcgraph (fmd_kcgraph.hip).  d_kmer ascending, d_arcs the arc bytes, d_pat NULL or a byte per node: a link is then
+// compactable only between nodes with equal bytes (FMD_KCGRAPH_SPLIT).  d_work = fmd_kgraph_compact_bytes(n) bytes and more; d_ctr = 128 u64 words whose
+// words 4, 5 and 16.. are zero.  Null stream; returns after the device is done.  The labels stay in d_work: label = the smallest node id of the chain,
+// off, oc = orient | 2 on a cycle.  fmd_kgraph_number_host turns downloaded labels into unitig ids and fills the per-unitig arrays (malloc'ed).
+struct FmdKgLabels { uint32_t *label, *off; uint8_t *oc; uint64_t n_links, n_cycles, n_rounds; double ms_links, ms_label; };
+size_t fmd_kgraph_compact_bytes(uint64_t n);
+int fmd_kgraph_compact_dev(int k, uint64_t n, const uint64_t *d_kmer, const uint8_t *d_arcs, const uint8_t *d_pat, void *d_work, size_t work_bytes,
+                           unsigned long long *d_ctr, FmdKgLabels *out);
+int fmd_kgraph_number_host(uint64_t n, uint32_t *unitig, const uint32_t *offset, uint8_t *orient, uint64_t *n_unitigs, uint32_t **u_nodes, uint32_t **u_first,
+                           uint8_t **u_flags);
+
 // next zeroed work-queue head for a persistent launch on `stream`
 uint32_t *fmd_next_queue(fmd_dev *h, hipStream_t stream);
 

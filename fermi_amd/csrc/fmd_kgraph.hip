@@ -109,8 +109,9 @@ __global__ __launch_bounds__(256) void k_kgraph_unpack(int k, uint64_t n, const 
 }
 
 // (b) the mate of every port.  Port p = 2 i + side leaves node i in the orientation u = side ? rc(x) : x through u's right end.
+// pat != NULL (kcgraph's split rule): a link is compactable only between nodes of one pattern.
 __global__ __launch_bounds__(256) void k_kgraph_links(int k, uint64_t n, const uint64_t *__restrict__ kmer, const uint8_t *__restrict__ arcs,
-                                                      uint32_t *__restrict__ mate, unsigned long long *__restrict__ ctr)
+                                                      const uint8_t *__restrict__ pat, uint32_t *__restrict__ mate, unsigned long long *__restrict__ ctr)
 {
     const uint64_t mask = ~0ull >> (64 - 2 * k);
     uint64_t n_mates = 0;
@@ -124,7 +125,7 @@ __global__ __launch_bounds__(256) void k_kgraph_links(int k, uint64_t n, const u
             const uint64_t v = (u << 2 | (uint64_t)(__ffs((int)r) - 1)) & mask, rv = kc_revcomp(v, k), y = v < rv ? v : rv;
             uint64_t lo = 0, hi = n;                                     // the first j with kmer[j] >= y
             while (lo < hi) { const uint64_t mid = (lo + hi) >> 1; if (kmer[mid] < y) lo = mid + 1; else hi = mid; }
-            if (lo < n && kmer[lo] == y && lo != i) {                    // (a self-loop or a hairpin is an end)
+            if (lo < n && kmer[lo] == y && lo != i && (!pat || pat[lo] == pat[i])) {   // (a self-loop or a hairpin is an end)
                 const uint32_t b = arcs[lo], l = v == y ? b >> 4 : b & 15u;   // v's left arcs, up to their order
                 if (__popc(l) == 1) mt = (uint32_t)(2 * lo) + (v == y ? 1u : 0u);   // v forward is entered through its left port
             }
@@ -343,30 +344,27 @@ static void kg_free_out(fmd_kunitig_t *o)
     memset(o, 0, sizeof(*o));
 }
 
-static int kg_kunitig(fmd_dev_t *h, int k, int min_occ, uint64_t cap, fmd_kunitig_t *out)
+// (b) + (c) on sorted nodes and their arc bytes, for kgraph and kcgraph alike (fmd_internal.h)
+size_t fmd_kgraph_compact_bytes(uint64_t n) { return 1024 + 6 * 256 + 2 * n * (4 + 16 + 16) + n * (4 + 4 + 1); }
+
+int fmd_kgraph_compact_dev(int k, uint64_t n, const uint64_t *d_kmer, const uint8_t *d_arcs, const uint8_t *d_pat, void *d_work, size_t work_bytes,
+                           unsigned long long *ctr, FmdKgLabels *out)
 {
-    FMD_TRY(kg_check(h, k, min_occ, cap));
-    KgDev g;
-    fmd_kgraph_stat_t st;
-    FMD_TRY(kg_arcs(h, k, min_occ, cap, g, &st));
-    const uint64_t n = g.n, n2 = 2 * n;
-    out->stat = st;
-    if (n == 0) return FMD_OK;
-    // (b) + (c) in the work area of the walk, behind its counters: 81 n bytes and the alignment, where the frontiers had 128 n and more
-    uint8_t *w = (uint8_t *)g.work.p + 1024;
+    const uint64_t n2 = 2 * n;
+    uint8_t *w = (uint8_t *)d_work + 1024;
     auto carve = [&w](size_t bytes) { uint8_t *p = (uint8_t *)(((uintptr_t)w + 255) & ~(uintptr_t)255); w = p + bytes; return p; };
     uint32_t *mate = (uint32_t *)carve(n2 * 4);
     uint4 *sts[2] = {(uint4 *)carve(n2 * 16), (uint4 *)carve(n2 * 16)};
     uint32_t *label = (uint32_t *)carve(n * 4), *off = (uint32_t *)carve(n * 4);
     uint8_t *oc = carve(n);
-    if ((size_t)(w - (uint8_t *)g.work.p) > g.wb) return FMD_E_OVERFLOW;   // (n <= fcap / 2 + 64, fcap >= 4096: cannot happen)
-    unsigned long long *ctr = g.ctr.as<unsigned long long>(), hc[KG_WORDS];
+    if ((size_t)(w - (uint8_t *)d_work) > work_bytes) return FMD_E_OVERFLOW;
+    unsigned long long hc[KG_WORDS];
     const unsigned grid = fmd_nblk(n2, 256) < 8192u ? fmd_nblk(n2, 256) : 8192u;
     KgClock::time_point t0 = KgClock::now();
-    k_kgraph_links<<<grid, 256, 0, nullptr>>>(k, n, g.kmer(), g.arcs(), mate, ctr);
+    k_kgraph_links<<<grid, 256, 0, nullptr>>>(k, n, d_kmer, d_arcs, d_pat, mate, ctr);
     FMD_CHECK_LAUNCH("kgraph links");
     FMD_HIP_TRY(hipStreamSynchronize(nullptr));
-    out->stat.ms_links = kg_ms(t0);
+    out->ms_links = kg_ms(t0);
     t0 = KgClock::now();
     int cur = 0, round = 0;
     FMD_HIP_TRY(hipMemsetAsync(oc, 0, n, nullptr));
@@ -379,14 +377,53 @@ static int kg_kunitig(fmd_dev_t *h, int k, int min_occ, uint64_t cap, fmd_kuniti
         k_kgraph_init<<<grid, 256, 0, nullptr>>>(n2, mate, sts[cur], 1);
         FMD_TRY(kg_double(n2, sts, cur, ctr, round, grid));
     }
-    k_kgraph_final<<<grid, 256, 0, nullptr>>>(k, n, g.kmer(), sts[cur], label, off, oc);
+    k_kgraph_final<<<grid, 256, 0, nullptr>>>(k, n, d_kmer, sts[cur], label, off, oc);
     FMD_CHECK_LAUNCH("kgraph final");
     FMD_HIP_TRY(hipStreamSynchronize(nullptr));
-    out->stat.ms_label = kg_ms(t0);
-    out->stat.n_links = hc[KG_MATES] / 2;
-    out->stat.n_cycles = hc[KG_CYC];
-    out->stat.n_rounds = (uint64_t)round;
-    // the arrays; labels (the smallest node of the chain) -> unitig ids in the order of the labels
+    out->ms_label = kg_ms(t0);
+    out->n_links = hc[KG_MATES] / 2;
+    out->n_cycles = hc[KG_CYC];
+    out->n_rounds = (uint64_t)round;
+    out->label = label; out->off = off; out->oc = oc;
+    return FMD_OK;
+}
+
+// labels (the smallest node of the chain; in `unitig`) -> unitig ids in the order of the labels, and the per-unitig arrays (calloc'ed here)
+int fmd_kgraph_number_host(uint64_t n, uint32_t *unitig, const uint32_t *offset, uint8_t *orient, uint64_t *n_unitigs, uint32_t **u_nodes, uint32_t **u_first,
+                           uint8_t **u_flags)
+{
+    uint64_t nu = 0;
+    for (uint64_t i = 0; i < n; ++i) nu += unitig[i] == i;
+    *n_unitigs = nu;
+    *u_nodes = (uint32_t *)calloc(nu, 4); *u_first = (uint32_t *)malloc(nu * 4); *u_flags = (uint8_t *)calloc(nu, 1);
+    if (!*u_nodes || !*u_first || !*u_flags) return FMD_E_NOMEM;
+    nu = 0;
+    for (uint64_t i = 0; i < n; ++i) {                // a label is the smallest node of its chain: it is met before the chain's other nodes
+        const uint32_t lab = unitig[i];
+        const uint32_t u = lab == i ? (uint32_t)nu++ : unitig[lab];
+        unitig[i] = u;
+        ++(*u_nodes)[u];
+        if (offset[i] == 0) (*u_first)[u] = (uint32_t)i;
+        if (orient[i] & 2) (*u_flags)[u] = FMD_KGRAPH_CYCLE;
+        orient[i] &= 1;
+    }
+    return FMD_OK;
+}
+
+static int kg_kunitig(fmd_dev_t *h, int k, int min_occ, uint64_t cap, fmd_kunitig_t *out)
+{
+    FMD_TRY(kg_check(h, k, min_occ, cap));
+    KgDev g;
+    fmd_kgraph_stat_t st;
+    FMD_TRY(kg_arcs(h, k, min_occ, cap, g, &st));
+    const uint64_t n = g.n;
+    out->stat = st;
+    if (n == 0) return FMD_OK;
+    // (b) + (c) in the work area of the walk, behind its counters: 81 n bytes and the alignment, where the frontiers had 128 n and more
+    FmdKgLabels lb;
+    FMD_TRY(fmd_kgraph_compact_dev(k, n, g.kmer(), g.arcs(), nullptr, g.work.p, g.wb, g.ctr.as<unsigned long long>(), &lb));   // (n <= fcap / 2 + 64, fcap >= 4096: it fits)
+    out->stat.ms_links = lb.ms_links; out->stat.ms_label = lb.ms_label;
+    out->stat.n_links = lb.n_links; out->stat.n_cycles = lb.n_cycles; out->stat.n_rounds = lb.n_rounds;
     out->n_nodes = n;
     out->kmer = (uint64_t *)malloc(n * 8); out->count = (uint32_t *)malloc(n * 4); out->arcs = (uint8_t *)malloc(n);
     out->unitig = (uint32_t *)malloc(n * 4); out->offset = (uint32_t *)malloc(n * 4); out->orient = (uint8_t *)malloc(n);
@@ -394,24 +431,11 @@ static int kg_kunitig(fmd_dev_t *h, int k, int min_occ, uint64_t cap, fmd_kuniti
     FMD_HIP_TRY(hipMemcpy(out->kmer, g.kmer(), n * 8, hipMemcpyDeviceToHost));
     FMD_HIP_TRY(hipMemcpy(out->count, g.count(), n * 4, hipMemcpyDeviceToHost));
     FMD_HIP_TRY(hipMemcpy(out->arcs, g.arcs(), n, hipMemcpyDeviceToHost));
-    FMD_HIP_TRY(hipMemcpy(out->unitig, label, n * 4, hipMemcpyDeviceToHost));
-    FMD_HIP_TRY(hipMemcpy(out->offset, off, n * 4, hipMemcpyDeviceToHost));
-    FMD_HIP_TRY(hipMemcpy(out->orient, oc, n, hipMemcpyDeviceToHost));
-    uint64_t nu = 0;
-    for (uint64_t i = 0; i < n; ++i) nu += out->unitig[i] == i;
-    out->n_unitigs = nu; out->stat.n_unitigs = nu;
-    out->u_nodes = (uint32_t *)calloc(nu, 4); out->u_first = (uint32_t *)malloc(nu * 4); out->u_flags = (uint8_t *)calloc(nu, 1);
-    if (!out->u_nodes || !out->u_first || !out->u_flags) return FMD_E_NOMEM;
-    nu = 0;
-    for (uint64_t i = 0; i < n; ++i) {                // a label is the smallest node of its chain: it is met before the chain's other nodes
-        const uint32_t lab = out->unitig[i];
-        const uint32_t u = lab == i ? (uint32_t)nu++ : out->unitig[lab];
-        out->unitig[i] = u;
-        ++out->u_nodes[u];
-        if (out->offset[i] == 0) out->u_first[u] = (uint32_t)i;
-        if (out->orient[i] & 2) out->u_flags[u] = FMD_KGRAPH_CYCLE;
-        out->orient[i] &= 1;
-    }
+    FMD_HIP_TRY(hipMemcpy(out->unitig, lb.label, n * 4, hipMemcpyDeviceToHost));
+    FMD_HIP_TRY(hipMemcpy(out->offset, lb.off, n * 4, hipMemcpyDeviceToHost));
+    FMD_HIP_TRY(hipMemcpy(out->orient, lb.oc, n, hipMemcpyDeviceToHost));
+    FMD_TRY(fmd_kgraph_number_host(n, out->unitig, out->offset, out->orient, &out->n_unitigs, &out->u_nodes, &out->u_first, &out->u_flags));
+    out->stat.n_unitigs = out->n_unitigs;
     return FMD_OK;
 }
 extern "C" int fmd_kunitig(fmd_dev_t *h, int k, int min_occ, uint64_t cap, fmd_kunitig_t *out)

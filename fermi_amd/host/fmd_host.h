@@ -435,6 +435,30 @@ int fmdh_kgraph_print_fasta(FILE *out, int k, const fmd_kunitig_t *g);
 void fmdh_kgraph_print_arcs(FILE *out, int k, uint64_t n, const uint64_t *kmer, const uint32_t *count, const uint8_t *arcs);
 void fmdh_kgraph_free(fmd_kunitig_t *g);
 int fmdh_main_kgraph(int argc, char *argv[]);
+/* what kcgraph_cmd.c shares with kgraph_cmd.c: the labelling with an optional byte per node -- a link is then compactable only between nodes with equal bytes
+ * (FMD_KCGRAPH_SPLIT) --, and the unitig printer with the per-colour sums of a coloured graph: KC = their sum over the colours (g->count may be NULL), the tags
+ * kc:B:I / kn:B:I on every S line and FASTA header, PT:Z:<bits> in the header, and with filter only the unitigs whose u_pattern equals want and the links between them */
+typedef struct { int n_idx; const uint64_t *u_count; const uint32_t *u_present; const uint8_t *u_pattern; int filter; uint8_t want; } fmdh_kgraph_colours_t;
+int fmdh_kgraph_compact_pat(int k, uint64_t n, const uint64_t *kmer, const uint8_t *arcs, const uint8_t *pat, fmd_kunitig_t *out);
+int fmdh_kgraph_print_coloured(FILE *out, int k, const fmd_kunitig_t *g, int gfa, const fmdh_kgraph_colours_t *x);
+/* kcgraph_cmd.c: `fermi-amd kcgraph [-k 21] [-o 2] [-c] [-f] [-a] [-p bits] [-g GPU] <a.fmd> [<b.fmd> ...]`: the coloured de Bruijn graph of 1 to 8 indexes (k odd,
+ * 3..31; include/fmd_hip.h, kcgraph) and its unitigs as GFA1 -- kgraph's lines, KC the sum over the colours, kc:B:I,<count sums> and kn:B:I,<nodes present> per
+ * colour on every S line --, as FASTA (-f: >id KC LN PT:Z:<pattern, index 0 first> kc kn), with -c compacted under FMD_KCGRAPH_SPLIT, with -p bits only the unitigs
+ * whose pattern equals bits and the links between them, or uncompacted (-a, streamed: KMER <tab> c_0,..,c_{N-1} <tab> pattern <tab> right <tab> left of the union,
+ * then <tab> right/left per colour; ACGT, a . for no arc).  Usage and unreadable-file errors return 1 before the device is looked for.  No GPU behind:
+ * fmdh_kcgraph_compact_host: the labelling of fmd_kcunitig from the n ascending k-mers, the union bytes, the patterns and the flags, walked by one thread, plus the
+ *   per-unitig sums from count (n_idx columns n entries apart; NULL: u_count stays 0): oracle and yardstick.  Writes the per-unitig arrays, unitig / offset /
+ *   orient, the counts and of stat.g n_nodes, n_arcs, n_links, n_unitigs, n_cycles; the other per-node arrays stay NULL.  1 without memory, 2 for bad arguments
+ * fmdh_kcgraph_print_gfa / _fasta: the command's output for a graph with all its arrays set (want: the pattern of -p as a number, bit i = index i; filter = 0: all)
+ * fmdh_kcgraph_print_arcs: the lines of -a for n nodes, columns `stride` entries apart; fmdh_kcgraph_free: releases the arrays and zeroes *g */
+int fmdh_kcgraph_compact_host(int k, int n_idx, uint64_t n, const uint64_t *kmer, const uint32_t *count, const uint8_t *uarcs, const uint8_t *pattern, unsigned flags,
+                              fmd_kcunitig_t *out);
+int fmdh_kcgraph_print_gfa(FILE *out, int k, const fmd_kcunitig_t *g, int filter, unsigned want);
+int fmdh_kcgraph_print_fasta(FILE *out, int k, const fmd_kcunitig_t *g, int filter, unsigned want);
+void fmdh_kcgraph_print_arcs(FILE *out, int k, int n_idx, uint32_t min_occ, uint64_t n, uint64_t stride, const uint64_t *kmer, const uint32_t *count, const uint8_t *arcs,
+                             const uint8_t *uarcs);
+void fmdh_kcgraph_free(fmd_kcunitig_t *g);
+int fmdh_main_kcgraph(int argc, char *argv[]);
 /* asearch_cmd.c: `fermi-amd asearch [-g GPU] [-d 1] [-b] [-m 1000] [-l] [-M 1000] [-r reads.rank] <reads.fmd> <query.fa>`: the patterns within -d substitutions of
  * every query that occur (fmd_asearch_batch), with -l the reads that hold each (fmd_locate_batch + fmdh_locate_hits); usage and unreadable-file errors return 1
  * before the device is looked for.  No GPU behind:

@@ -45,7 +45,7 @@ static uint64_t kg_step(int k, uint64_t n, const uint64_t *kmer, uint64_t i, int
 }
 
 /* the port (2 j + side) a compactable link out of port p = 2 i + side arrives at, or KG_NONE: side 0 = the right end of the canonical string */
-static uint32_t kg_mate(int k, uint64_t n, const uint64_t *kmer, const uint8_t *arcs, uint64_t p)
+static uint32_t kg_mate(int k, uint64_t n, const uint64_t *kmer, const uint8_t *arcs, const uint8_t *pat, uint64_t p)
 {
     const uint64_t i = p >> 1;
     const int o = (int)(p & 1);
@@ -54,12 +54,14 @@ static uint32_t kg_mate(int k, uint64_t n, const uint64_t *kmer, const uint8_t *
     if (kg_pop4(r) != 1) return KG_NONE;
     while (!(r >> c & 1u)) ++c;
     const uint64_t j = kg_step(k, n, kmer, i, o, c, &vo);
-    if (j == n || j == i) return KG_NONE;
+    if (j == n || j == i || (pat && pat[j] != pat[i])) return KG_NONE;   /* (pat: kcgraph's split rule) */
     if (kg_pop4(vo ? arcs[j] & 15u : (uint32_t)arcs[j] >> 4) != 1) return KG_NONE;   /* the left arcs of the successor as oriented */
     return (uint32_t)(2 * j) + (vo ? 0u : 1u);
 }
 
-int fmdh_kgraph_compact_host(int k, uint64_t n, const uint64_t *kmer, const uint8_t *arcs, fmd_kunitig_t *out)
+int fmdh_kgraph_compact_host(int k, uint64_t n, const uint64_t *kmer, const uint8_t *arcs, fmd_kunitig_t *out) { return fmdh_kgraph_compact_pat(k, n, kmer, arcs, 0, out); }
+
+int fmdh_kgraph_compact_pat(int k, uint64_t n, const uint64_t *kmer, const uint8_t *arcs, const uint8_t *pat, fmd_kunitig_t *out)
 {
     if (!out) return 2;
     memset(out, 0, sizeof(*out));
@@ -76,7 +78,7 @@ int fmdh_kgraph_compact_host(int k, uint64_t n, const uint64_t *kmer, const uint
     }
     const uint64_t mask1 = ~0ull >> (64 - 2 * (k + 1));
     uint64_t bits = 0, pal = 0, mates = 0, nu = 0;
-    for (uint64_t p = 0; p < 2 * n; ++p) mates += (mate[p] = kg_mate(k, n, kmer, arcs, p)) != KG_NONE;
+    for (uint64_t p = 0; p < 2 * n; ++p) mates += (mate[p] = kg_mate(k, n, kmer, arcs, pat, p)) != KG_NONE;
     for (uint64_t i = 0; i < n; ++i) {
         out->unitig[i] = KG_NONE;
         for (int c = 0; c < 4; ++c) {
@@ -151,7 +153,7 @@ static int kg_order(const fmd_kunitig_t *g, uint64_t **first_, uint32_t **order_
 }
 
 /* the string of unitig u into seq (u_nodes + k - 1 characters and a NUL), *kc = the sum of its nodes' counts */
-static void kg_seq(int k, const fmd_kunitig_t *g, const uint64_t *first, const uint32_t *order, uint64_t u, char *seq, uint64_t *kc)
+static void kg_seq(int k, const fmd_kunitig_t *g, const uint64_t *first, const uint32_t *order, uint64_t u, char *seq, uint64_t *kc)   /* (no counts: *kc = 0) */
 {
     uint64_t len = 0, sum = 0;
     for (uint64_t t = first[u]; t < first[u + 1]; ++t) {
@@ -159,14 +161,29 @@ static void kg_seq(int k, const fmd_kunitig_t *g, const uint64_t *first, const u
         const uint64_t x = g->orient[i] ? kg_rc(g->kmer[i], k) : g->kmer[i];
         if (t == first[u]) { fmdh_kmer_text(x, k, seq); len = (uint64_t)k; }
         else seq[len++] = "ACGT"[x & 3];
-        sum += g->count[i];
+        if (g->count) sum += g->count[i];
     }
     seq[len] = 0;
     *kc = sum;
 }
 
-static int kg_print_unitigs(FILE *out, int k, const fmd_kunitig_t *g, int gfa)
+/* the bits of a pattern, index 0 first */
+static const char *kg_bits(uint32_t p, int n_idx, char *buf) { for (int i = 0; i < n_idx; ++i) buf[i] = p >> i & 1 ? '1' : '0'; buf[n_idx] = 0; return buf; }
+
+/* the tags of unitig u that only a coloured graph has */
+static void kg_colour_tags(FILE *out, const fmdh_kgraph_colours_t *x, uint64_t u, int sep)
 {
+    fprintf(out, "%ckc:B:I", sep);
+    for (int i = 0; i < x->n_idx; ++i) fprintf(out, ",%llu", (unsigned long long)x->u_count[u * x->n_idx + i]);
+    fprintf(out, "%ckn:B:I", sep);
+    for (int i = 0; i < x->n_idx; ++i) fprintf(out, ",%u", x->u_present[u * x->n_idx + i]);
+}
+
+static int kg_print_unitigs(FILE *out, int k, const fmd_kunitig_t *g, int gfa) { return fmdh_kgraph_print_coloured(out, k, g, gfa, 0); }
+
+int fmdh_kgraph_print_coloured(FILE *out, int k, const fmd_kunitig_t *g, int gfa, const fmdh_kgraph_colours_t *x)
+{
+    char bits[9];
     uint64_t *first = 0, longest = 0, kc;
     uint32_t *order = 0;
     const int rc = kg_order(g, &first, &order);
@@ -176,13 +193,23 @@ static int kg_print_unitigs(FILE *out, int k, const fmd_kunitig_t *g, int gfa)
     if (!seq) { free(first); free(order); return 1; }
     if (gfa) fprintf(out, "H\tVN:Z:1.0\n");
     for (uint64_t u = 0; u < g->n_unitigs; ++u) {
+        if (x && x->filter && x->u_pattern[u] != x->want) continue;
         kg_seq(k, g, first, order, u, seq, &kc);
+        for (int i = 0; x && i < x->n_idx; ++i) kc += x->u_count[u * x->n_idx + i];   /* KC of a coloured unitig: the sum over the colours */
         const unsigned long long ln = (unsigned long long)g->u_nodes[u] + (unsigned long long)k - 1;
-        if (gfa) fprintf(out, "S\t%llu\t%s\tKC:i:%llu\tLN:i:%llu\n", (unsigned long long)u, seq, (unsigned long long)kc, ln);
-        else fprintf(out, ">%llu KC:i:%llu LN:i:%llu\n%s\n", (unsigned long long)u, (unsigned long long)kc, ln, seq);
+        if (gfa) {
+            fprintf(out, "S\t%llu\t%s\tKC:i:%llu\tLN:i:%llu", (unsigned long long)u, seq, (unsigned long long)kc, ln);
+            if (x) kg_colour_tags(out, x, u, '\t');
+            fputc('\n', out);
+        } else {
+            fprintf(out, ">%llu KC:i:%llu LN:i:%llu", (unsigned long long)u, (unsigned long long)kc, ln);
+            if (x) { fprintf(out, " PT:Z:%s", kg_bits(x->u_pattern[u], x->n_idx, bits)); kg_colour_tags(out, x, u, ' '); }
+            fprintf(out, "\n%s\n", seq);
+        }
     }
     for (uint64_t a = 0; gfa && a < g->n_unitigs; ++a)
-        for (int oa = 0; oa < 2; ++oa) {              /* leaving a read as printed (+) through its last node, or reversed (-) through its first */
+        for (int oa = 0; oa < 2; ++oa) {
+            if (x && x->filter && x->u_pattern[a] != x->want) continue;              /* leaving a read as printed (+) through its last node, or reversed (-) through its first */
             const uint32_t e = oa ? order[first[a]] : order[first[a + 1] - 1];
             const int eo = oa ? !g->orient[e] : g->orient[e];
             const uint32_t r = kg_right(g->arcs, e, eo);
@@ -193,6 +220,7 @@ static int kg_print_unitigs(FILE *out, int k, const fmd_kunitig_t *g, int gfa)
                 if (j == g->n_nodes) continue;        /* (arcs that name no node: not from this library) */
                 const uint32_t b = g->unitig[j];
                 int ob;
+                if (x && x->filter && x->u_pattern[b] != x->want) continue;   /* links between printed unitigs only */
                 if (g->offset[j] == 0 && vo == g->orient[j]) ob = 0;
                 else if (g->offset[j] == g->u_nodes[b] - 1 && vo != g->orient[j]) ob = 1;
                 else continue;

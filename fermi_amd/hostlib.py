@@ -97,6 +97,11 @@ def lib():
         L.fmdh_kgraph_print_fasta.argtypes = [vp, C.c_int, vp]
         L.fmdh_kgraph_print_arcs.restype = None; L.fmdh_kgraph_print_arcs.argtypes = [vp, C.c_int, C.c_uint64, vp, vp, vp]
         L.fmdh_kgraph_free.restype = None; L.fmdh_kgraph_free.argtypes = [vp]
+        L.fmdh_kcgraph_compact_host.argtypes = [C.c_int, C.c_int, C.c_uint64, vp, vp, vp, vp, C.c_uint, vp]
+        L.fmdh_kcgraph_print_gfa.argtypes = [vp, C.c_int, vp, C.c_int, C.c_uint]
+        L.fmdh_kcgraph_print_fasta.argtypes = [vp, C.c_int, vp, C.c_int, C.c_uint]
+        L.fmdh_kcgraph_print_arcs.restype = None; L.fmdh_kcgraph_print_arcs.argtypes = [vp, C.c_int, C.c_int, C.c_uint32, C.c_uint64, C.c_uint64, vp, vp, vp, vp]
+        L.fmdh_kcgraph_free.restype = None; L.fmdh_kcgraph_free.argtypes = [vp]
         L.fmdh_asearch_pattern.argtypes = [vp, C.c_uint32, vp, vp]
         L.fmdh_esearch_cigar.restype = vp; L.fmdh_esearch_cigar.argtypes = [vp, C.c_uint32, vp, C.c_uint32, C.POINTER(C.c_uint32)]
         L.fmdh_esearch_rankmap.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_uint64)]
@@ -375,6 +380,78 @@ def kgraph_arcs_text(k, kmers, counts, arcs):
         raise ValueError("kgraph_arcs_text: arrays of different lengths")
     return _printed(lambda fp: lib().fmdh_kgraph_print_arcs(fp, int(k), len(kmers), kmers.ctypes.data if len(kmers) else None,
                                                            counts.ctypes.data if len(kmers) else None, arcs.ctypes.data if len(kmers) else None))
+
+
+def kcgraph_compact_host(k, kmers, counts, uarcs, pattern, split=False, arcs=None):
+    """fmdh_kcgraph_compact_host: the unitigs of the coloured de Bruijn graph given by its ascending canonical k-mers, their counts (n x N), union arc bytes and
+    patterns (include/fmd_hip.h, kcgraph), walked by one thread on the host, with the per-unitig sums -> an api.KCUnitigs whose stat has n_nodes, n_arcs,
+    n_links, n_unitigs, n_cycles and n_nodes_in.  split: FMD_KCGRAPH_SPLIT.  arcs (n x N): carried along (default 0)."""
+    from . import api
+    kmers = np.ascontiguousarray(kmers, dtype=np.uint64); uarcs = np.ascontiguousarray(uarcs, dtype=np.uint8); pattern = np.ascontiguousarray(pattern, dtype=np.uint8)
+    counts = np.asfortranarray(np.asarray(counts, dtype=np.uint32))
+    if counts.ndim != 2:
+        raise ValueError("kcgraph_compact_host: counts is not n x N")
+    n, n_idx = counts.shape
+    if not len(kmers) == len(uarcs) == len(pattern) == n:
+        raise ValueError("kcgraph_compact_host: arrays of different lengths")
+    g = api.KCUnitigC()
+    d = lambda a: a.ctypes.data if a.size else None
+    rc = lib().fmdh_kcgraph_compact_host(int(k), n_idx, n, d(kmers), d(counts), d(uarcs), d(pattern), api.KCGRAPH_SPLIT if split else 0, C.addressof(g))
+    if rc == 1:
+        raise MemoryError("fmdh_kcgraph_compact_host")
+    if rc:
+        raise ValueError("kcgraph_compact_host: k = %d with %d nodes of %d indexes" % (k, n, n_idx))
+    try:
+        arrays = dict(kmers=kmers, counts=counts, uarcs=uarcs, pattern=pattern, arcs=np.zeros((n, n_idx), np.uint8) if arcs is None else arcs)
+        for name, field, dt in api.KCUnitigs.NODE[5:] + api.KCUnitigs.UNITIG:
+            m = int(g.n_nodes if field in ("unitig", "offset", "orient") else g.n_unitigs)
+            a = np.zeros(m * n_idx if field in ("u_count", "u_present") else m, dtype=dt)
+            if m:
+                C.memmove(a.ctypes.data, getattr(g, field), a.nbytes)
+            arrays[name] = a
+        out = api.KCUnitigs(k, n_idx, **arrays)
+        out.stat = {f: getattr(g.stat.g, f) for f in ("n_nodes", "n_arcs", "n_links", "n_unitigs", "n_cycles")}
+        out.stat["n_nodes_in"] = [int(v) for v in g.stat.n_nodes_in[:n_idx]]
+    finally:
+        lib().fmdh_kcgraph_free(C.addressof(g))
+    return out
+
+
+def _kcgraph_text(fn, name, g, pattern):
+    want = 0
+    if pattern is not None:
+        if len(pattern) != g.n_idx or set(pattern) - set("01"):
+            raise ValueError("%s: pattern %r for %d indexes" % (name, pattern, g.n_idx))
+        want = sum(1 << i for i, c in enumerate(pattern) if c == "1")
+
+    def call(fp):
+        c = g.as_c()
+        if fn(fp, g.k, C.addressof(c), int(pattern is not None), want) != 0:
+            raise RuntimeError(name + " failed")
+    return _printed(call)
+
+
+def kcgraph_gfa_text(g, pattern=None):
+    """fmdh_kcgraph_print_gfa: what `fermi-amd kcgraph [-p pattern]` prints for an api.KCUnitigs (H, S and L lines), as one str; pattern = the bits of -p."""
+    return _kcgraph_text(lib().fmdh_kcgraph_print_gfa, "fmdh_kcgraph_print_gfa", g, pattern)
+
+
+def kcgraph_fasta_text(g, pattern=None):
+    """fmdh_kcgraph_print_fasta: what `fermi-amd kcgraph -f [-p pattern]` prints for an api.KCUnitigs, as one str."""
+    return _kcgraph_text(lib().fmdh_kcgraph_print_fasta, "fmdh_kcgraph_print_fasta", g, pattern)
+
+
+def kcgraph_arcs_text(k, min_occ, kmers, counts, arcs, uarcs):
+    """fmdh_kcgraph_print_arcs: the lines `fermi-amd kcgraph -a` prints (KMER, the counts, the pattern, right and left of the union, right/left per index), as
+    one str; counts and arcs are n x N."""
+    kmers = np.ascontiguousarray(kmers, dtype=np.uint64); uarcs = np.ascontiguousarray(uarcs, dtype=np.uint8)
+    n = len(kmers)
+    counts = np.asfortranarray(np.asarray(counts, dtype=np.uint32).reshape(n, -1)) if n else np.zeros((0, 1), np.uint32)
+    arcs = np.asfortranarray(np.asarray(arcs, dtype=np.uint8).reshape(n, -1)) if n else np.zeros((0, 1), np.uint8)
+    if counts.shape != arcs.shape or len(uarcs) != n:
+        raise ValueError("kcgraph_arcs_text: arrays of different shapes")
+    d = lambda a: a.ctypes.data if a.size else None
+    return _printed(lambda fp: lib().fmdh_kcgraph_print_arcs(fp, int(k), counts.shape[1], int(min_occ), n, n, d(kmers), d(counts), d(arcs), d(uarcs)))
 
 
 _libc = C.CDLL(None)

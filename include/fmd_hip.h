@@ -362,6 +362,52 @@ typedef struct {
 int fmd_karcs(fmd_dev_t *h, int k, int min_occ, uint64_t cap, fmd_karcs_sink_fn sink, void *ctx, fmd_kgraph_stat_t *stat);
 int fmd_kunitig(fmd_dev_t *h, int k, int min_occ, uint64_t cap, fmd_kunitig_t *out);
 
+/* ---- kcgraph (no reference counterpart): the COLOURED de Bruijn graph of up to eight indexes of both strands, unmerged, and its unitigs -------
+ * The inputs are n_idx handles h[0 .. n_idx - 1], 1 <= n_idx <= FMD_KMAT_MAX_IDX, the COLOURS, all on one device; each passes kcount's test of
+ * both strands; the same handle may be given several times; FMD_OPEN_NO_TABLES handles work; a handle of an empty index (FMD_OPEN_EMPTY_OK) is a
+ * colour in which every count is 0.  k is ODD, 3 <= k <= 31, and min_occ >= 1, as for kgraph.  c_i(W) = kcount's COUNT of W in index i: occ_i(W)
+ * on both strands, halved when W = rc(W) -- which only a (k+1)-mer can be here.
+ * NODES: a canonical k-mer x is a node iff c_i(x) >= min_occ for SOME i (a sum over the colours that reaches min_occ makes no node when no single
+ * colour does); ids run along the ascending list.  count[i] = c_i(x), exact even below min_occ, saturated to uint32_t.  The node's PATTERN has
+ * bit i set iff c_i(x) >= min_occ; it is never 0.
+ * ARCS: one byte per node AND colour in kgraph's layout: in arcs[i], bit c is set iff c_i(x.c) >= min_occ, bit 4 + c iff c_i(c.x) >= min_occ.
+ * The UNION byte (uarcs) is the OR over i; it is symmetric like kgraph's.  Hence: with n_idx = 1 everything equals fmd_karcs / fmd_kunitig; the
+ * nodes with pattern bit i, with count[i] and arcs[i], are exactly the answer of fmd_karcs(h[i], k, min_occ); an arc bit in colour i implies
+ * pattern bit i at both of its nodes.
+ * WALK: the trie of the k-mers of all the colours (kmat's, one level further); an inner node is DROPPED iff occ_i < min_occ for ALL i, which is
+ * exact by kcmp's argument (NOT kmat's predicate, an AND of per-index minima).
+ * COMPACTION: kgraph's LINK and UNITIGS rules on the union byte, word for word: cycles opened at the smallest node id, the smaller of string and
+ * reverse complement printed, ids by smallest node.  With FMD_KCGRAPH_SPLIT a link is compactable only if, in addition, both nodes have the same
+ * pattern: every unitig then has one pattern, and a chain that closes on itself is a cycle only if all its nodes agree.
+ * Per unitig, besides kgraph's three arrays: u_count[u * n_idx + i] = the uint64_t sum of the listed count[i] of its nodes, u_present[u * n_idx +
+ * i] = its nodes with pattern bit i, u_pattern[u] = the OR of its nodes' patterns.
+ * stat: g = kgraph's fields on the union graph (ms_label includes the per-unitig sums); n_nodes_in[i] = nodes with pattern bit i, n_arcs_in[i] =
+ * the (k+1)-mers up to reverse complement behind colour i's bits (= the length of fmd_kcount(h[i], k + 1, min_occ)'s list); 0 from n_idx on.
+ * fmd_kcarcs: sink(ctx, n, kmer, count, arcs, uarcs) gets the nodes ascending in consecutive slices, count[i][j] and arcs[i][j] of kmer[j] --
+ * host arrays that live until it returns; a non-zero return stops the run (FMD_E_IO); sink == NULL: stat only.  fmd_kcunitig: *out is written
+ * whole; count and arcs are n_idx columns of n_nodes entries (count[i * n_nodes + j]); its arrays are malloc'ed, each released with fmd_host_free
+ * (all NULL, and the counts 0, for an empty graph and after an error).  Device buffers come from h[0]'s cache (fmd_dev_trim); null stream; both
+ * return after the device is done.  cap = the most nodes the graph may have, 0 = no limit but FMD_KGRAPH_MAX_NODES; the frontiers are sized from
+ * the distinct indexes and the free device memory as fmd_kmat sizes them and grown after an overflow; the graph is held whole.  FMD_E_NOMEM, with
+ * nothing kept, when the graph has more nodes than cap or the frontiers do not fit; the handles stay usable.  FMD_E_ARG: k even or outside 3..31,
+ * min_occ < 1, n_idx outside 1..8, cap > FMD_KGRAPH_MAX_NODES, unknown flag bits, a null pointer, handles on different devices, or a handle that
+ * fails kcount's test of both strands (necessary, NOT sufficient; indexes whose depth-k frontier is not pairs of orientations are refused too). */
+#define FMD_KCGRAPH_SPLIT 1u
+typedef struct { fmd_kgraph_stat_t g; uint64_t n_nodes_in[8], n_arcs_in[8]; } fmd_kcgraph_stat_t;
+typedef int (*fmd_kcarcs_sink_fn)(void *ctx, uint64_t n, const uint64_t *kmer, const uint32_t *const *count, const uint8_t *const *arcs,
+                                  const uint8_t *uarcs);
+typedef struct {
+    uint64_t n_nodes, n_unitigs;
+    int32_t n_idx, reserved;
+    uint64_t *kmer; uint32_t *count; uint8_t *arcs, *uarcs, *pattern;   /* per node; count and arcs: n_idx columns */
+    uint32_t *unitig, *offset; uint8_t *orient;                         /* per node */
+    uint32_t *u_nodes, *u_first; uint8_t *u_flags;                      /* per unitig */
+    uint64_t *u_count; uint32_t *u_present; uint8_t *u_pattern;         /* per unitig; u_count and u_present: n_idx per unitig */
+    fmd_kcgraph_stat_t stat;
+} fmd_kcunitig_t;
+int fmd_kcarcs(int n_idx, fmd_dev_t *const *h, int k, int min_occ, uint64_t cap, fmd_kcarcs_sink_fn sink, void *ctx, fmd_kcgraph_stat_t *stat);
+int fmd_kcunitig(int n_idx, fmd_dev_t *const *h, int k, int min_occ, unsigned flags, uint64_t cap, fmd_kcunitig_t *out);
+
 /* ---- asearch (no reference counterpart): search with up to max_sub substitutions ---------------------------------------------------
  * Query i is seqs[off[i] .. off[i+1]) in nt6, L bases (the contract of fmd_bsearch_dev: the bytes 4-byte aligned and readable to the next
  * multiple of 4).  A PATTERN P is a string over A/C/G/T of length L; it is a HIT of the query when occ(P) > 0 and P differs from the query in
