@@ -1062,13 +1062,17 @@ def _ovlp_pack(self, rec, nei, seq):
 DevIndex.overlap_pack = _ovlp_pack
 
 
-def _kmer_collect(self, w, min_occ, suf_len=None):
-    """fm6_traverse + ec_collect over all buckets: (bucket u32[], key u32[], val u8[], cnt[2])."""
+def _kmer_collect(self, w, min_occ, suf_len=None, seed_mask=None):
+    """fm6_traverse + ec_collect over all buckets: (bucket u32[], key u32[], val u8[], cnt[2]).  seed_mask: fmd_kmer_collect_seeds instead, the
+    k-mers that end in a base of the mask (bit c-1 = nt6 base c)."""
     if suf_len is None:
         suf_len = w - 15 if w > 15 else 1   # compute_SUF (correct.c:319)
     b, k, v, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64()
     cnt = (C.c_int64 * 2)()
-    check(lib().fmd_kmer_collect(self.h, w, min_occ, suf_len, C.byref(b), C.byref(k), C.byref(v), C.byref(n), cnt))
+    if seed_mask is None:
+        check(lib().fmd_kmer_collect(self.h, w, min_occ, suf_len, C.byref(b), C.byref(k), C.byref(v), C.byref(n), cnt))
+    else:
+        check(lib().fmd_kmer_collect_seeds(self.h, w, min_occ, suf_len, seed_mask, C.byref(b), C.byref(k), C.byref(v), C.byref(n), cnt))
     m = n.value
 
     def take(p, ct, dt):   # (ctypes.string_at stops at 2^31 bytes; a 5*10^10-symbol index has 1.7*10^9 solid k-mers)
@@ -1080,6 +1084,7 @@ def _kmer_collect(self, w, min_occ, suf_len=None):
 
 
 DevIndex.kmer_collect = _kmer_collect
+DevIndex.kmer_collect_seeds = lambda self, w, min_occ, suf_len, seed_mask: _kmer_collect(self, w, min_occ, suf_len, seed_mask)   # one GPU's shard of `correct -g`
 
 
 def _smem(self, seqs, self_match=0, max_mem=32):

@@ -591,6 +591,7 @@ extern "C" int fmd_ectab_build_dev(int device, void *stream_, int w, int suf_len
                                    const uint8_t *d_val, fmd_ectab_t **out)
 {
     if (!out || w < 2 || w > 27 || suf_len < 1 || 2 * w - 2 * suf_len > 30 || (n && (!d_bucket || !d_key || !d_val))) return FMD_E_ARG;
+    if (suf_len > 16) return FMD_E_ARG;   // a bucket is a uint32_t: the harvest refuses these too
     if (fmd_device_count() <= 0) return FMD_E_NODEV;
     FMD_HIP_TRY(hipSetDevice(device));
     fmd_ectab *t = (fmd_ectab *)calloc(1, sizeof(fmd_ectab));
@@ -619,7 +620,7 @@ extern "C" int fmd_ectab_build_dev(int device, void *stream_, int w, int suf_len
 
 extern "C" int fmd_ectab_build(int device, int w, int suf_len, uint64_t n, const uint32_t *bucket, const uint32_t *key, const uint8_t *val, fmd_ectab_t **out)
 {
-    if (n && (!bucket || !key || !val)) return FMD_E_ARG;
+    if (suf_len > 16 || (n && (!bucket || !key || !val))) return FMD_E_ARG;
     if (fmd_device_count() <= 0) return FMD_E_NODEV;
     FMD_HIP_TRY(hipSetDevice(device));
     FmdDevBuf db, dk, dv;

@@ -167,6 +167,7 @@ extern "C" int fmd_kmer_collect_part_dev(fmd_dev_t *h, void *stream_, int w, int
 {
     if (!h || !d_work || !d_bucket || !d_key || !d_val || !d_status) return FMD_E_ARG;
     if (w < 2 || w > 27 || suf_len < 1 || suf_len >= w || min_occ < 1 || w - suf_len > 15 || cap < (1u << 16) || !(seed_mask & 0xf)) return FMD_E_ARG; // MAX_KMER 27 (correct.c:303)
+    if (suf_len > 16) return FMD_E_ARG;   // the bucket is a uint32_t: 2 * suf_len bits must fit
     if (work_bytes < fmd_kmer_work_bytes(cap)) return FMD_E_ARG;
     FMD_HIP_TRY(hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)stream_;
@@ -198,7 +199,8 @@ extern "C" int fmd_kmer_collect_part_dev(fmd_dev_t *h, void *stream_, int w, int
     if (grid > h->n_cu * per_cu) grid = h->n_cu * per_cu;
     // chunk of output slots a wave reserves per atomic: as large as the capacity comfortably allows
     // (at most one partial chunk per wave is wasted per level), at least one iteration's worth (256)
-    static const int xcd_aware = getenv("FMD_KMER_XCD") ? atoi(getenv("FMD_KMER_XCD")) : 1;
+    int xcd_aware = 1;
+    { const char *e = getenv("FMD_KMER_XCD"); if (e) xcd_aware = atoi(e); }
     uint32_t ch = 1024;
     while (ch > 256 && (uint64_t)grid * ch * 8 > cap) ch >>= 1;
     fmd_intv_t *in = fa, *out = fb;
@@ -301,6 +303,14 @@ static int km_collect_part_host(fmd_dev_t *h, int w, int min_occ, int suf_len, i
     return FMD_E_OVERFLOW;
 }
 
+// the capacity the host forms start from: FMD_KMER_CAP0 (at least 1 << 16), else 1 << 22
+static uint64_t km_cap0()
+{
+    const char *e = getenv("FMD_KMER_CAP0");
+    const uint64_t v = e ? strtoull(e, nullptr, 10) : 1u << 22;
+    return v < (1u << 16) ? 1u << 16 : v;
+}
+
 // Host form; outputs are malloc'ed (fmd_host_free).  One pass over the whole trie when its frontiers fit next to the index
 // (triples sorted by (bucket, key)), else the four parts by last base one after the other (each part sorted, parts
 // concatenated: the consumers -- fmd_ectab_build, multiset comparisons -- do not depend on the order).
@@ -316,11 +326,12 @@ extern "C" int fmd_kmer_collect(fmd_dev_t *h, int w, int min_occ, int suf_len, u
     const double est = (double)h->mcnt[0] / 20.0;
     int parts = est * 73.0 > 0.8 * (double)free_b ? 4 : 1;
     { const char *e = getenv("FMD_KMER_PARTS"); if (e && (atoi(e) == 1 || atoi(e) == 4)) parts = atoi(e); }
+    const uint64_t cap0 = km_cap0();
     uint64_t m_alloc = 0;
     int rc = FMD_OK;
     for (;;) {
         for (int p = 0; p < parts && rc == FMD_OK; ++p)
-            rc = km_collect_part_host(h, w, min_occ, suf_len, parts == 1 ? 0xf : 1 << p, 1u << 22, bucket, key, val, n, &m_alloc, cnt);
+            rc = km_collect_part_host(h, w, min_occ, suf_len, parts == 1 ? 0xf : 1 << p, cap0, bucket, key, val, n, &m_alloc, cnt);
         if (rc != FMD_E_NOMEM || parts != 1) break;
         // the frontiers of the whole trie did not fit beside the index after all: start over, a quarter at a time
         free(*bucket); free(*key); free(*val); *bucket = nullptr; *key = nullptr; *val = nullptr; *n = 0; m_alloc = 0; cnt[0] = cnt[1] = 0;
@@ -342,10 +353,11 @@ extern "C" int fmd_kmer_collect_seeds(fmd_dev_t *h, int w, int min_occ, int suf_
     if (!h || !bucket || !key || !val || !n || !cnt || (seed_mask & ~0xf)) return FMD_E_ARG;
     FMD_HIP_TRY(hipSetDevice(h->device));
     *bucket = nullptr; *key = nullptr; *val = nullptr; *n = 0; cnt[0] = cnt[1] = 0;
+    const uint64_t cap0 = km_cap0();
     uint64_t m_alloc = 0;
     int rc = FMD_OK;
     for (int p = 0; p < 4 && rc == FMD_OK; ++p)     // one tree at a time: a quarter of the frontier memory of the whole harvest
-        if ((seed_mask >> p) & 1) rc = km_collect_part_host(h, w, min_occ, suf_len, 1 << p, 1u << 22, bucket, key, val, n, &m_alloc, cnt);
+        if ((seed_mask >> p) & 1) rc = km_collect_part_host(h, w, min_occ, suf_len, 1 << p, cap0, bucket, key, val, n, &m_alloc, cnt);
     if (rc != FMD_OK) { free(*bucket); free(*key); free(*val); *bucket = nullptr; *key = nullptr; *val = nullptr; *n = 0; }
     else if (!*bucket) { *bucket = (uint32_t *)malloc(4); *key = (uint32_t *)malloc(4); *val = (uint8_t *)malloc(4); }
     return rc;

@@ -842,7 +842,9 @@ void fmd_ovlp_dist_free(fmd_ovlp_dist_t *d);
  * (bucket, key, val) triple per solid k-mer: bucket = index into `solid[]` (correct.c:346-349),
  * key/val exactly what kh_put/kh_val store (correct.c:71-75).  The order of triples is
  * unspecified for the _dev form (the reference's own order is hash-table iteration order); the host
- * form returns them sorted by (bucket, key), or -- for an index whose frontiers do not fit beside it -- as four sorted parts.  w <= 27, w - suf_len <= 15.
+ * form returns them sorted by (bucket, key), or -- for an index whose frontiers do not fit beside it -- as four sorted parts.  w <= 27, w - suf_len <= 15,
+ * suf_len <= 16 (a bucket is 32 bits; fmd_ectab_build* asks the same): anything else is FMD_E_ARG.  FMD_KMER_CAP0 (read per call, at least 1 << 16;
+ * default 1 << 22) is the capacity the host forms start from before they grow it.
  * d_status (4 x u64): [0] #triples, [1] non-zero = cap overflowed (re-run larger), [2] cnt[0],
  * [3] cnt[1] (correct.c:64-69). */
 size_t fmd_kmer_work_bytes(uint64_t cap);

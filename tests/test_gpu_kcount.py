@@ -2,7 +2,6 @@
 indexed: the canonical form of every N-free k-window of the forward sequences, counted with numpy.  The kernel computes the other form of the same
 number -- occ(W) on the index of both strands, halved for a k-mer that is its own reverse complement -- so the two meet only if both are right."""
 import ctypes as C
-import gzip
 import os
 import subprocess
 
@@ -10,6 +9,7 @@ import numpy as np
 import pytest
 
 from fermi_amd import api, hostlib
+from harvest_ref import forward_as_indexed, revcomp      # the golden reads as `build` indexed them
 
 pytestmark = pytest.mark.gpu
 
@@ -20,31 +20,6 @@ GUARD = 0x5A5A5A5A5A5A5A5A
 
 
 # ---- the forward sequences as indexed, and brute force over them --------------------------------------------------------------------------------
-def fastq_reads(name):
-    tab = np.full(256, 5, dtype=np.uint8)
-    for ch, v in zip(b"ACGTacgt", [1, 2, 3, 4, 1, 2, 3, 4]):
-        tab[ch] = v
-    with gzip.open(os.path.join(GOLD, name + ".fq.gz"), "rb") as f:
-        lines = f.read().split(b"\n")
-    return [tab[np.frombuffer(lines[i], dtype=np.uint8)] for i in range(1, len(lines) - 1, 4)]
-
-
-def forward_as_indexed(name):
-    """the reads of the golden FASTQ; an even-length read that is its own reverse complement loses its last base, as `build` trims it"""
-    out = []
-    for r in fastq_reads(name):
-        r = np.ascontiguousarray(r, dtype=np.uint8)
-        out.append(r[:hostlib.trim_palindrome(r)])
-    return out
-
-
-def revcomp(s):
-    out = s[::-1].copy()
-    m = (out >= 1) & (out <= 4)
-    out[m] = 5 - out[m]
-    return out
-
-
 def canonical_windows(seqs, k):
     """the canonical packed k-mer of every N-free k-window of seqs, in no order"""
     sh = (2 * (k - 1 - np.arange(k))).astype(np.uint64)
