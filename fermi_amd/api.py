@@ -42,6 +42,7 @@ KCGRAPH_SPLIT = 1   # FMD_KCGRAPH_SPLIT
 KCGRAPH_STAT_DT = np.dtype(KGRAPH_STAT_DT.descr + [("n_nodes_in", "<u8", 8), ("n_arcs_in", "<u8", 8)])  # fmd_kcgraph_stat_t
 KCARCS_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.POINTER(C.c_uint8)),
                           C.POINTER(C.c_uint8))  # fmd_kcarcs_sink_fn
+KBUBBLE_DT = np.dtype([("src", "<u4"), ("dst", "<u4"), ("first", "<u4", 2), ("len", "<u4", 2)])  # fmd_kbubble_t
 ASEARCH_HIT_DT = np.dtype([("beg", "<u8"), ("cnt", "<u8"), ("query", "<u4"), ("n_sub", "<u4"), ("sub", "<u2", 4)])  # fmd_asearch_hit_t
 ASEARCH_STAT_DT = np.dtype([(f, "<u8") for f in ("n_hits", "n_occ", "n_skipped", "n_truncated", "n_unfinished", "overflow", "n_ext", "widest_level")])  # fmd_asearch_stat_t
 ASEARCH_MAX_SUB, ASEARCH_MAX_LEN, ASEARCH_MIN_CAP, ASEARCH_MAX_CAP = 4, 16383, 4096, 1 << 28   # FMD_ASEARCH_*
@@ -85,6 +86,7 @@ ABI_SYMBOLS = [
     "fmd_kprofile_dev", "fmd_kprofile_batch",
     "fmd_karcs", "fmd_kunitig",
     "fmd_kcarcs", "fmd_kcunitig",
+    "fmd_kcbubble", "fmd_kcbubble_dev",
     "fmd_asearch_work_bytes", "fmd_asearch_bound_dev", "fmd_asearch_dev", "fmd_asearch_batch",
     "fmd_esearch_work_bytes", "fmd_esearch_dev", "fmd_esearch_batch",
 ]
@@ -124,6 +126,11 @@ class KCUnitigC(C.Structure):
     _fields_ = [("n_nodes", C.c_uint64), ("n_unitigs", C.c_uint64), ("n_idx", C.c_int32), ("reserved", C.c_int32)] + \
                [(f, C.c_void_p) for f in ("kmer", "count", "arcs", "uarcs", "pattern", "unitig", "offset", "orient", "u_nodes", "u_first", "u_flags", "u_count",
                                           "u_present", "u_pattern")] + [("stat", KCGraphStatC)]
+
+
+class KCBubbleC(C.Structure):
+    """fmd_kcbubble_t"""
+    _fields_ = [("g", KCUnitigC), ("n_forks", C.c_uint64), ("n_bubbles", C.c_uint64), ("bubble", C.c_void_p), ("ms_bubble", C.c_double)]
 
 
 def _kcgraph_stat(st, n_idx):
@@ -256,6 +263,8 @@ def _configure(L):
     L.fmd_kunitig.argtypes = [vp, C.c_int, C.c_int, C.c_uint64, C.POINTER(KUnitigC)]
     L.fmd_kcarcs.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_uint64, vp, vp, C.POINTER(KCGraphStatC)]
     L.fmd_kcunitig.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_uint, C.c_uint64, C.POINTER(KCUnitigC)]
+    L.fmd_kcbubble.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_uint32, C.c_uint64, C.POINTER(KCBubbleC)]
+    L.fmd_kcbubble_dev.argtypes = [vp, C.c_int, C.c_uint64, vp, vp, C.c_uint32, C.c_int, u64p, u64p, C.POINTER(vp)]
     L.fmd_asearch_work_bytes.restype = sz; L.fmd_asearch_work_bytes.argtypes = [sz, C.c_uint64]
     L.fmd_asearch_bound_dev.argtypes = [vp, vp, sz, vp, u64p, vp]
     L.fmd_asearch_dev.argtypes = [vp, vp, sz, vp, u64p, vp, C.c_int, C.c_uint32, C.c_uint32, vp, C.c_uint64, u64p, vp, vp, sz]
@@ -895,22 +904,131 @@ def kmer_joint_unitigs(indexes, k, min_occ=1, split=False, cap=0, with_stat=Fals
     g = KCUnitigC()
     try:
         check(lib().fmd_kcunitig(n_idx, _handles(indexes), int(k), int(min_occ), KCGRAPH_SPLIT if split else 0, int(cap), C.byref(g)))
-        arrays = {}
-        for name, field, dt in KCUnitigs.NODE + KCUnitigs.UNITIG:
-            n = int(g.n_nodes if (name, field, dt) in KCUnitigs.NODE else g.n_unitigs)
-            wide = name in ("counts", "arcs", "u_count", "u_present")
-            a = np.zeros(n * n_idx if wide else n, dtype=dt)
-            if n:
-                C.memmove(_ptr(a), getattr(g, field), a.nbytes)
-            if name in ("counts", "arcs"):
-                a = a.reshape(n_idx, n).T               # columns n_nodes apart
-            arrays[name] = a
+        out = _kcunitigs_copied(g, k, n_idx)
     finally:
-        for _, field, _ in KCUnitigs.NODE + KCUnitigs.UNITIG:
-            lib().fmd_host_free(getattr(g, field))
-    out = KCUnitigs(k, n_idx, **arrays)
+        _kcunitig_free(g)
     if with_stat:
         out.stat = _kcgraph_stat(g.stat, n_idx)
+    return out
+
+
+def _kcunitigs_copied(g, k, n_idx):
+    """the arrays of a KCUnitigC the library filled, copied into a KCUnitigs"""
+    arrays = {}
+    for name, field, dt in KCUnitigs.NODE + KCUnitigs.UNITIG:
+        n = int(g.n_nodes if (name, field, dt) in KCUnitigs.NODE else g.n_unitigs)
+        wide = name in ("counts", "arcs", "u_count", "u_present")
+        a = np.zeros(n * n_idx if wide else n, dtype=dt)
+        if n:
+            C.memmove(_ptr(a), getattr(g, field), a.nbytes)
+        if name in ("counts", "arcs"):
+            a = a.reshape(n_idx, n).T               # columns n_nodes apart
+        arrays[name] = a
+    return KCUnitigs(k, n_idx, **arrays)
+
+
+def _kcunitig_free(g):
+    for _, field, _ in KCUnitigs.NODE + KCUnitigs.UNITIG:
+        lib().fmd_host_free(getattr(g, field))
+
+
+def _bubbles_copied(ptr, n):
+    out = np.zeros(int(n), dtype=KBUBBLE_DT)
+    if n:
+        C.memmove(_ptr(out), ptr, out.nbytes)
+    return out
+
+
+def kmer_joint_bubbles(indexes, k, min_occ=1, max_len=0, cap=0, with_stat=False):
+    """fmd_kcbubble: (KCUnitigs, bubbles): the unsplit compaction of kmer_joint_unitigs and the simple variant bubbles of its graph (include/fmd_hip.h, kbubble)
+    as a KBUBBLE_DT array ascending by src -- src, dst, first[2], len[2], nodes oriented as 2 * id + o.  max_len: only bubbles whose branches have at most
+    that many nodes (0 = any).  The graph's n_forks is the number of ports with exactly two right arcs; with_stat fills its .stat, ms_bubble included."""
+    n_idx = len(indexes)
+    o = KCBubbleC()
+    try:
+        check(lib().fmd_kcbubble(n_idx, _handles(indexes), int(k), int(min_occ), int(max_len), int(cap), C.byref(o)))
+        g = _kcunitigs_copied(o.g, k, n_idx)
+        bubbles = _bubbles_copied(o.bubble, o.n_bubbles)
+    finally:
+        _kcunitig_free(o.g)
+        lib().fmd_host_free(o.bubble)
+    g.n_forks = int(o.n_forks)
+    if with_stat:
+        g.stat = _kcgraph_stat(o.g.stat, n_idx)
+        g.stat["n_forks"] = int(o.n_forks); g.stat["n_bubbles"] = int(o.n_bubbles); g.stat["ms_bubble"] = float(o.ms_bubble)
+    return g, bubbles
+
+
+def kmer_bubbles_dev(index, k, kmers, uarcs, max_len=0, grid=0):
+    """fmd_kcbubble_dev: (n_forks, bubbles) of the graph given by its ascending canonical k-mers and arc bytes, uploaded to index's GPU; the bubble kernels run
+    on `grid` blocks of 256 threads (0 = the library's choice)."""
+    kmers = np.ascontiguousarray(kmers, dtype=np.uint64); uarcs = np.ascontiguousarray(uarcs, dtype=np.uint8)
+    if len(kmers) != len(uarcs):
+        raise ValueError("kmer_bubbles_dev: %d k-mers and %d arc bytes" % (len(kmers), len(uarcs)))
+    L = lib()
+    bufs = []
+    nf, nb, ptr = C.c_uint64(), C.c_uint64(), C.c_void_p()
+    try:
+        for a in (kmers, uarcs):
+            p = C.c_void_p()
+            check(L.fmd_dev_malloc(index.device, max(a.nbytes, 16), C.byref(p)))
+            bufs.append(p)
+            check(L.fmd_memcpy_h2d(p, _ptr(a), a.nbytes, None))
+        check(L.fmd_kcbubble_dev(index.h, int(k), len(kmers), bufs[0], bufs[1], int(max_len), int(grid), C.byref(nf), C.byref(nb), C.byref(ptr)))
+        out = _bubbles_copied(ptr, nb.value)
+    finally:
+        L.fmd_host_free(ptr)
+        for p in bufs:
+            L.fmd_dev_free(p)
+    return int(nf.value), out
+
+
+def bubble_alleles(g, bubbles):
+    """Per record of kmer_joint_bubbles over the KCUnitigs g: (type, left flank, allele_0, allele_1, right flank) as `fermi-amd kbubble` prints them.  P_b =
+    text(src) + the last base of every node of branch b + the last base of text(dst); the longest common prefix of P_0 and P_1 is stripped, then the longest
+    common suffix of the rest; an empty allele is "-".  SNP: both 1 base; MNP: equal lengths above 1; INDEL: exactly one empty; COMPLEX: anything else."""
+    k, mask = g.k, (1 << (2 * g.k)) - 1
+
+    def comp(w):                                        # the reverse complement of a packed k-mer
+        r = 0
+        for _ in range(k):
+            r, w = r << 2 | (3 - (w & 3)), w >> 2
+        return r
+
+    def word(u):
+        x = int(g.kmers[u >> 1])
+        return comp(x) if u & 1 else x
+
+    def right(u):
+        a = int(g.uarcs[u >> 1])
+        return [c for c in range(4) if (a >> (4 + 3 - c) & 1 if u & 1 else a >> c & 1)]
+
+    def follow(u, c):
+        v = (word(u) << 2 | c) & mask
+        r = comp(v)
+        j = int(np.searchsorted(g.kmers, np.uint64(min(v, r))))
+        return 2 * j + (0 if v < r else 1)
+
+    out = []
+    for b in bubbles:
+        P = []
+        for br in (0, 1):
+            s = "".join("ACGT"[word(int(b["src"])) >> (2 * (k - 1 - i)) & 3] for i in range(k))
+            v = int(b["first"][br])
+            for _ in range(int(b["len"][br])):
+                s += "ACGT"[word(v) & 3]
+                v = follow(v, right(v)[0])
+            P.append(s + "ACGT"[word(v) & 3])
+        pre = 0
+        while pre < min(len(P[0]), len(P[1])) and P[0][pre] == P[1][pre]:
+            pre += 1
+        R = [P[0][pre:], P[1][pre:]]
+        suf = 0
+        while suf < min(len(R[0]), len(R[1])) and R[0][len(R[0]) - 1 - suf] == R[1][len(R[1]) - 1 - suf]:
+            suf += 1
+        a = [r[:len(r) - suf] for r in R]
+        kind = "SNP" if len(a[0]) == len(a[1]) == 1 else "MNP" if len(a[0]) == len(a[1]) else "INDEL" if (not a[0]) != (not a[1]) else "COMPLEX"
+        out.append((kind, P[0][pre - k:pre], a[0] or "-", a[1] or "-", R[0][len(R[0]) - suf:][:k]))
     return out
 
 

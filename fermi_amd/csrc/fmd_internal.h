@@ -100,12 +100,20 @@ int fmd_kcount_levels(fmd_dev *h, hipStream_t st, int depth, int min_occ, int ro
 // compactable only between nodes with equal bytes (FMD_KCGRAPH_SPLIT).  d_work = fmd_kgraph_compact_bytes(n) bytes and more; d_ctr = 128 u64 words whose
 // words 4, 5 and 16.. are zero.  Null stream; returns after the device is done.  The labels stay in d_work: label = the smallest node id of the chain,
 // off, oc = orient | 2 on a cycle.  fmd_kgraph_number_host turns downloaded labels into unitig ids and fills the per-unitig arrays (malloc'ed).
-struct FmdKgLabels { uint32_t *label, *off; uint8_t *oc; uint64_t n_links, n_cycles, n_rounds; double ms_links, ms_label; };
+// st = the settled doubling state of the 2 n ports, in d_work too (k_kgraph_round: x = the free port at the chain's end, y = the steps there, w = 1), and
+// st_spare = the doubling's other buffer, 32 n bytes that nobody reads any more: what the bubble stage (fmd_kbubble.hip) takes.
+struct FmdKgLabels { uint32_t *label, *off; uint8_t *oc; uint64_t n_links, n_cycles, n_rounds; double ms_links, ms_label; const uint4 *st; void *st_spare; };
 size_t fmd_kgraph_compact_bytes(uint64_t n);
 int fmd_kgraph_compact_dev(int k, uint64_t n, const uint64_t *d_kmer, const uint8_t *d_arcs, const uint8_t *d_pat, void *d_work, size_t work_bytes,
                            unsigned long long *d_ctr, FmdKgLabels *out);
 int fmd_kgraph_number_host(uint64_t n, uint32_t *unitig, const uint32_t *offset, uint8_t *orient, uint64_t *n_unitigs, uint32_t **u_nodes, uint32_t **u_first,
                            uint8_t **u_flags);
+
+// kbubble's stage (fmd_kbubble.hip) on a graph that fmd_kgraph_compact_dev has just compacted WITHOUT the split rule (d_pat == NULL) and whose work area is
+// still there: the simple bubbles of include/fmd_hip.h, ascending by src, in *bubble (malloc'ed; NULL when there are none).  grid = the blocks of 256
+// threads (0: as the link kernel's).  Scratch comes from h's cache.  Null stream; returns after the device is done; *ms = its host wall time.
+int fmd_kbubble_stage_dev(fmd_dev *h, int k, uint64_t n, const uint64_t *d_kmer, const uint8_t *d_arcs, const FmdKgLabels *lb, uint32_t max_len, int grid,
+                          uint64_t *n_forks, uint64_t *n_bubbles, fmd_kbubble_t **bubble, double *ms);
 
 // next zeroed work-queue head for a persistent launch on `stream`
 uint32_t *fmd_next_queue(fmd_dev *h, hipStream_t stream);

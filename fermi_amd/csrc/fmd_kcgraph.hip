@@ -444,7 +444,9 @@ static void kc_free_out(fmd_kcunitig_t *o)
     memset(o, 0, sizeof(*o));
 }
 
-static int kc_kcunitig(int n_idx, fmd_dev_t *const *h, int k, int min_occ, unsigned flags, uint64_t cap, fmd_kcunitig_t *out)
+// bub != NULL (fmd_kcbubble; flags = 0): the bubble stage runs on the graph before the device lets go of it
+static int kc_kcunitig(int n_idx, fmd_dev_t *const *h, int k, int min_occ, unsigned flags, uint64_t cap, fmd_kcunitig_t *out, fmd_kcbubble_t *bub = nullptr,
+                       uint32_t max_len = 0)
 {
     if (flags & ~FMD_KCGRAPH_SPLIT) return FMD_E_ARG;
     FMD_TRY(kc_check(n_idx, h, k, min_occ, cap));
@@ -500,6 +502,7 @@ static int kc_kcunitig(int n_idx, fmd_dev_t *const *h, int k, int min_occ, unsig
     free(pt);
     FMD_HIP_TRY(e);
     out->stat.g.ms_label += kc_ms(t0);
+    if (bub) FMD_TRY(fmd_kbubble_stage_dev(h[0], k, n, g.kmer(), g.uarcs(), &lb, max_len, 0, &bub->n_forks, &bub->n_bubbles, &bub->bubble, &bub->ms_bubble));
     return FMD_OK;
 }
 extern "C" int fmd_kcunitig(int n_idx, fmd_dev_t *const *h, int k, int min_occ, unsigned flags, uint64_t cap, fmd_kcunitig_t *out)
@@ -510,5 +513,16 @@ extern "C" int fmd_kcunitig(int n_idx, fmd_dev_t *const *h, int k, int min_occ, 
     try { rc = kc_kcunitig(n_idx, h, k, min_occ, flags, cap, out); }
     catch (const std::bad_alloc &) { rc = FMD_E_NOMEM; }
     if (rc) kc_free_out(out);
+    return rc;
+}
+
+extern "C" int fmd_kcbubble(int n_idx, fmd_dev_t *const *h, int k, int min_occ, uint32_t max_len, uint64_t cap, fmd_kcbubble_t *out)
+{
+    if (!out) return FMD_E_ARG;
+    memset(out, 0, sizeof(*out));
+    int rc;
+    try { rc = kc_kcunitig(n_idx, h, k, min_occ, 0, cap, &out->g, out, max_len); }
+    catch (const std::bad_alloc &) { rc = FMD_E_NOMEM; }
+    if (rc) { kc_free_out(&out->g); free(out->bubble); memset(out, 0, sizeof(*out)); }
     return rc;
 }

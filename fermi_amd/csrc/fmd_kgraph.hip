@@ -385,6 +385,7 @@ int fmd_kgraph_compact_dev(int k, uint64_t n, const uint64_t *d_kmer, const uint
     out->n_cycles = hc[KG_CYC];
     out->n_rounds = (uint64_t)round;
     out->label = label; out->off = off; out->oc = oc;
+    out->st = sts[cur]; out->st_spare = sts[cur ^ 1];
     return FMD_OK;
 }
 

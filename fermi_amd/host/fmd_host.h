@@ -459,6 +459,19 @@ void fmdh_kcgraph_print_arcs(FILE *out, int k, int n_idx, uint32_t min_occ, uint
                              const uint8_t *uarcs);
 void fmdh_kcgraph_free(fmd_kcunitig_t *g);
 int fmdh_main_kcgraph(int argc, char *argv[]);
+/* kbubble_cmd.c: `fermi-amd kbubble [-k 21] [-o 2] [-L 0] [-d] [-g GPU] <a.fmd> [<b.fmd> ...]`: the simple variant bubbles of kcgraph's graph (include/fmd_hip.h,
+ * kbubble): SM <nodes> <unitigs> <forks> <bubbles>, then per bubble BB <index> <type> <left flank> <allele 0> <allele 1> <right flank> <len 0> <len 1> <unitig 0>
+ * <unitig 1> kc:B:I,<2 N count sums> kn:B:I,<2 N present nodes> GT:Z:<a code per colour>; -d: only the bubbles that not every colour holds alike.  Usage and
+ * unreadable-file errors return 1 before the device is looked for.  No GPU behind:
+ * fmdh_kcbubble_host: the bubbles of fmd_kcbubble from g's n_nodes, kmer and uarcs alone -- none of the unitig labels --, every branch walked node by node by one
+ *   thread with a binary search per step: oracle and yardstick.  *bubble malloc'ed (fmd_host_free), NULL when *n = 0; 1 without memory, 2 for bad arguments
+ * fmdh_kbubble_print: the BB lines of n records over a graph with all its arrays set.  P_b = text(s) + the last base of every node of branch b + the last base of
+ *   text(t); the longest common prefix of P_0 and P_1 (k bases or more) is stripped, then the longest common suffix of what is left: the remainders are the alleles
+ *   (`-` when empty), SNP = both 1 base, MNP = equal lengths above 1, INDEL = exactly one empty, COMPLEX otherwise; left flank = the last k bases of the prefix,
+ *   right flank = the first min(k, length) bases of the suffix.  1 without memory, 2 for bad arguments or a record that is no walk of the graph */
+int fmdh_kcbubble_host(int k, const fmd_kcunitig_t *g, uint32_t max_len, uint64_t *n_forks, uint64_t *n, fmd_kbubble_t **bubble);
+int fmdh_kbubble_print(FILE *out, int k, const fmd_kcunitig_t *g, uint64_t n, const fmd_kbubble_t *b, int differing_only);
+int fmdh_main_kbubble(int argc, char *argv[]);
 /* asearch_cmd.c: `fermi-amd asearch [-g GPU] [-d 1] [-b] [-m 1000] [-l] [-M 1000] [-r reads.rank] <reads.fmd> <query.fa>`: the patterns within -d substitutions of
  * every query that occur (fmd_asearch_batch), with -l the reads that hold each (fmd_locate_batch + fmdh_locate_hits); usage and unreadable-file errors return 1
  * before the device is looked for.  No GPU behind:

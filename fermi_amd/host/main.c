@@ -405,6 +405,7 @@ int main(int argc, char *argv[])
         fprintf(stderr, "         kprofile   k-mer counts along query sequences: how often each of their k-mers occurs in the reads of each index\n");
         fprintf(stderr, "         kgraph     the de Bruijn graph of the counted k-mers, compacted to unitigs (GFA)\n");
         fprintf(stderr, "         kcgraph    the coloured de Bruijn graph of up to 8 indexes: unitigs with per-index counts, sample-specific sequence\n");
+        fprintf(stderr, "         kbubble    the variant bubbles of that graph: SNPs and short indels between the indexes, or within one\n");
         fprintf(stderr, "         asearch    the patterns within a few substitutions of each query that occur, with count and interval\n");
         fprintf(stderr, "         esearch    the patterns within a few edits -- insertions and deletions included -- of each query that occur\n");
         fprintf(stderr, "         chkbwt     print / check the BWT held on the GPU (fermi chkbwt)\n");
@@ -428,7 +429,7 @@ int main(int argc, char *argv[])
     if (strcmp(argv[1], "cnt2qual") == 0) return fmdh_main_cnt2qual(argc - 1, argv + 1);
     if (strcmp(argv[1], "clean") == 0) return fmdh_main_clean(argc - 1, argv + 1);
     { const int node = stay_on_one_node(argv[1]); if (timing && node >= 0) fprintf(stderr, "[M::main] the process stays on NUMA node %d\n", node); }
-    if (strcmp(argv[1], "fltuniq") != 0 && strcmp(argv[1], "scaf") != 0 && strcmp(argv[1], "ropebwt") != 0 && strcmp(argv[1], "msearch") != 0 && strcmp(argv[1], "locate") != 0 && strcmp(argv[1], "kcount") != 0 && strcmp(argv[1], "kcmp") != 0 && strcmp(argv[1], "kmat") != 0 && strcmp(argv[1], "kprofile") != 0 && strcmp(argv[1], "kgraph") != 0 && strcmp(argv[1], "kcgraph") != 0 && strcmp(argv[1], "asearch") != 0 && strcmp(argv[1], "esearch") != 0 && fmd_device_count() <= 0) {   /* (fltuniq, scaf, ropebwt, msearch, locate, kcount, kcmp, kmat, kprofile, kgraph, kcgraph, asearch and esearch look at their arguments first, as the reference does, then for the device) */
+    if (strcmp(argv[1], "fltuniq") != 0 && strcmp(argv[1], "scaf") != 0 && strcmp(argv[1], "ropebwt") != 0 && strcmp(argv[1], "msearch") != 0 && strcmp(argv[1], "locate") != 0 && strcmp(argv[1], "kcount") != 0 && strcmp(argv[1], "kcmp") != 0 && strcmp(argv[1], "kmat") != 0 && strcmp(argv[1], "kprofile") != 0 && strcmp(argv[1], "kgraph") != 0 && strcmp(argv[1], "kcgraph") != 0 && strcmp(argv[1], "kbubble") != 0 && strcmp(argv[1], "asearch") != 0 && strcmp(argv[1], "esearch") != 0 && fmd_device_count() <= 0) {   /* (fltuniq, scaf, ropebwt, msearch, locate, kcount, kcmp, kmat, kprofile, kgraph, kcgraph, kbubble, asearch and esearch look at their arguments first, as the reference does, then for the device) */
         fprintf(stderr, "[E::main] %s\n", fmd_strerror(FMD_E_NODEV));
         return 1;
     }
@@ -453,6 +454,7 @@ int main(int argc, char *argv[])
     else if (strcmp(argv[1], "kprofile") == 0) rc = fmdh_main_kprofile(argc - 1, argv + 1);
     else if (strcmp(argv[1], "kgraph") == 0) rc = fmdh_main_kgraph(argc - 1, argv + 1);
     else if (strcmp(argv[1], "kcgraph") == 0) rc = fmdh_main_kcgraph(argc - 1, argv + 1);
+    else if (strcmp(argv[1], "kbubble") == 0) rc = fmdh_main_kbubble(argc - 1, argv + 1);
     else if (strcmp(argv[1], "asearch") == 0) rc = fmdh_main_asearch(argc - 1, argv + 1);
     else if (strcmp(argv[1], "esearch") == 0) rc = fmdh_main_esearch(argc - 1, argv + 1);
     else if (strcmp(argv[1], "correct") == 0) rc = main_correct(argc - 1, argv + 1);

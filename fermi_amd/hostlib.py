@@ -102,6 +102,8 @@ def lib():
         L.fmdh_kcgraph_print_fasta.argtypes = [vp, C.c_int, vp, C.c_int, C.c_uint]
         L.fmdh_kcgraph_print_arcs.restype = None; L.fmdh_kcgraph_print_arcs.argtypes = [vp, C.c_int, C.c_int, C.c_uint32, C.c_uint64, C.c_uint64, vp, vp, vp, vp]
         L.fmdh_kcgraph_free.restype = None; L.fmdh_kcgraph_free.argtypes = [vp]
+        L.fmdh_kcbubble_host.argtypes = [C.c_int, vp, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(vp)]
+        L.fmdh_kbubble_print.argtypes = [vp, C.c_int, vp, C.c_uint64, vp, C.c_int]
         L.fmdh_asearch_pattern.argtypes = [vp, C.c_uint32, vp, vp]
         L.fmdh_esearch_cigar.restype = vp; L.fmdh_esearch_cigar.argtypes = [vp, C.c_uint32, vp, C.c_uint32, C.POINTER(C.c_uint32)]
         L.fmdh_esearch_rankmap.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_uint64)]
@@ -452,6 +454,46 @@ def kcgraph_arcs_text(k, min_occ, kmers, counts, arcs, uarcs):
         raise ValueError("kcgraph_arcs_text: arrays of different shapes")
     d = lambda a: a.ctypes.data if a.size else None
     return _printed(lambda fp: lib().fmdh_kcgraph_print_arcs(fp, int(k), counts.shape[1], int(min_occ), n, n, d(kmers), d(counts), d(arcs), d(uarcs)))
+
+
+def kcbubble_host(g, max_len=0):
+    """fmdh_kcbubble_host: (n_forks, bubbles) of the graph of an api.KCUnitigs -- its k-mers and union arc bytes alone, none of its labels --, every branch walked
+    node by node by one thread on the host; bubbles is an api.KBUBBLE_DT array ascending by src (include/fmd_hip.h, kbubble)."""
+    from . import api
+    c = g.as_c()
+    nf, n, ptr = C.c_uint64(), C.c_uint64(), C.c_void_p()
+    rc = lib().fmdh_kcbubble_host(int(g.k), C.addressof(c), int(max_len), C.byref(nf), C.byref(n), C.byref(ptr))
+    if rc == 1:
+        raise MemoryError("fmdh_kcbubble_host")
+    if rc:
+        raise ValueError("kcbubble_host: k = %d with %d nodes" % (g.k, len(g.kmers)))
+    try:
+        out = np.zeros(n.value, dtype=api.KBUBBLE_DT)
+        if n.value:
+            C.memmove(out.ctypes.data, ptr, out.nbytes)
+    finally:
+        _libc.free(ptr)
+    return int(nf.value), out
+
+
+def kbubble_text(g, bubbles, differing_only=False):
+    """fmdh_kbubble_print: the BB lines `fermi-amd kbubble [-d]` prints for the records `bubbles` (api.KBUBBLE_DT) over an api.KCUnitigs, as one str."""
+    from . import api
+    bubbles = np.ascontiguousarray(bubbles, dtype=api.KBUBBLE_DT)
+
+    def call(fp):
+        c = g.as_c()
+        rc = lib().fmdh_kbubble_print(fp, g.k, C.addressof(c), len(bubbles), bubbles.ctypes.data if len(bubbles) else None, int(bool(differing_only)))
+        if rc == 1:
+            raise MemoryError("fmdh_kbubble_print")
+        if rc:
+            raise ValueError("kbubble_text: the records are not bubbles of this graph")
+    return _printed(call)
+
+
+def kbubble_sm_text(g, n_forks, n_bubbles):
+    """the SM line of `fermi-amd kbubble`"""
+    return "SM\t%d\t%d\t%d\t%d\n" % (len(g.kmers), len(g.u_nodes), n_forks, n_bubbles)
 
 
 _libc = C.CDLL(None)

@@ -408,6 +408,37 @@ typedef struct {
 int fmd_kcarcs(int n_idx, fmd_dev_t *const *h, int k, int min_occ, uint64_t cap, fmd_kcarcs_sink_fn sink, void *ctx, fmd_kcgraph_stat_t *stat);
 int fmd_kcunitig(int n_idx, fmd_dev_t *const *h, int k, int min_occ, unsigned flags, uint64_t cap, fmd_kcunitig_t *out);
 
+/* ---- kbubble (no reference counterpart): the simple variant bubbles of kcgraph's graph ------------------------------------------------------
+ * Everything is defined on the node graph of kcgraph: its nodes, its UNION arc byte, k odd in 3..31, min_occ >= 1, 1 <= n_idx <= 8 as there.
+ * ORIENTED NODES: 2 * id + o; o = 0 is the canonical k-mer x, o = 1 is rc(x) -- the port numbering of the compaction: port p leaves that oriented
+ * node through its right end.  The right arcs of (id, 0) are uarcs & 15, those of (id, 1) the high nibble with its bits reversed; the left degree
+ * of u is the right degree of u ^ 1; follow(u, c) is the oriented node of text(u)[1:] + c.
+ * SIMPLE BUBBLE (s, t, A, B): s is an oriented node with exactly two right arcs, bases c0 < c1.  Branch A starts at a_0 = follow(s, c0), branch B
+ * at b_0 = follow(s, c1).  A branch is a chain v_0 .. v_{m-1}, m >= 1: every v_j has left degree 1 and right degree 1, and v_{j+1} is v_j's only
+ * successor; it ends at the first successor whose left degree is not 1, its TARGET (a first node whose left degree is not 1 makes no branch: there
+ * are no empty branches).  Both branches have the same oriented target t, t has exactly two left arcs, id(t) != id(s), and with max_len > 0 both
+ * branches have at most max_len nodes.  Hence: neither s nor t lies in a branch, the branches share no node, and in the UNSPLIT compaction each
+ * branch is exactly one whole unitig.  Every bubble is met twice -- from s, and from t ^ 1 with the branches reversed -- and REPORTED once, from the
+ * side with id(s) < id(t).
+ * RECORD: src = s, dst = t, first[b] = the oriented first node of branch b, len[b] = its nodes; branch 0 leaves s by the smaller base in s's
+ * orientation.  Records ascend by src (a port is the source of at most one bubble).
+ * HELD: colour i holds branch b iff every node of it has pattern bit i: u_present[u * n_idx + i] == u_nodes[u] for its unitig u = unitig[first[b]
+ * >> 1]; the branch's count sum in colour i is u_count[u * n_idx + i].
+ * NOT LOOKED FOR: a bubble with an empty branch (s -> t directly), branches that branch themselves (a tip on an allele, nested variants,
+ * superbubbles); the graph is not cleaned.
+ * fmd_kcbubble: g = exactly what fmd_kcunitig(n_idx, h, k, min_occ, 0, cap, &g) returns; n_forks = the ports with exactly two right arcs; bubble
+ * is malloc'ed (fmd_host_free), NULL with n_bubbles = 0 when there are none and after an error; ms_bubble = the host wall time of the stage, ended
+ * by a wait for the device.  Errors and argument rules are fmd_kcunitig's (flags = 0).  The stage runs on the graph while it is still on the
+ * device, one thread per port, and reads a branch's far end and length from the settled pointer-doubling state of the compaction: it does not walk.
+ * fmd_kcbubble_dev: the same stage for a graph already on h's device -- d_kmer the n ascending canonical k-mers, d_uarcs their arc bytes; link
+ * resolution and doubling are run first (scratch from h's cache) -- on `grid` blocks of 256 threads, 0 = fmd_kcbubble's choice.  n = 0 gives no
+ * bubble; FMD_E_ARG for a null pointer, k even or outside 3..31, n > FMD_KGRAPH_MAX_NODES or grid < 0. */
+typedef struct { uint32_t src, dst, first[2], len[2]; } fmd_kbubble_t;
+typedef struct { fmd_kcunitig_t g; uint64_t n_forks, n_bubbles; fmd_kbubble_t *bubble; double ms_bubble; } fmd_kcbubble_t;
+int fmd_kcbubble(int n_idx, fmd_dev_t *const *h, int k, int min_occ, uint32_t max_len, uint64_t cap, fmd_kcbubble_t *out);
+int fmd_kcbubble_dev(fmd_dev_t *h, int k, uint64_t n, const uint64_t *d_kmer, const uint8_t *d_uarcs, uint32_t max_len, int grid, uint64_t *n_forks,
+                     uint64_t *n_bubbles, fmd_kbubble_t **bubble);
+
 /* ---- asearch (no reference counterpart): search with up to max_sub substitutions ---------------------------------------------------
  * Query i is seqs[off[i] .. off[i+1]) in nt6, L bases (the contract of fmd_bsearch_dev: the bytes 4-byte aligned and readable to the next
  * multiple of 4).  A PATTERN P is a string over A/C/G/T of length L; it is a HIT of the query when occ(P) > 0 and P differs from the query in
