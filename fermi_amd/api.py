@@ -1234,26 +1234,39 @@ DevIndex.reach = _reach
 
 
 def _smem_chain(self, seq, max_len=256, self_match=0, full_only=False):
-    """fm6_smem of one long sequence, exactly as the reference walks it: reach -> chain positions ->
-    one fm6_smem1_core item per position, results concatenated in chain order."""
+    """fm6_smem of one long sequence, exactly as the reference walks it.  self_match=0: reach -> chain positions -> one
+    fm6_smem1_core item per position, results concatenated in chain order.  With self_match the chain's step is not the plain
+    reach (the forward sweep stops where fewer than two occurrences are left), so the sequence is one window [0, len) that walks
+    the chain inside the kernel, as `exact -s` does on a long query.  max_len bounds the length of a match."""
     seq = np.ascontiguousarray(seq, dtype=np.uint8)
     L = len(seq)
+    if L == 0:
+        return np.zeros(0, dtype=INTV_DT)
     flat = np.zeros(L + 8, dtype=np.uint8); flat[:L] = seq
-    reach = self.reach(flat[:L + 1])
-    pos = []
-    x = 0
-    while x < L:
-        pos.append(x)
-        x += int(reach[x]) if reach[x] else 1
+    if self_match:
+        pos, stop = [0], [L]
+    else:
+        reach = self.reach(flat[:L + 1])
+        pos = []
+        x = 0
+        while x < L:
+            pos.append(x)
+            x += int(reach[x]) if reach[x] else 1
+        stop = np.array(pos) + 1
     n = len(pos)
     wins = np.zeros(n, dtype=SMEM_WIN_DT)
-    wins["seq_len"] = L; wins["start"] = pos; wins["stop"] = np.array(pos) + 1; wins["reserved"] = 1 if full_only else 0
+    wins["seq_len"] = L; wins["start"] = pos; wins["stop"] = stop; wins["reserved"] = 1 if full_only else 0
     max_mem = 2 * max_len + 2
-    mem = np.zeros((n, max_mem), dtype=INTV_DT); n_mem = np.zeros(n, dtype=np.uint32)
-    check(lib().fmd_smem_win_batch(self.h, n, _ptr(flat), L, _ptr(wins), self_match, max_len, max_mem, _ptr(mem), _ptr(n_mem)))
+    for _ in range(2):
+        mem = np.zeros((n, max_mem), dtype=INTV_DT); n_mem = np.zeros(n, dtype=np.uint32)
+        check(lib().fmd_smem_win_batch(self.h, n, _ptr(flat), L, _ptr(wins), self_match, max_len, max_mem, _ptr(mem), _ptr(n_mem)))
+        need = int((n_mem & 0x7fffffff).max())
+        if not (n_mem >> 31).any() or need <= max_mem:
+            break
+        max_mem = need   # rows that were too short: the low bits are the true counts (a whole chain in one window has no bound known up front)
     if (n_mem >> 31).any():
-        raise FmdError("smem_chain: capacity exceeded in %d calls" % int((n_mem >> 31).sum()))
-    return np.concatenate([mem[i, :n_mem[i]] for i in range(n)]) if n else np.zeros(0, dtype=INTV_DT)
+        raise FmdError("smem_chain: capacity exceeded in %d calls (raise max_len)" % int((n_mem >> 31).sum()))
+    return np.concatenate([mem[i, :n_mem[i]] for i in range(n)])
 
 
 DevIndex.smem_chain = _smem_chain

@@ -568,7 +568,15 @@ int fmd_reach_batch(fmd_dev_t *h, size_t n_bytes, const uint8_t *seqs, uint32_t 
  * (smem.c:13-80); what `fermi exact [-s]` prints (cmd.c:319-327, smem.c:412-418).
  * mem: n rows of max_mem intervals in the reference's order; info = leftclosed<<63 | beg<<32 | end
  * (FM_MASK30 fields, smem.c:63).  n_mem[i] = number of SMEMs of read i; bit 31 set = the read was
- * longer than max_len or produced more than max_mem SMEMs (row invalid: re-run larger).
+ * longer than max_len or produced more than max_mem SMEMs (row invalid: re-run larger).  The low 31
+ * bits: 0 for a read longer than max_len (nothing was computed, its row is not touched); else, when
+ * only max_mem was too small, the TRUE number of SMEMs of the read, so the caller knows the max_mem that
+ * fits.  (Windows: a candidate list that outgrew 2 * max_len + 2 entries also sets bit 31, and the low
+ * bits then count what an incomplete list gave: meaningless.)  An overflowing read writes nothing outside
+ * its own row and its lane's part of the work area; the other reads of the launch are unaffected.
+ * A start the reference leaves undefined -- a base q[x] the index does not hold, or (self_match) a forward
+ * sweep that pushes no interval because every occurrence of q[x] ends its sequence, where fm6_smem1_core
+ * reads a[0] of an empty vector -- ends the read: n_mem = the SMEMs found before it, bit 31 clear.
  * d_seqs: 4-byte aligned and readable up to the next multiple of 4 past off[n] (the kernels read
  * the sequences one aligned word at a time); same for fmd_bsearch_dev. */
 size_t fmd_smem_work_bytes(size_t n, uint32_t max_len);

@@ -59,7 +59,8 @@ def lib():
         L.orc_backward_search_batch.argtypes = [P, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         L.orc_traverse.restype = C.c_void_p; L.orc_traverse.argtypes = [P, C.c_int]
         L.orc_smem.restype = C.c_int; L.orc_smem.argtypes = [P, C.c_int, C.c_void_p, C.POINTER(IntvV), C.c_int]
-        L.orc_smem_batch.argtypes = [P, C.c_size_t, C.c_int, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int]
+        L.orc_smem1.restype = C.c_int; L.orc_smem1.argtypes = [P, C.c_int, C.c_void_p, C.c_int, C.POINTER(IntvV), C.c_int]
+        L.orc_smem_batch.argtypes =[P, C.c_size_t, C.c_int, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int]
         L.orc_ec_range.argtypes = [P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.orc_is_contained.restype = C.c_int
         L.orc_is_contained.argtypes = [P, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(IntvV)]
@@ -167,6 +168,15 @@ class OrcIndex:
         out = _take(v)
         _libc.free(v.a)
         return out
+
+    def smem1(self, seq, x, self_match=0):
+        """fm6_smem1 (smem.c:104) at start x: (mem, ret).  Undefined where the index lacks seq[x] or the forward sweep pushes nothing."""
+        seq = np.ascontiguousarray(seq, dtype=np.uint8)
+        v = IntvV(0, 0, None)
+        ret = self.L.orc_smem1(self.e, len(seq), seq.ctypes.data, x, C.byref(v), self_match)
+        out = _take(v)
+        _libc.free(v.a)
+        return out, ret
 
     def overlap(self, seq_id, min_match):
         """Same record as refbind.RefIndex.overlap, computed by the oracle."""

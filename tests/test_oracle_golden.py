@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import orcbind
+import smem_ref
 
 U64 = np.uint64
 
@@ -126,12 +127,7 @@ def test_exact_cli_text(tiny_oracle, gold):
     mcnt1 = int(tiny_oracle.mcnt[1])
     for i, q in enumerate(reads):
         m = tiny_oracle.smem(q, 0)
-        out = [b"SQ\tr%d\t%d\t%d" % (i, len(q), len(m))]
-        for r in m:
-            info = int(r["info"])
-            out.append(b"EM\t%d\t%d\t%d\t%s%s" % (info >> 32 & 0x3fffffff, info & 0x3fffffff, min(int(r["x"][2]), 0xffffffff),
-                                                    b"OT"[info >> 63:(info >> 63) + 1], b"OT"[int(r["x"][1]) < mcnt1:][:1]))
-        assert b"\n".join(out) + b"\n" == want[i], i
+        assert smem_ref.exact_record(b"r%d" % i, len(q), m, mcnt1) == want[i], i
 
 
 @pytest.mark.parametrize("name,key", [("tiny", "l50"), ("tiny", "l30"), ("special", "l20"), ("repeat", "l20"), ("repeat", "l35")])
